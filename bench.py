@@ -10,9 +10,13 @@ random-init weights, per-GPU batch 256, bf16 GEMM operands (fp32 accumulate / re
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-`roofline` (dominant kernel class, algorithmic FLOPs / HIP-event time measured in an instrumented
-pass of the same step) and `cpu_baseline` (the CPU oracle timed on the host cores, N=1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times
+--steps steps and reports them; --full adds the measurements that need runs of their own or other hardware:
+`roofline` (dominant kernel class, algorithmic FLOPs / HIP-event time measured in an instrumented pass of the
+same step), `cpu_baseline` (the CPU oracle timed on the host cores, N=1 only), `config.dense_text` (the same step
+with dense 77-row captions) and `power_sample` (board power / shader clock over the timed steps).
+--dump-outputs DIR writes what the last timed step returned (its losses and a fixed sample of the updated parameters)
+as DIR/<name>.npy.
 """
 import argparse
 import ctypes
@@ -49,15 +53,21 @@ def parse():
                     help="geometry: vit_b32 = the headline metric (BASELINE configs 1-4); vit_l14_336 = BASELINE config 5")
     ap.add_argument("--fp8", type=int, nargs="?", const=3, default=0,
                     help="BASELINE config 5's fp8 MFMA weight path: bit 0 forward GEMMs, bit 1 input-gradient GEMMs (bare --fp8 = 3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra measurements after the timed steps: CPU oracle baseline, dense-text comparison, "
+                         "instrumented roofline pass; and sample board power during them (a plain run only times the step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (its losses and a fixed seeded sample of the updated "
+                         "parameters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the instrumented roofline pass")
     ap.add_argument("--descriptions", type=int, default=1,
                     help="descriptions per image K (1 positive + K-1 hard negatives, BASELINE config 3 uses 5); the "
                          "headline metric is K = 1")
     ap.add_argument("--dense-text", action="store_true",
                     help="run the text tower on all 77 positions of every caption (default: live tokens SOT..EOT only; "
-                         "the default run also reports this dense variant as config.dense_text)")
-    ap.add_argument("--no-dense-compare", action="store_true", help="skip the dense-text comparison run")
+                         "a --full run also reports this dense variant as config.dense_text)")
+    ap.add_argument("--no-dense-compare", action="store_true", help="with --full: skip the dense-text comparison run")
     ap.add_argument("--reuse-captions", action="store_true",
                     help="hand the model the SAME caption tensor every step (its live-token layout is then cached; the "
                          "default gives every step a new tensor, so the per-batch length read-back of real training is "
@@ -245,6 +255,45 @@ class PowerSampler:
         return out or None
 
 
+class OutputDump:
+    """``--dump-outputs DIR``: what a caller of ``train_step`` holds after the last timed step, as .npy files, for comparing
+    two builds output for output.  ``loss_<name>.npy``: the loss dict the last step returned (float64 scalars).
+    ``params_sample.npy``: the updated parameters at a fixed, seeded set of 2^21 positions of their concatenation in name
+    order (ViT-B/32: ~150 M values; float32, 8 MB), gathered per parameter without a copy of the model.
+
+    Both depend on the gradients: over the default 3 + 10 steps the loss falls from 11.16 to 10.87 and the parameters move
+    by ~4.5e-4 (relative L2), against run-to-run spreads of ~2e-5 and ~5e-6.  The gradients and the parameter update
+    themselves are not written: from one state the step's gradients agree to ~2e-8 between runs, but each step re-draws
+    the bf16 rounding of a state that differs in the last bits, so after a few steps they differ by ~1.5 % from run to
+    run, the size of their own bf16 rounding error, and could not be compared output for output."""
+
+    SAMPLES = 1 << 21
+    SEED = 20240601
+
+    def __init__(self, model, out_dir):
+        import numpy as np
+        self.model, self.dir = model, out_dir
+        named = sorted(model.named_parameters(), key=lambda t: t[0])
+        starts = np.concatenate([[0], np.cumsum([p.numel() for _, p in named])]).astype(np.int64)
+        idx = np.sort(np.random.default_rng(self.SEED).choice(int(starts[-1]), size=min(self.SAMPLES, int(starts[-1])),
+                                                              replace=False))
+        dev = next(model.parameters()).device
+        # per parameter, the sampled positions inside it
+        cut = np.searchsorted(idx, starts)
+        self.picks = [(n, torch.from_numpy(idx[cut[i]:cut[i + 1]] - starts[i]).to(dev))
+                      for i, (n, _) in enumerate(named) if cut[i + 1] > cut[i]]
+
+    def write(self, loss_dict):
+        import numpy as np
+        os.makedirs(self.dir, exist_ok=True)
+        params = dict(self.model.named_parameters())
+        out = {"loss_" + k.removeprefix("loss_"): v.detach().double().reshape(()) for k, v in loss_dict.items()}
+        out["params_sample"] = torch.cat([params[n].detach().reshape(-1)[local].float() for n, local in self.picks])
+        for name, t in out.items():
+            np.save(os.path.join(self.dir, name + ".npy"), t.cpu().numpy())
+        log(f"outputs of the last timed step -> {self.dir}: {', '.join(sorted(out))}")
+
+
 def ms_per_step_tmp(dt, steps):
     return dt / steps * 1e3
 
@@ -394,6 +443,7 @@ def main():
             dt = float(t)
         return dt, out
 
+    dump = OutputDump(model, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     for _ in range(args.warmup):
         ld = step()
     if args.cu_hog:          # calibrate the hog's duration on the un-hogged step, then warm up again with it
@@ -402,10 +452,13 @@ def main():
         log(f"cu hog: {args.cu_hog} CUs for {hog['us']:.0f} us per step (un-hogged step {hog['us'] / 1e3:.2f} ms)")
         for _ in range(2):
             step()
-    sampler = PowerSampler(local_rank)
-    sampler.start()
+    sampler = PowerSampler(local_rank) if args.full else None
+    if sampler is not None:
+        sampler.start()
     dt, ld = timed(args.steps)
-    power = sampler.stop()
+    power = sampler.stop() if sampler is not None else None
+    if dump is not None:
+        dump.write(ld)
     loss = float(sum(v.detach() for v in ld.values()))
     hog_mhz = None
     if args.cu_hog:
@@ -418,7 +471,7 @@ def main():
     # text rows the tower actually ran on (live tokens SOT..EOT) vs the dense [B, 77] layout
     live_frac = 1.0 if args.dense_text else txt_live / float(n_txt * 77)
     dense = None
-    if not args.dense_text and not args.no_dense_compare and not extra and args.arch == "vit_b32":      # the same step with every caption padded out to 77 rows, for comparison
+    if args.full and not args.dense_text and not args.no_dense_compare and not extra and args.arch == "vit_b32":      # the same step with every caption padded out to 77 rows, for comparison
         model.pack_text = False
         nd = max(5, args.steps // 2)
         for _ in range(2):
@@ -430,7 +483,8 @@ def main():
         step()
 
     roof = None
-    if not args.no_roofline:     # every rank runs the instrumented steps (they contain collectives); rank 0 reports
+    profile = args.full and not args.no_roofline
+    if profile:     # every rank runs the instrumented steps (they contain collectives); rank 0 reports
         # instrumented pass: HIP events on the launch stream around every launch, summed per kernel class
         cl = lib()
         cl.ce_profile_class_name.restype = ctypes.c_char_p
@@ -461,7 +515,7 @@ def main():
                              "gbps": by / (ms * 1e-3) / 1e9 if ms > 0 else 0.0})
         rows.sort(key=lambda r: -r["ms_per_step"])
         issued_flops = sum(r["tflops"] * 1e12 * r["ms_per_step"] * 1e-3 for r in rows)
-    if rank == 0 and not args.no_roofline and rows:
+    if rank == 0 and profile and rows:
         top = rows[0]
         mfma = top["kernel"].startswith("gemm") or top["kernel"].startswith("attn")
         ach = top["tflops"] if mfma else top["gbps"]
@@ -493,7 +547,7 @@ def main():
         dist.barrier()
 
     cpu = None
-    if rank == 0 and W == 1 and not args.no_cpu_baseline:
+    if rank == 0 and W == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     if rank == 0:
@@ -514,7 +568,7 @@ def main():
                                      % (100.0 * live_frac)),
                        "fresh_captions_every_step": not args.reuse_captions,
                        "alignment": bool(args.alignment), "train_arg": args.train_arg, "cu_hog": args.cu_hog, "cu_hog_shader_clock_mhz": hog_mhz,
-                       "nt_pgrid": int(os.environ.get("CE_NT_PGRID", "256")),
+                       "nt_pgrid": int(os.environ.get("CE_NT_PGRID", "256")), "full": bool(args.full),
                        "dense_text": dense},
             "roofline": roof, "cpu_baseline": cpu,
             "power_sample": power,      # board power / shader clock (hwmon) over the timed steps of rank 0

@@ -1,10 +1,10 @@
 #!/bin/bash
-# same-box A/B of prebuilt library variants on the step: tools/diag/ab_libs.sh TAG LIB1 LIB2 ... (each run twice, interleaved)
-TAG=$1; shift; mkdir -p gpurun_out/$TAG
+# same-box A/B of prebuilt library variants on the step: tools/diag/ab_libs.sh OUT_DIR LIB1 LIB2 ... (each run twice, interleaved)
+OUT=${1:?usage: see above}; shift; mkdir -p $OUT
 for rep in 1 2; do
   for lib in "$@"; do
-    CE_DIAG_LIB=$lib python tools/diag/bench_with_lib.py --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare $BENCH_ARGS > gpurun_out/$TAG/ab.json 2>gpurun_out/$TAG/ab.err || { tail -3 gpurun_out/$TAG/ab.err; exit 1; }
-    python - "$lib" gpurun_out/$TAG/ab.json <<'PY'
+    CE_DIAG_LIB=$lib python tools/diag/bench_with_lib.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare $BENCH_ARGS > $OUT/ab.json 2>$OUT/ab.err || { tail -3 $OUT/ab.err; exit 1; }
+    python - "$lib" $OUT/ab.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))
 cl = d.get("roofline", {}).get("classes", [])

@@ -1,7 +1,7 @@
 #!/bin/bash
 # LayerNorm ablations (timing only where the flag says so): compile-time flag sets of layernorm.hip against the default build, on the step.
-#   tools/diag/ab_ln_occ.sh "-DFLAG ..." ...
-mkdir -p gpurun_out/lnabl
+#   tools/diag/ab_ln_occ.sh OUT_DIR "-DFLAG ..." ...
+OUT=${1:?usage: see above}; shift; mkdir -p $OUT
 i=0
 for flags in "-DCE_DIAG_NONE" "$@"; do
   i=$((i+1))
@@ -12,8 +12,8 @@ for rep in 1 2; do
 i=0
 for flags in "-DCE_DIAG_NONE" "$@"; do
   i=$((i+1))
-  CE_DIAG_LIB=/tmp/libce_ln_$i.so python tools/diag/bench_with_lib.py --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare > gpurun_out/lnabl/b.json 2>gpurun_out/lnabl/b.err || { tail -3 gpurun_out/lnabl/b.err; exit 1; }
-  python - "$flags" gpurun_out/lnabl/b.json <<'PY'
+  CE_DIAG_LIB=/tmp/libce_ln_$i.so python tools/diag/bench_with_lib.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare > $OUT/b.json 2>$OUT/b.err || { tail -3 $OUT/b.err; exit 1; }
+  python - "$flags" $OUT/b.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))
 cl = {c["kernel"]: c for c in d["roofline"]["classes"]}

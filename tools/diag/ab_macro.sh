@@ -13,7 +13,7 @@ for rep in 1 2; do
   i=0
   for flags in "$@"; do
     i=$((i+1))
-    CE_DIAG_LIB=/tmp/libce_ab_$i.so python tools/diag/bench_with_lib.py --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare $BENCH_ARGS > /tmp/ab_$i.json 2>/tmp/ab_$i.err || { tail -3 /tmp/ab_$i.err; exit 1; }
+    CE_DIAG_LIB=/tmp/libce_ab_$i.so python tools/diag/bench_with_lib.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare $BENCH_ARGS > /tmp/ab_$i.json 2>/tmp/ab_$i.err || { tail -3 /tmp/ab_$i.err; exit 1; }
     python - "$flags" /tmp/ab_$i.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))

@@ -16,7 +16,7 @@ ls -la /tmp/libce_st_*.so || exit 1
 for rep in 1 2; do
  for chunk in 0 -1; do
   for aux in 0 16 2; do
-    CE_NT_CHUNK=$chunk CE_DIAG_LIB=/tmp/libce_st_$aux.so python tools/diag/bench_with_lib.py --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare > $OUT/st_${aux}_${chunk}_$rep.json 2> $OUT/st.err || { tail -5 $OUT/st.err; exit 1; }
+    CE_NT_CHUNK=$chunk CE_DIAG_LIB=/tmp/libce_st_$aux.so python tools/diag/bench_with_lib.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare > $OUT/st_${aux}_${chunk}_$rep.json 2> $OUT/st.err || { tail -5 $OUT/st.err; exit 1; }
     python - "aux=$aux chunk=$chunk" $OUT/st_${aux}_${chunk}_$rep.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))

@@ -1,12 +1,12 @@
 #!/bin/bash
-# A/B of env-selected variants in one GPU session (tn column: the gemm_tn3_kernel class): tools/gpu_ab.sh TAG "ENV1=.. ENV2=.." "ENV..." ...
-TAG=$1; shift
-mkdir -p gpurun_out/$TAG
+# A/B of env-selected variants in one GPU session (tn column: the gemm_tn3_kernel class): tools/gpu_ab.sh OUT_DIR "ENV1=.. ENV2=.." "ENV..." ...
+OUT=${1:?usage: see above}; shift
+mkdir -p $OUT
 i=0
 for envs in "$@"; do
   i=$((i+1))
-  env $envs python bench.py --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare > gpurun_out/$TAG/ab_$i.json 2> gpurun_out/$TAG/ab_$i.err || { echo "variant $i failed"; tail -5 gpurun_out/$TAG/ab_$i.err; exit 1; }
-  python - "$envs" gpurun_out/$TAG/ab_$i.json <<'PY'
+  env $envs python bench.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare > $OUT/ab_$i.json 2> $OUT/ab_$i.err || { echo "variant $i failed"; tail -5 $OUT/ab_$i.err; exit 1; }
+  python - "$envs" $OUT/ab_$i.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))
 r = d["roofline"]

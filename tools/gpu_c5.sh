@@ -6,7 +6,7 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 600 python -m pytest tests/test_hip_ops.py -m gpu -x -q -k "attention or attn" > $OUT/pytest_attn.log 2>&1; rc=$?; tail -3 $OUT/pytest_attn.log; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 600 python -m pytest tests/test_model_gpu.py -m gpu -x -q -k "patch14 or vit_l14 or 577 or long" > $OUT/pytest_model.log 2>&1; rc=$?; tail -3 $OUT/pytest_model.log; [ $rc -eq 0 ] || exit $rc
-python bench.py --arch vit_l14_336 --steps 5 --warmup 2 --no-cpu-baseline ${C5FLAGS} > $OUT/bench_config5.json 2> $OUT/bench_config5.err || { tail -20 $OUT/bench_config5.err; exit 1; }
+python bench.py --full --arch vit_l14_336 --steps 5 --warmup 2 --no-cpu-baseline ${C5FLAGS} > $OUT/bench_config5.json 2> $OUT/bench_config5.err || { tail -20 $OUT/bench_config5.err; exit 1; }
 python - $OUT <<'PY'
 import json, sys, os
 d = json.load(open(os.path.join(sys.argv[1], "bench_config5.json")))

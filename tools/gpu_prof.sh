@@ -1,15 +1,15 @@
 #!/bin/bash
-# rocprofv3 kernel stats of the single-stream bench -> gpurun_out/$1/stats.csv (+ the run's own JSON)
-TAG=$1
-mkdir -p gpurun_out/$TAG
+# rocprofv3 kernel stats of the single-stream bench -> OUT_DIR/stats.csv (+ the run's own JSON).  Usage: tools/gpu_prof.sh OUT_DIR
+mkdir -p "${1:?usage: tools/gpu_prof.sh OUT_DIR}"
+OUT=$(cd "$1" && pwd)
 ROOT=$(pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $ROOT/gpurun_out/$TAG/prof --output-format csv -- python3 $ROOT/bench.py --single-stream --no-cpu-baseline --no-dense-compare --steps 10 --warmup 3 > $ROOT/gpurun_out/$TAG/bench_single_under_rocprof.json 2> $ROOT/gpurun_out/$TAG/prof.err || exit 1
+rocprofv3 --kernel-trace --stats -d $OUT/prof --output-format csv -- python3 $ROOT/bench.py --full --single-stream --no-cpu-baseline --no-dense-compare --steps 10 --warmup 3 > $OUT/bench_single_under_rocprof.json 2> $OUT/prof.err || exit 1
 cd $ROOT
-f=$(find gpurun_out/$TAG/prof -name "*kernel_stats.csv" | head -1)
-cp "$f" gpurun_out/$TAG/stats.csv
-rm -rf gpurun_out/$TAG/prof
-python3 - gpurun_out/$TAG/stats.csv <<'PY'
+f=$(find $OUT/prof -name "*kernel_stats.csv" | head -1)
+cp "$f" $OUT/stats.csv
+rm -rf $OUT/prof
+python3 - $OUT/stats.csv <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 tot = sum(float(r["TotalDurationNs"]) for r in rows)

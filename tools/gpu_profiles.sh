@@ -8,9 +8,9 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 cut -c1-300 $OUT/bench.json
-tools/gpu_prof.sh $TAG > $OUT/stats_summary.txt || exit 1
+tools/gpu_prof.sh $OUT > $OUT/stats_summary.txt || exit 1
 head -3 $OUT/stats_summary.txt
 BARGS="--single-stream --no-cpu-baseline --no-roofline --no-dense-compare --steps 3 --warmup 1"
 cd /tmp

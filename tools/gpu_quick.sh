@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 python -m pytest tests/test_hip_ops.py -m gpu -x -q -k "$KEXPR" > $OUT/pytest_ops.log 2>&1 || { tail -30 $OUT/pytest_ops.log; exit 1; }
 tail -1 $OUT/pytest_ops.log
 for rep in 1 2; do
-  python bench.py --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare > $OUT/bench_$rep.json 2> $OUT/bench_$rep.err || { tail -5 $OUT/bench_$rep.err; exit 1; }
+  python bench.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare > $OUT/bench_$rep.json 2> $OUT/bench_$rep.err || { tail -5 $OUT/bench_$rep.err; exit 1; }
   python - $OUT/bench_$rep.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 python -m pytest tests/test_hip_ops.py -m gpu -x -q -k "gemm_nt" > $OUT/pytest_nt.log 2>&1 || { tail -20 $OUT/pytest_nt.log; exit 1; }
 tail -2 $OUT/pytest_nt.log
-tools/gpu_ab.sh $TAG "CE_NT_CHUNK=0" "CE_NT_CHUNK=-1" "CE_NT_CHUNK=5" "CE_NT_CHUNK=0" "CE_NT_CHUNK=-1" || exit 1
+tools/gpu_ab.sh $OUT "CE_NT_CHUNK=0" "CE_NT_CHUNK=-1" "CE_NT_CHUNK=5" "CE_NT_CHUNK=0" "CE_NT_CHUNK=-1" || exit 1
 BARGS="--single-stream --no-cpu-baseline --no-roofline --no-dense-compare --steps 3 --warmup 1"
 cd /tmp
 CE_NT_CHUNK=0 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch_old --output-format csv -- python3 $ROOT/bench.py $BARGS > $OUT/pmc_fetch_old.log 2>&1 || exit 1

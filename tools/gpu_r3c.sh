@@ -12,7 +12,7 @@ python -m pytest tests/test_hip_ops.py tests/test_model_gpu.py -m gpu -x -q -s -
 grep -E "noise floor|passed|failed|fp16 stream|config 3 per rank|gradient rel-L2" $OUT/pytest_model.log | tail -20
 for rep in 1 2; do
 for s16 in 0 1; do
-  CE_STREAM16=$s16 python bench.py --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare > $OUT/bench_s$s16.json 2> $OUT/bench_s$s16.err || { tail -5 $OUT/bench_s$s16.err; exit 1; }
+  CE_STREAM16=$s16 python bench.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-dense-compare > $OUT/bench_s$s16.json 2> $OUT/bench_s$s16.err || { tail -5 $OUT/bench_s$s16.err; exit 1; }
   python - "CE_STREAM16=$s16" $OUT/bench_s$s16.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))

@@ -14,11 +14,11 @@ for i in 1 2; do
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-dense-compare 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('host lengths  ', d['ms_per_step'])" || exit 1
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --no-dense-compare --device-lengths 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('device lengths', d['ms_per_step'])" || exit 1
 done
-python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
-CE_MERGE_PASSES=0 python bench.py --batch 64 --descriptions 5 --alignment --train-arg desc --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_config4_unmerged.json 2> $OUT/bench_config4_unmerged.err || { tail -20 $OUT/bench_config4_unmerged.err; exit 1; }
-python bench.py --batch 64 --descriptions 5 --alignment --train-arg desc --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_config4.json 2> $OUT/bench_config4.err || { tail -20 $OUT/bench_config4.err; exit 1; }
-python bench.py --arch vit_l14_336 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_config5_bf16.json 2> $OUT/bench_config5_bf16.err || { tail -20 $OUT/bench_config5_bf16.err; exit 1; }
-python bench.py --arch vit_l14_336 --fp8 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_config5_fp8.json 2> $OUT/bench_config5_fp8.err || { tail -20 $OUT/bench_config5_fp8.err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+CE_MERGE_PASSES=0 python bench.py --full --batch 64 --descriptions 5 --alignment --train-arg desc --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_config4_unmerged.json 2> $OUT/bench_config4_unmerged.err || { tail -20 $OUT/bench_config4_unmerged.err; exit 1; }
+python bench.py --full --batch 64 --descriptions 5 --alignment --train-arg desc --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_config4.json 2> $OUT/bench_config4.err || { tail -20 $OUT/bench_config4.err; exit 1; }
+python bench.py --full --arch vit_l14_336 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_config5_bf16.json 2> $OUT/bench_config5_bf16.err || { tail -20 $OUT/bench_config5_bf16.err; exit 1; }
+python bench.py --full --arch vit_l14_336 --fp8 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_config5_fp8.json 2> $OUT/bench_config5_fp8.err || { tail -20 $OUT/bench_config5_fp8.err; exit 1; }
 python - $OUT <<'PY'
 import json, sys, os
 for f in ("bench.json", "bench_config4_unmerged.json", "bench_config4.json", "bench_config5_bf16.json", "bench_config5_fp8.json"):

@@ -7,9 +7,9 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 cut -c1-200 $OUT/bench.json
-tools/gpu_prof.sh $TAG > $OUT/stats_summary.txt || exit 1
+tools/gpu_prof.sh $OUT > $OUT/stats_summary.txt || exit 1
 head -3 $OUT/stats_summary.txt
 BARGS="--single-stream --no-cpu-baseline --no-roofline --no-dense-compare --steps 3 --warmup 1"
 cd /tmp
@@ -28,11 +28,11 @@ python3 tools/pmc_generic.py $OUT/pmc_sq 16 > $OUT/pmc_sq.txt
 python3 tools/pmc_mfma.py $OUT/pmc_mfma_c5 > $OUT/pmc_mfma_util_config5.json
 python3 tools/pmc_generic.py $OUT/pmc_sq_c5 12 > $OUT/pmc_sq_config5.txt
 rm -rf $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_mfma $OUT/pmc_sq $OUT/pmc_mfma_c5 $OUT/pmc_sq_c5
-python bench.py --batch 64 --descriptions 5 --alignment --train-arg desc --no-cpu-baseline --steps 10 --warmup 3 > $OUT/bench_config4.json 2> $OUT/bench_c4.err || exit 1
-python bench.py --arch vit_l14_336 --no-cpu-baseline --steps 5 --warmup 2 > $OUT/bench_config5_bf16.json 2> $OUT/bench_c5.err || exit 1
-python bench.py --arch vit_l14_336 --fp8 --no-cpu-baseline --steps 5 --warmup 2 > $OUT/bench_config5_fp8.json 2> $OUT/bench_c5f.err || exit 1
-python bench.py --descriptions 5 --no-cpu-baseline --no-roofline --steps 10 --warmup 3 > $OUT/bench_config3_shape.json 2> $OUT/bench_c3.err || exit 1
-python bench.py --batch 512 --descriptions 5 --no-cpu-baseline --no-roofline --steps 5 --warmup 2 > $OUT/bench_config3_per_rank.json 2> $OUT/bench_c3r.err || exit 1
+python bench.py --full --batch 64 --descriptions 5 --alignment --train-arg desc --no-cpu-baseline --steps 10 --warmup 3 > $OUT/bench_config4.json 2> $OUT/bench_c4.err || exit 1
+python bench.py --full --arch vit_l14_336 --no-cpu-baseline --steps 5 --warmup 2 > $OUT/bench_config5_bf16.json 2> $OUT/bench_c5.err || exit 1
+python bench.py --full --arch vit_l14_336 --fp8 --no-cpu-baseline --steps 5 --warmup 2 > $OUT/bench_config5_fp8.json 2> $OUT/bench_c5f.err || exit 1
+python bench.py --full --descriptions 5 --no-cpu-baseline --no-roofline --steps 10 --warmup 3 > $OUT/bench_config3_shape.json 2> $OUT/bench_c3.err || exit 1
+python bench.py --full --batch 512 --descriptions 5 --no-cpu-baseline --no-roofline --steps 5 --warmup 2 > $OUT/bench_config3_per_rank.json 2> $OUT/bench_c3r.err || exit 1
 for f in bench_config4 bench_config5_bf16 bench_config5_fp8 bench_config3_shape bench_config3_per_rank; do python -c "
 import json; d=json.load(open('$OUT/$f.json')); print('$f', d['ms_per_step'], 'ms', d['value'], 'pairs/s', (d['roofline'] or {}).get('step_frac'))"; done
 # idle accounting

@@ -8,5 +8,5 @@ export TMPDIR=/tmp
 python -m pytest tests -m gpu -x -q -s > $OUT/pytest.log 2>&1; rc=$?
 tail -5 $OUT/pytest.log
 [ $rc -ne 0 ] && exit $rc
-python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || exit 1
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || exit 1
 cat $OUT/bench.json | cut -c1-600
