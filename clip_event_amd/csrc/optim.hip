@@ -295,6 +295,11 @@ __global__ __launch_bounds__(256) void adam_segments_kernel(float* __restrict__ 
     }
 }
 
+// Bias corrections in double, rounded once to fp32 -- as torch.optim.Adam takes them (Python floats).  In fp32, 1 - powf(beta2,
+// step) cancels: at step 2 (1 - 0.998) the rounding of powf is up to 1.5e-5 of the result, and the update inherits it.
+float adam_bc1(float beta1, int step) { return (float)(1.0 - pow((double)beta1, (double)step)); }
+float adam_bc2_sqrt(float beta2, int step) { return (float)sqrt(1.0 - pow((double)beta2, (double)step)); }
+
 }  // namespace
 
 extern "C" int ce_multi_transpose_bf16(const ce_transpose_job* jobs_device, int njobs, int total_tiles, void* stream) {
@@ -324,8 +329,7 @@ extern "C" int ce_adam_step(float* p, const float* g, float* m, float* v, void* 
                             float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                             void* stream) {
     CE_CHECK_ARG(n > 0 && step >= 1, "ce_adam_step: need n>0 and step>=1");
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
+    const float bc1 = adam_bc1(beta1, step), bc2_sqrt = adam_bc2_sqrt(beta2, step);
     long blocks = (n + 2047) / 2048;
     static const long cap = getenv("CE_ADAM_BLOCKS") ? atol(getenv("CE_ADAM_BLOCKS")) : 4096;
     if (blocks > cap) blocks = cap;
@@ -341,8 +345,7 @@ extern "C" int ce_adam_step_tiles(float* p, const float* g, float* m, float* v, 
                                   void* stream) {
     CE_CHECK_ARG(p && g && m && v && p_bf16 && step >= 1, "ce_adam_step_tiles: null buffer or step < 1");
     CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "ce_adam_step_tiles: nothing to update");
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
+    const float bc1 = adam_bc1(beta1, step), bc2_sqrt = adam_bc2_sqrt(beta2, step);
     if (njobs > 0)
         hipLaunchKernelGGL(adam_tiles_kernel, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
                            jobs_device, njobs, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt);
