@@ -16,7 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libclip_event_hip.so")
 _lib = None
 
-EPI_BF16, EPI_F32, EPI_BIAS_BF16, EPI_BIAS_F32, EPI_BIAS_RESID_F32, EPI_BIAS_GELU, EPI_GELUGRAD_BF16, EPI_BIAS_RESID_F16 = range(8)
+(EPI_BF16, EPI_F32, EPI_BIAS_BF16, EPI_BIAS_F32, EPI_BIAS_RESID_F32, EPI_BIAS_GELU, EPI_GELUGRAD_BF16, EPI_BIAS_RESID_F16,
+ EPI_BIAS_QGELU_BF16) = range(9)
 T_F32, T_BF16, T_F16 = 0, 1, 2          # element types of stream operands (CE_T_* of include/clip_event_hip.h)
 
 

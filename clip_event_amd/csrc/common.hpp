@@ -174,6 +174,11 @@ __device__ __forceinline__ void quick_gelu_both(float x, float& g, float& d) {
     g = x * s;
     d = __builtin_fmaf(1.702f * g, 1.0f - s, s);
 }
+// the activation half alone, the same operations in the same order: bit-identical to quick_gelu_both's g
+__device__ __forceinline__ float quick_gelu_act(float x) {
+    const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.4554669595930157f * x));
+    return x * s;
+}
 
 // ---- fp16-stream saturation counters (runtime.cpp: the buffer registered with ce_stream16_set_counters, or null) ----
 // [0] forward residual stream: (wave, lane) slots of a LayerNorm forward that READ an element at the fp16 limit (every fp16

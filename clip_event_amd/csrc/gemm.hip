@@ -1990,7 +1990,7 @@ int g_cus = getenv("CE_GEMM_CUS") ? atoi(getenv("CE_GEMM_CUS")) : 256;
 // epilogues for which the persistent kernel is also built with two tile heights (launch_nt)
 constexpr bool nt_two_heights(int epi) {
     return epi == CE_EPI_BIAS_GELU || epi == CE_EPI_GELUGRAD_BF16 || epi == CE_EPI_BIAS_BF16 || epi == CE_EPI_BF16 ||
-           epi == CE_EPI_BIAS_RESID_F16 || epi == CE_EPI_BIAS_RESID_F32;
+           epi == CE_EPI_BIAS_RESID_F16 || epi == CE_EPI_BIAS_RESID_F32 || epi == CE_EPI_BIAS_QGELU_BF16;
 }
 inline int cu_budget() { return g_cus >= 32 && g_cus <= 256 ? g_cus : 256; }
 inline long nt256_cost(long tiles, int tm) { return ((tiles + cu_budget() - 1) / cu_budget()) * (28 + 10 * tm); }
@@ -2078,8 +2078,8 @@ int launch_nt(NTArgs a, hipStream_t stream) {
             hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 5, 0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
         }
     });
-    const double out_b = (EPI == CE_EPI_F32 || EPI == CE_EPI_BIAS_F32) ? 4.0 : (EPI == CE_EPI_BIAS_RESID_F32 ? 8.0 : (EPI == CE_EPI_BIAS_GELU || EPI == CE_EPI_GELUGRAD_BF16 || EPI == CE_EPI_BIAS_RESID_F16 ? 4.0 : 2.0));
-    CeProfScope prof(CE_PROF_GEMM_NT0 + CE_PROF_NT_FAMILIES * EPI, 2.0 * a.M * a.N * a.K, 2.0 * ((double)a.M * a.K + (double)a.N * a.K) + out_b * a.M * a.N, stream);
+    const double out_b = epi_traffic_bytes(EPI);
+    CeProfScope prof(nt_prof_class(EPI), 2.0 * a.M * a.N * a.K, 2.0 * ((double)a.M * a.K + (double)a.N * a.K) + out_b * a.M * a.N, stream);
     const int force = nt_variant();
     const bool can256 = (a.K % N2_BK == 0) && a.N % 8 == 0 && a.ldo % 8 == 0 && a.ldo2 % 8 == 0 && a.ldaux % 8 == 0;
     const bool want256 = force == 256 || (force == 0 && a.M >= 1024 && a.N >= 256);
@@ -2116,7 +2116,7 @@ int launch_nt(NTArgs a, hipStream_t stream) {
         const bool fits31 = span(a.ldo, epi_out_bytes(EPI)) < (1l << 31) && span(a.ldo2, 2) < (1l << 31) && span(a.ldaux, 2) < (1l << 31) &&
                             span(a.ldr, 4) < (1l << 31);
         const bool lw = fits31 && (f == 161 || (half && f == 0 && (policy & 16)));       // one 160x256 loader-wave workgroup per CU
-        prof.retag(CE_PROF_GEMM_NT0 + CE_PROF_NT_FAMILIES * EPI + (lw ? 5 : (half || f == 104 ? 1 : (use32 ? 3 : 2))));
+        prof.retag(nt_prof_class(EPI) + (lw ? 5 : (half || f == 104 ? 1 : (use32 ? 3 : 2))));
         // multi-round launches: the persistent loader-wave kernel.  Bit 5 = for the light epilogues (qkv forward: 726 ->
         // 810 TF/s), bit 6 = also for the GELU epilogues (as kernels about equal to the two-workgroup 160x256x32 kernel
         // since their epilogues lost the division and the backward's transcendentals).  Both on by default: B = 256 step
@@ -2161,7 +2161,7 @@ int launch_nt(NTArgs a, hipStream_t stream) {
             // dynamic tile list (off by default): only where a workgroup walks more than one tile, with >= 3 K iterations
             // (the fetched id is published by the barrier of iteration 1 and needed from iteration nk - 2) on the launch-wide walk
             a.tile_queue = (g_dynamic && tiles > (long)grid.x && a.K >= 3 * N4_BK && a.tile_chunk == 0) ? next_tile_queue(stream) : nullptr;
-            prof.retag(CE_PROF_GEMM_NT0 + CE_PROF_NT_FAMILIES * EPI + 6);
+            prof.retag(nt_prof_class(EPI) + 6);
             // TWO TILE HEIGHTS (gemm_nt160p_kernel<EPI, 5, 0, TS>): n_tall row panels of 160 rows, the rest in panels of 32 TS, chosen so
             // that the longest per-workgroup list (tall tiles first, round-robin over the grid) is shortest under the same cost
             // model; taken when it beats the best single height by >= 3 %.  12800 x 3072: 960 tiles of 160 rows = 3.75 rounds -> 3
@@ -2267,7 +2267,7 @@ int launch_nt(NTArgs a, hipStream_t stream) {
         });
         a.tiles_m = ce_div_up(a.M, 64);
         a.tiles_n = ce_div_up(a.N, 64);
-        prof.retag(CE_PROF_GEMM_NT0 + CE_PROF_NT_FAMILIES * EPI + 7);
+        prof.retag(nt_prof_class(EPI) + 7);
         hipLaunchKernelGGL(gemm_nt_skinny_kernel<EPI>, dim3(a.tiles_m * a.tiles_n), dim3(512), SK_LDS_BYTES, stream, a);
     } else {
         hipLaunchKernelGGL(gemm_nt_kernel<EPI>, dim3(a.tiles_m * a.tiles_n), dim3(256), NT_LDS_BYTES, stream, a);
@@ -2304,8 +2304,8 @@ int launch_nt_f8(NTArgs a, hipStream_t stream) {
     if ((long)a.M * a.ldo * epi_out_bytes(EPI) >= (1l << 31) || (long)a.M * a.ldo2 * 2 >= (1l << 31) || (long)a.M * a.ldaux * 2 >= (1l << 31) ||
         (long)a.M * a.ldr * 4 >= (1l << 31))
         return 1;                                  // 32-bit epilogue offsets (EpiBuf)
-    const double out_b = EPI == CE_EPI_BIAS_RESID_F32 ? 8.0 : (EPI == CE_EPI_BIAS_GELU || EPI == CE_EPI_GELUGRAD_BF16 || EPI == CE_EPI_BIAS_RESID_F16 ? 4.0 : 2.0);
-    CeProfScope prof(CE_PROF_GEMM_NT0 + CE_PROF_NT_FAMILIES * EPI + 4, 2.0 * a.M * a.N * a.K, 1.0 * ((double)a.M * a.K + (double)a.N * a.K) + out_b * a.M * a.N, stream);
+    const double out_b = epi_traffic_bytes(EPI);
+    CeProfScope prof(nt_prof_class(EPI) + 4, 2.0 * a.M * a.N * a.K, 1.0 * ((double)a.M * a.K + (double)a.N * a.K) + out_b * a.M * a.N, stream);
     a.tiles_n = ce_div_up(a.N, N4_BN);
     const long half_tiles = (long)ce_div_up(a.M, 160) * ce_div_up(a.N, 128);
     const dim3 block(64 * (8 + N4_LOADERS));
@@ -2384,6 +2384,7 @@ extern "C" int ce__gemm_nt_fp8_lw(const void* A8, long lda, const float* sa, con
         case CE_EPI_BIAS_RESID_F32: return launch_nt_f8<CE_EPI_BIAS_RESID_F32>(a, s);
         case CE_EPI_BIAS_RESID_F16: return launch_nt_f8<CE_EPI_BIAS_RESID_F16>(a, s);
         case CE_EPI_BIAS_GELU: return launch_nt_f8<CE_EPI_BIAS_GELU>(a, s);
+        case CE_EPI_BIAS_QGELU_BF16: return launch_nt_f8<CE_EPI_BIAS_QGELU_BF16>(a, s);
         case CE_EPI_GELUGRAD_BF16: return launch_nt_f8<CE_EPI_GELUGRAD_BF16>(a, s);
         default: return 1;
     }
@@ -2444,6 +2445,9 @@ extern "C" int ce_gemm_nt(const void* A, long lda, const void* B, long ldb, int 
         case CE_EPI_BIAS_GELU:
             CE_CHECK_ARG(bias && out2 && ldo2 >= N && ldo2 % 4 == 0, "ce_gemm_nt: gelu epilogue needs bias+out2");
             return launch_nt<CE_EPI_BIAS_GELU>(a, s);
+        case CE_EPI_BIAS_QGELU_BF16:
+            CE_CHECK_ARG(bias, "ce_gemm_nt: QuickGELU epilogue without bias");
+            return launch_nt<CE_EPI_BIAS_QGELU_BF16>(a, s);
         case CE_EPI_GELUGRAD_BF16:
             CE_CHECK_ARG(aux && ldaux >= N && ldaux % 4 == 0, "ce_gemm_nt: gelu-grad epilogue needs aux");
             return launch_nt<CE_EPI_GELUGRAD_BF16>(a, s);

@@ -28,7 +28,17 @@ struct NTArgs {
 
 constexpr bool epi_has_bias(int epi) {
     return epi == CE_EPI_BIAS_BF16 || epi == CE_EPI_BIAS_RESID_F32 || epi == CE_EPI_BIAS_GELU || epi == CE_EPI_BIAS_F32 ||
-           epi == CE_EPI_BIAS_RESID_F16;
+           epi == CE_EPI_BIAS_RESID_F16 || epi == CE_EPI_BIAS_QGELU_BF16;
+}
+// profiler class of an NT launch with this epilogue (+ kernel family)
+constexpr int nt_prof_class(int epi) {
+    return epi == CE_EPI_BIAS_QGELU_BF16 ? CE_PROF_GEMM_NT_QGELU : CE_PROF_GEMM_NT0 + CE_PROF_NT_FAMILIES * epi;
+}
+// bytes a launch writes (and reads back, for the residual adds) per output element: the cost models' output term
+constexpr double epi_traffic_bytes(int epi) {
+    return (epi == CE_EPI_F32 || epi == CE_EPI_BIAS_F32) ? 4.0
+           : epi == CE_EPI_BIAS_RESID_F32 ? 8.0
+           : (epi == CE_EPI_BIAS_GELU || epi == CE_EPI_GELUGRAD_BF16 || epi == CE_EPI_BIAS_RESID_F16) ? 4.0 : 2.0;
 }
 
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
@@ -116,6 +126,10 @@ __device__ __forceinline__ void nt_epilogue(const NTArgs& p, int m, int n, f32x4
         *reinterpret_cast<u32x2*>(reinterpret_cast<bf16_t*>(p.out) + (long)m * p.ldo + n) = o;
         u32x2 g = {pack_bf2(gv[0], gv[1]), pack_bf2(gv[2], gv[3])};
         *reinterpret_cast<u32x2*>(p.out2 + (long)m * p.ldo2 + n) = g;
+    } else if constexpr (EPI == CE_EPI_BIAS_QGELU_BF16) {
+        // out = QuickGELU(a) (bf16) alone: the forward-only form of BIAS_GELU
+        u32x2 g = {pack_bf2(quick_gelu_act(v[0]), quick_gelu_act(v[1])), pack_bf2(quick_gelu_act(v[2]), quick_gelu_act(v[3]))};
+        *reinterpret_cast<u32x2*>(reinterpret_cast<bf16_t*>(p.out) + (long)m * p.ldo + n) = g;
     } else if constexpr (EPI == CE_EPI_GELUGRAD_BF16) {
         // out = acc * aux, aux = the bf16 QuickGELU'(a) the forward epilogue saved
         u32x2 a = *reinterpret_cast<const u32x2*>(p.aux + (long)m * p.ldaux + n);
@@ -227,6 +241,10 @@ __device__ __forceinline__ void nt_epilogue8b(const EpiBuf& eo, const EpiBuf& eo
         u32x4 g = {pack_bf2(gv[0], gv[1]), pack_bf2(gv[2], gv[3]), pack_bf2(gv[4], gv[5]), pack_bf2(gv[6], gv[7])};
         epi_bstore16(eo, slot, o);
         epi_bstore16(eo2, slot, g);
+    } else if constexpr (EPI == CE_EPI_BIAS_QGELU_BF16) {
+        u32x4 g = {pack_bf2(quick_gelu_act(v0[0]), quick_gelu_act(v0[1])), pack_bf2(quick_gelu_act(v0[2]), quick_gelu_act(v0[3])),
+                   pack_bf2(quick_gelu_act(v1[0]), quick_gelu_act(v1[1])), pack_bf2(quick_gelu_act(v1[2]), quick_gelu_act(v1[3]))};
+        epi_bstore16(eo, slot, g);
     }
 }
 
@@ -264,6 +282,10 @@ __device__ __forceinline__ void nt_epilogue8(const NTArgs& p, int m, int n, f32x
         epi_store16(p.out, ((long)m * p.ldo + n) * 2, o);
         u32x4 g = {pack_bf2(gv[0], gv[1]), pack_bf2(gv[2], gv[3]), pack_bf2(gv[4], gv[5]), pack_bf2(gv[6], gv[7])};
         epi_store16(p.out2, ((long)m * p.ldo2 + n) * 2, g);
+    } else if constexpr (EPI == CE_EPI_BIAS_QGELU_BF16) {
+        u32x4 g = {pack_bf2(quick_gelu_act(v0[0]), quick_gelu_act(v0[1])), pack_bf2(quick_gelu_act(v0[2]), quick_gelu_act(v0[3])),
+                   pack_bf2(quick_gelu_act(v1[0]), quick_gelu_act(v1[1])), pack_bf2(quick_gelu_act(v1[2]), quick_gelu_act(v1[3]))};
+        epi_store16(p.out, ((long)m * p.ldo + n) * 2, g);
     } else if constexpr (EPI == CE_EPI_GELUGRAD_BF16) {
         u32x4 a = *reinterpret_cast<const u32x4*>(p.aux + (long)m * p.ldaux + n);
         f32x4 r0 = {v0[0] * bf_lo(a[0]), v0[1] * bf_hi(a[0]), v0[2] * bf_lo(a[1]), v0[3] * bf_hi(a[1])};

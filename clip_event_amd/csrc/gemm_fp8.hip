@@ -368,8 +368,8 @@ int g_force8 = 0;     // tools: 0 auto, 4/5/6/8 = tile height of the 256-column 
 
 template <int EPI>
 int launch_nt8(NTArgs a, hipStream_t stream) {
-    const double out_b = EPI == CE_EPI_BIAS_RESID_F32 ? 8.0 : (EPI == CE_EPI_BIAS_GELU || EPI == CE_EPI_GELUGRAD_BF16 || EPI == CE_EPI_BIAS_RESID_F16 ? 4.0 : 2.0);
-    CeProfScope prof(CE_PROF_GEMM_NT0 + CE_PROF_NT_FAMILIES * EPI + 4, 2.0 * a.M * a.N * a.K, 1.0 * ((double)a.M * a.K + (double)a.N * a.K) + out_b * a.M * a.N, stream);
+    const double out_b = epi_traffic_bytes(EPI);
+    CeProfScope prof(nt_prof_class(EPI) + 4, 2.0 * a.M * a.N * a.K, 1.0 * ((double)a.M * a.K + (double)a.N * a.K) + out_b * a.M * a.N, stream);
     // tile choice as in gemm.hip: rounds over the 256 CUs x cost of a round; the two-workgroup 160x128 tile when its
     // tiles fit one resident round
     const long half_tiles = (long)ce_div_up(a.M, 160) * ce_div_up(a.N, 128);
@@ -490,6 +490,7 @@ static int gemm_nt_fp8_any(const void* A8, long lda, const float* sa, const uint
             case CE_EPI_BIAS_RESID_F32: ok = bias && resid && ldr >= N && ldr % 4 == 0; break;
             case CE_EPI_BIAS_RESID_F16: ok = bias && resid && ldr >= N && ldr % 8 == 0; break;
             case CE_EPI_BIAS_GELU: ok = bias && out2 && ldo2 >= N; break;
+            case CE_EPI_BIAS_QGELU_BF16: ok = bias != nullptr; break;
             case CE_EPI_GELUGRAD_BF16: ok = aux && ldaux >= N; break;
             default: break;
         }
@@ -520,6 +521,9 @@ static int gemm_nt_fp8_any(const void* A8, long lda, const float* sa, const uint
         case CE_EPI_BIAS_GELU:
             CE_CHECK_ARG(bias && out2 && ldo2 >= N, "ce_gemm_nt_fp8: gelu epilogue needs bias+out2");
             return launch_nt8<CE_EPI_BIAS_GELU>(a, s);
+        case CE_EPI_BIAS_QGELU_BF16:
+            CE_CHECK_ARG(bias, "ce_gemm_nt_fp8: QuickGELU epilogue without bias");
+            return launch_nt8<CE_EPI_BIAS_QGELU_BF16>(a, s);
         case CE_EPI_GELUGRAD_BF16:
             CE_CHECK_ARG(aux && ldaux >= N, "ce_gemm_nt_fp8: gelu-grad epilogue needs aux");
             return launch_nt8<CE_EPI_GELUGRAD_BF16>(a, s);

@@ -38,11 +38,11 @@ std::mutex g_mu;
 bool g_on = false;
 std::vector<Rec> g_recs;
 std::vector<std::pair<hipEvent_t, hipEvent_t>> g_pool;
-const char* kEpi[8] = {"BF16", "F32", "BIAS_BF16", "BIAS_F32", "BIAS_RESID_F32", "BIAS_GELU", "GELUGRAD_BF16", "BIAS_RESID_F16"};
+const char* kEpi[9] = {"BF16", "F32", "BIAS_BF16", "BIAS_F32", "BIAS_RESID_F32", "BIAS_GELU", "GELUGRAD_BF16", "BIAS_RESID_F16", "BIAS_QGELU_BF16"};
 const char* kFam[CE_PROF_NT_FAMILIES] = {"gemm_nt_kernel<%d>", "gemm_nt256_kernel<%d,*,2>", "gemm_nt256_kernel<%d,*,4>",
                                          "gemm_nt32_kernel<%d>", "gemm_nt8_kernel<%d,*,*>", "gemm_nt160lw_kernel<%d,*>",
                                          "gemm_nt160p_kernel<%d,*>", "gemm_nt_skinny_kernel<%d>"};
-const char* kRest[CE_PROF_NCLASS - CE_PROF_GEMM_TN] = {"gemm_tn3_kernel", "attn_fwd", "attn_bwd", "ln_fwd", "ln_bwd",
+const char* kRest[CE_PROF_GEMM_NT_QGELU - CE_PROF_GEMM_TN] = {"gemm_tn3_kernel", "attn_fwd", "attn_bwd", "ln_fwd", "ln_bwd",
                                                        "colsum_bf16", "other", "gemm_tn2_kernel"};
 thread_local char g_name[96];
 }  // namespace
@@ -79,10 +79,11 @@ extern "C" const char* ce_profile_class_name(int cls) {
         static const bool lw = getenv("CE_TN3_LW") ? atoi(getenv("CE_TN3_LW")) != 0 : true;
         return lw ? "gemm_tn3lw_kernel" : "gemm_tn3_kernel";
     }
-    if (cls >= CE_PROF_GEMM_TN) return kRest[cls - CE_PROF_GEMM_TN];
+    if (cls >= CE_PROF_GEMM_TN && cls < CE_PROF_GEMM_NT_QGELU) return kRest[cls - CE_PROF_GEMM_TN];
+    const int epi = cls >= CE_PROF_GEMM_NT_QGELU ? CE_EPI_BIAS_QGELU_BF16 : cls / CE_PROF_NT_FAMILIES;
     char fam[64];
-    snprintf(fam, sizeof(fam), kFam[cls % CE_PROF_NT_FAMILIES], cls / CE_PROF_NT_FAMILIES);
-    snprintf(g_name, sizeof(g_name), "%s %s", fam, kEpi[cls / CE_PROF_NT_FAMILIES]);       // e.g. "gemm_nt256_kernel<0,*,2> BF16"
+    snprintf(fam, sizeof(fam), kFam[cls % CE_PROF_NT_FAMILIES], epi);
+    snprintf(g_name, sizeof(g_name), "%s %s", fam, kEpi[epi]);       // e.g. "gemm_nt256_kernel<0,*,2> BF16"
     return g_name;
 }
 

@@ -6,6 +6,7 @@
 // Activation stash per block (rows M = batch*tokens, width d), all needed by the backward:
 //   x_in (previous block's output; stream type: f32, or f16 with ce_tower_desc.stream16), h1 bf16, qkv bf16 [M,3d], o bf16,
 //   lse f32, x_mid (stream type), h2 bf16, a bf16 [M,4d] (QuickGELU' of the c_fc output), g bf16 [M,4d] (QuickGELU of it), LayerNorm mean/rstd.
+// ce_tower_forward_infer runs the same launches without a stash (carve_infer): one set of buffers for every block.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
@@ -110,6 +111,38 @@ void carve(const ce_tower_desc* d, int batch, size_t rows, void* ws, Layout& L) 
     L.bytes = (c.off + 255) & ~size_t(255);
 }
 
+// Forward-only layout (ce_tower_forward_infer): no backward follows, so nothing is kept.  Every block sees the SAME buffers -- x_mid
+// in one stream-typed buffer, x_out in a second (block l reads its input from the second while it writes the first, and has
+// finished with it by the time mlp.c_proj writes it again; block 0 reads the caller's x0, which is never written), one h for
+// both LayerNorm outputs, one qkv, o, g, one set of statistics and lse -- and there is no derivative buffer (`a`) and no
+// backward ring.  Per row: 2 stream elements + 18 bytes, times width (22 / 26 x width; + 4 x width of fp8 scratch), once.
+void carve_infer(const ce_tower_desc* d, int batch, size_t rows, void* ws, Layout& L) {
+    Carver c(ws);
+    const size_t M = rows, w = d->width;
+    const size_t esz = d->stream16 ? 2 : 4;
+    L = Layout{};
+    BlockStash s{};
+    s.x_mid = c.take<char>(M * w * esz);
+    s.x_out = c.take<char>(M * w * esz);
+    s.h1 = s.h2 = c.take<bf16_t>(M * w);
+    s.qkv = c.take<bf16_t>(M * 3 * w);
+    s.o = c.take<bf16_t>(M * w);
+    s.a = nullptr;
+    s.g = c.take<bf16_t>(M * 4 * w);
+    s.mean1 = s.mean2 = c.take<float>(M);
+    s.rstd1 = s.rstd2 = c.take<float>(M);
+    s.lse = c.take<float>((size_t)batch * d->heads * d->tokens);
+    for (int l = 0; l < d->layers; ++l) L.blk[l] = s;
+    L.blk[d->layers - 1].x_out = nullptr;                                    // the last block writes the caller's x_out
+    L.q8 = d->fp8 ? c.take<uint8_t>(M * 4 * w) : nullptr;
+    L.q8s = d->fp8 ? c.take<float>(M) : nullptr;
+    const size_t Bn = (size_t)batch;
+    L.xs_in = c.take<float>(Bn * w); L.xs_mid = c.take<float>(Bn * w);
+    L.means = c.take<float>(Bn); L.rstds = c.take<float>(Bn);
+    L.os = c.take<bf16_t>(Bn * w); L.h2s = c.take<bf16_t>(Bn * w); L.gs = c.take<bf16_t>(Bn * 4 * w);
+    L.bytes = (c.off + 255) & ~size_t(255);
+}
+
 int check_rows(const ce_tower_desc* d, int batch, int rows, const int* cu) {
     CE_CHECK_ARG(rows > 0 && (long)rows <= (long)batch * d->tokens, "tower: rows=%d outside 1..batch*tokens", rows);
     CE_CHECK_ARG(cu || rows == batch * d->tokens, "tower: a dense batch has batch*tokens rows (got %d)", rows);
@@ -149,26 +182,16 @@ int linear(bool use8, const Layout& L, const void*& q8_of, const void* A, long l
     return ce_gemm_nt(A, lda, W, K, M, N, K, epi, bias, resid, ldr, out, ldo, out2, ldo2, aux, ldaux, stream);
 }
 
-}  // namespace
-
-extern "C" size_t ce_tower_workspace_bytes(const ce_tower_desc* d, int batch) {
-    if (check_desc(d, batch) != 0) return 0;
-    Layout L;
-    carve(d, batch, (size_t)batch * d->tokens, nullptr, L);
-    return L.bytes;
-}
-
-extern "C" int ce_tower_forward(const ce_tower_desc* d, int batch, int rows, const int* cu_seqlens, const void* x0,
-                                void* workspace, void* x_out, const int* sel_rows, void* stream) {
-    TRY(check_desc(d, batch));
-    TRY(check_rows(d, batch, rows, cu_seqlens));
-    CE_CHECK_ARG(x0 && workspace && x_out, "ce_tower_forward: null buffer");
-    Layout L;
-    carve(d, batch, rows, workspace, L);
+// The launches of one tower forward over the buffers of `L`.  infer = false: the training layout (carve), mlp.c_fc writes the
+// QuickGELU derivative next to the activation; true: the forward-only layout (carve_infer), activation alone.  Everything else
+// -- order, shapes, leading dimensions, tile choice -- is the same, so the two produce the same x_out bit for bit.
+int forward_run(const ce_tower_desc* d, int batch, int rows, const int* cu_seqlens, const void* x0, Layout& L, void* x_out,
+                const int* sel_rows, bool infer, void* stream) {
     const int M = rows, w = d->width;
     const bool f8 = (d->fp8 & 1) != 0;
     const int ST = d->stream16 ? CE_T_F16 : CE_T_F32;                         // residual-stream element type
     const int EPI_RESID = d->stream16 ? CE_EPI_BIAS_RESID_F16 : CE_EPI_BIAS_RESID_F32;
+    const int EPI_FC = infer ? CE_EPI_BIAS_QGELU_BF16 : CE_EPI_BIAS_GELU;
     const long esz = d->stream16 ? 2 : 4;
     const void* x = x0;
     const void* q8_of = nullptr;
@@ -193,8 +216,8 @@ extern "C" int ce_tower_forward(const ce_tower_desc* d, int batch, int rows, con
             TRY(linear(f8, L, q8_of, L.os, w, p.w_out, p.w8_out, p.s8_out, Bn, w, w, EPI_RESID, p.b_out, L.xs_in, w, L.xs_mid, w, nullptr,
                            0, nullptr, 0, stream));
             TRY(ce_layernorm_fwd_t(L.xs_mid, ST, w, nullptr, p.ln2_w, p.ln2_b, L.h2s, CE_T_BF16, w, L.means, L.rstds, Bn, w, 1e-5f, stream));
-            TRY(linear(f8, L, q8_of, L.h2s, w, p.w_fc, p.w8_fc, p.s8_fc, Bn, 4 * w, w, CE_EPI_BIAS_GELU, p.b_fc, nullptr, 0, L.as, 4 * w, L.gs, 4 * w,
-                           nullptr, 0, stream));
+            TRY(linear(f8, L, q8_of, L.h2s, w, p.w_fc, p.w8_fc, p.s8_fc, Bn, 4 * w, w, EPI_FC, p.b_fc, nullptr, 0, infer ? L.gs : L.as, 4 * w,
+                           infer ? nullptr : L.gs, infer ? 0 : 4 * w, nullptr, 0, stream));
             TRY(linear(f8, L, q8_of, L.gs, 4 * w, p.w_proj, p.w8_proj, p.s8_proj, Bn, w, 4 * w, EPI_RESID, p.b_proj, L.xs_mid, w, x_out, w,
                            nullptr, 0, nullptr, 0, stream));
             break;
@@ -204,13 +227,49 @@ extern "C" int ce_tower_forward(const ce_tower_desc* d, int batch, int rows, con
         TRY(ce_layernorm_fwd_q8(s.x_mid, ST, w, nullptr, p.ln2_w, p.ln2_b, s.h2, CE_T_BF16, w, s.mean2, s.rstd2, M, w, 1e-5f,
                                 lnq ? L.q8 : nullptr, w, L.q8s, stream));
         if (lnq) q8_of = s.h2;
-        TRY(linear(f8, L, q8_of, s.h2, w, p.w_fc, p.w8_fc, p.s8_fc, M, 4 * w, w, CE_EPI_BIAS_GELU, p.b_fc, nullptr, 0, s.a, 4 * w, s.g, 4 * w,
-                       nullptr, 0, stream));
+        TRY(linear(f8, L, q8_of, s.h2, w, p.w_fc, p.w8_fc, p.s8_fc, M, 4 * w, w, EPI_FC, p.b_fc, nullptr, 0, infer ? s.g : s.a, 4 * w,
+                       infer ? nullptr : s.g, infer ? 0 : 4 * w, nullptr, 0, stream));
         TRY(linear(f8, L, q8_of, s.g, 4 * w, p.w_proj, p.w8_proj, p.s8_proj, M, w, 4 * w, EPI_RESID, p.b_proj, s.x_mid, w, xo, w,
                        nullptr, 0, nullptr, 0, stream));
         x = xo;
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" size_t ce_tower_workspace_bytes(const ce_tower_desc* d, int batch) {
+    if (check_desc(d, batch) != 0) return 0;
+    Layout L;
+    carve(d, batch, (size_t)batch * d->tokens, nullptr, L);
+    return L.bytes;
+}
+
+extern "C" int ce_tower_forward(const ce_tower_desc* d, int batch, int rows, const int* cu_seqlens, const void* x0,
+                                void* workspace, void* x_out, const int* sel_rows, void* stream) {
+    TRY(check_desc(d, batch));
+    TRY(check_rows(d, batch, rows, cu_seqlens));
+    CE_CHECK_ARG(x0 && workspace && x_out, "ce_tower_forward: null buffer");
+    Layout L;
+    carve(d, batch, rows, workspace, L);
+    return forward_run(d, batch, rows, cu_seqlens, x0, L, x_out, sel_rows, false, stream);
+}
+
+extern "C" size_t ce_tower_infer_workspace_bytes(const ce_tower_desc* d, int batch) {
+    if (check_desc(d, batch) != 0) return 0;
+    Layout L;
+    carve_infer(d, batch, (size_t)batch * d->tokens, nullptr, L);
+    return L.bytes;
+}
+
+extern "C" int ce_tower_forward_infer(const ce_tower_desc* d, int batch, int rows, const int* cu_seqlens, const void* x0,
+                                      void* workspace, void* x_out, const int* sel_rows, void* stream) {
+    TRY(check_desc(d, batch));
+    TRY(check_rows(d, batch, rows, cu_seqlens));
+    CE_CHECK_ARG(x0 && workspace && x_out, "ce_tower_forward_infer: null buffer");
+    Layout L;
+    carve_infer(d, batch, rows, workspace, L);
+    return forward_run(d, batch, rows, cu_seqlens, x0, L, x_out, sel_rows, true, stream);
 }
 
 extern "C" int ce_tower_backward(const ce_tower_desc* d, int batch, int rows, const int* cu_seqlens, const void* x0,

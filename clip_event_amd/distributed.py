@@ -258,7 +258,14 @@ class GradSync:
     Whatever was not reduced eagerly (a tower whose pass count is unknown, logit_scale) is reduced by
     ``finish()``, which runs as an autograd final callback at the end of ``backward()`` -- the gradients are
     averaged when ``backward()`` returns, as under DDP -- and may also be called explicitly (a second call is a
-    no-op)."""
+    no-op).
+
+    Counting announcements only works when every forward of the step is announced before the first backward runs.
+    A micro-batched step (engine.train_step(micro_batch=...)) interleaves them -- chunk 1 forward, chunk 1 backward,
+    chunk 2 forward, ... -- and calls ``backward()`` once per chunk; it says so up front with ``expect_passes``:
+    the n-th backward of a tower is then its last whatever the announcement order, and the final callback of the
+    earlier ``backward()`` calls does nothing, so the step has ONE exchange whose eager pieces overlap the last
+    chunk's backward."""
 
     TOWERS = ("visual", "text")
     plan = None          # ShardPlan of the sharded optimiser step, when switched on
@@ -298,6 +305,7 @@ class GradSync:
         self.expected = {t: 0 for t in self.TOWERS}      # tower forwards of this step that recorded a graph
         self.seen = {t: 0 for t in self.TOWERS}          # tower backwards completed this step
         self.fences = {t: [] for t in self.TOWERS}       # events behind the gradient writes of non-final passes
+        self.announced = {}                              # expect_passes: backwards per tower this step will run
         self.dirty = False
         self._cb_queued = False
 
@@ -307,7 +315,23 @@ class GradSync:
         self.expected[tower] += 1
         self.dirty = True
 
+    def expect_passes(self, passes: Dict[str, int]):
+        """The number of backward passes this step will run through each tower named in ``passes``, told BEFORE the
+        first of them: from now until ``finish()`` the last pass of such a tower is its ``passes[tower]``-th backward,
+        not the last one announced so far, and the autograd final callback holds ``finish()`` back until every such
+        tower has seen all of its passes.  Towers not named keep counting ``note_forward`` calls."""
+        for tower, n in passes.items():
+            if tower not in self.TOWERS or int(n) < 1:
+                raise ValueError(f"expect_passes: {tower!r}: {n!r} (towers {self.TOWERS}, at least one pass each)")
+            self.announced[tower] = int(n)
+
+    def _passes_outstanding(self) -> bool:
+        return any(self.seen[t] < n for t, n in self.announced.items())
+
     def _is_last_pass(self, tower: str) -> bool:
+        n = self.announced.get(tower)
+        if n is not None:
+            return self.seen[tower] + 1 == n
         return self.expected[tower] > 0 and self.seen[tower] + 1 == self.expected[tower]
 
     def layer_cuts(self, tower: str, layers: int):
@@ -384,6 +408,8 @@ class GradSync:
 
     def _finish_callback(self):
         self._cb_queued = False
+        if self._passes_outstanding():        # expect_passes: a later backward() of this step writes these ranges again
+            return
         self.finish()
 
     def finish(self, passes_per_tower: Optional[int] = None):

@@ -174,11 +174,82 @@ def merged_step_losses(model, criterion, criterion_ot, image, text, labels_per_i
     return loss_dict
 
 
+def _sum_losses(loss_dict, check_finite: bool):
+    """engine.py:67-82: the loss SUM, and with ``check_finite`` the all-rank mean of the losses, ``.item()``, stop on a
+    non-finite value."""
+    losses = functools.reduce(operator.add, loss_dict.values())                            # engine.py:67 (sum() would add an int 0 first: one more launch)
+    if check_finite:
+        reduced = D.reduce_dict({k: v.detach() for k, v in loss_dict.items()})
+        loss_value = float(sum(v for v in reduced.values()))
+        if not math.isfinite(loss_value):
+            logging.error("Loss is {}, stopping training".format(loss_value))
+            logging.error(reduced)
+            sys.exit(1)
+    return losses
+
+
+def micro_batched_backward(model, criterion, image, text, labels_per_image, labels_per_text, index_pos, micro_batch: int,
+                           grad_sync: Optional[D.GradSync] = None, check_finite: bool = False,
+                           global_batch: bool = True) -> Dict[str, torch.Tensor]:
+    """Forward + backward of the plain contrastive step for a batch whose activation stash does not fit: the stash is
+    32-36 x width bytes per row AND block (0.45 GB per ViT-L/14@336 image), and the contrastive loss needs the features of
+    the WHOLE batch, so accumulating the gradients of small steps would be a different loss.  Instead:
+
+      1. features of every chunk of ``micro_batch`` images (and their ``micro_batch * K`` captions) without grad -- the
+         forward-only tower, which keeps no stash (``ce_tower_forward_infer``);
+      2. the head ONCE over all of them, and its backward: the gradients of the loss w.r.t. every feature row (and the
+         ``logit_scale`` gradient);
+      3. per chunk a second forward, now with the stash, and its backward with those feature gradients injected.  One
+         stash per tower lives at a time; the parameter gradients of the chunks accumulate in the flat buffer (the first
+         chunk's backward writes the block weights, ``zero_grad_first_touch``).
+
+    The towers treat rows independently, so the cut needs no knowledge of the label layout, and the loss dict is the
+    unchunked step's up to what a different tile choice at a smaller M does to the bf16 roundings.  Costs one extra tower
+    forward: 4/3 of the unchunked step's tower FLOPs.  The caller has zeroed the gradients and runs the optimiser."""
+    B, n = int(image.shape[0]), int(text.shape[0])
+    mb = int(micro_batch)
+    if mb < 1:
+        raise ValueError(f"micro_batch must be at least 1 (got {micro_batch})")
+    if n % B != 0:
+        raise RuntimeError(f"micro_batch needs the same number of captions per image ({n} captions, {B} images)")
+    K = n // B
+    lens = getattr(text, "_ce_lengths", None)
+    if lens is None:                       # tokens on the device without host lengths: ONE read-back for the whole batch
+        lens = (text.reshape(n, -1).argmax(dim=-1) + 1).cpu().numpy()
+    lens = np.asarray(lens).reshape(-1)
+    if text.dtype != torch.int64:          # the text tower would convert every view anew, and the copy carries no lengths
+        text = text.long()
+    chunks = []
+    for lo in range(0, B, mb):
+        hi = min(lo + mb, B)
+        chunks.append((lo, hi, image[lo:hi], attach_lengths(text[lo * K:hi * K], lens[lo * K:hi * K])))
+    gs = grad_sync if grad_sync is not None else getattr(model, "grad_sync", None)
+    if gs is not None and hasattr(gs, "expect_passes"):
+        gs.expect_passes({"visual": len(chunks), "text": len(chunks)})
+    # every chunk, the shorter last one included, runs in buffers leased for a full chunk (the pool is keyed by byte count)
+    model._lease_batch = {"vision": mb, "text": mb * K}
+    try:
+        with torch.no_grad():
+            feats = [model.encode_both(img_c, txt_c) for _, _, img_c, txt_c in chunks]
+        fi = torch.cat([f[0] for f in feats], dim=0).requires_grad_()
+        ft = torch.cat([f[1] for f in feats], dim=0).requires_grad_()
+        del feats
+        loss_dict = _contrastive_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch)
+        _sum_losses(loss_dict, check_finite).backward()        # fi.grad, ft.grad, logit_scale.grad; no tower node, no exchange
+        for lo, hi, img_c, txt_c in chunks:
+            fi_c, ft_c = model.encode_both(img_c, txt_c)
+            torch.autograd.backward([fi_c, ft_c], [fi.grad[lo:hi], ft.grad[lo * K:hi * K]])
+            del fi_c, ft_c
+    finally:
+        model._lease_batch = None
+    return loss_dict
+
+
 def train_step(model, criterion, optimizer, image, text, labels_per_image, labels_per_text, index_pos,
                grad_sync: Optional[D.GradSync] = None, criterion_ot: Optional[CriterionAlignment] = None,
                object_vec=None, entitytxt_vec=None, object_num=None, entitytxt_num=None,
                check_finite: bool = False, train_arg=None, bboxs=None, bbox_desc_vec=None,
-               bbox_label_vec=None, text_lengths=None) -> Dict[str, torch.Tensor]:
+               bbox_label_vec=None, text_lengths=None, micro_batch: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """One iteration of engine.py:48-95.  BASELINE config 4 is this call with ``criterion_ot`` + the object / entity
     tensors (``model.alignment``) and ``train_arg`` + boxes in ONE step, as the reference's forward takes them
     (model_clip.py:419-528, engine.py:57-63).  ``check_finite`` reproduces engine.py:70-81 (all-rank mean of the
@@ -189,9 +260,18 @@ def train_step(model, criterion, optimizer, image, text, labels_per_image, label
     caption lengths are then taken on the host and travel with the asynchronous copy, so the text tower never reads
     anything back from the device.  For tokens already on the GPU pass ``text_lengths`` (host integers, tokens up to and
     including the EOT) or tag the tensor with ``functional.attach_lengths``; without either the lengths are read back
-    (one small synchronous copy per new tensor)."""
+    (one small synchronous copy per new tensor).
+
+    ``micro_batch`` (images per chunk; None or >= the number of images: the step above, untouched) runs the plain contrastive
+    step for a batch whose activation stash does not fit the card: see ``micro_batched_backward``.  Same loss over the whole
+    batch, one extra tower forward.  Not available with ``train_arg`` / ``criterion_ot``."""
     wrapped = model
     model = _unwrap(model)
+    chunked = micro_batch is not None and int(micro_batch) < int(image.shape[0])
+    if chunked and (train_arg is not None or criterion_ot is not None):
+        raise NotImplementedError("train_step(micro_batch=...) covers the plain contrastive step only: the region / alignment "
+                                  "losses of train_arg / criterion_ot couple rows inside the towers' outputs; run that "
+                                  "configuration without micro_batch")
     dev = next(model.parameters()).device
     _throttle(model)
     if text_lengths is not None:
@@ -206,7 +286,10 @@ def train_step(model, criterion, optimizer, image, text, labels_per_image, label
     else:
         optimizer.zero_grad()
     want_align = model.alignment and criterion_ot is not None
-    if (want_align or train_arg is not None) and os.environ.get("CE_MERGE_PASSES", "1") != "0":
+    if chunked:
+        loss_dict = micro_batched_backward(model, criterion, image, text, labels_per_image, labels_per_text, index_pos,
+                                           int(micro_batch), grad_sync=grad_sync, check_finite=check_finite)
+    elif (want_align or train_arg is not None) and os.environ.get("CE_MERGE_PASSES", "1") != "0":
         # config 4: one pass per tower over [images | object crops] and [captions | entity mentions | role texts]
         loss_dict = merged_step_losses(model, criterion, criterion_ot if want_align else None, image, text, labels_per_image,
                                        labels_per_text, index_pos, train_arg=train_arg, bboxs=bboxs, bbox_desc_vec=bbox_desc_vec,
@@ -219,15 +302,8 @@ def train_step(model, criterion, optimizer, image, text, labels_per_image, label
         if want_align:
             image_features, text_features = model.sim_entity(object_vec, entitytxt_vec)       # engine.py:57-63
             loss_dict.update(criterion_ot(text_features, image_features, entitytxt_num, object_num))
-    losses = functools.reduce(operator.add, loss_dict.values())                            # engine.py:67 (sum() would add an int 0 first: one more launch)
-    if check_finite:
-        reduced = D.reduce_dict({k: v.detach() for k, v in loss_dict.items()})
-        loss_value = float(sum(v for v in reduced.values()))
-        if not math.isfinite(loss_value):
-            logging.error("Loss is {}, stopping training".format(loss_value))
-            logging.error(reduced)
-            sys.exit(1)
-    losses.backward()
+    if not chunked:
+        _sum_losses(loss_dict, check_finite).backward()
     if check_finite and getattr(model, "stream16", False):
         # the fp16 streams clamp instead of overflowing, so a clipped activation / gradient never shows up as a non-finite
         # loss: read the device-side clamp counters on the synchronisation this mode pays anyway, before the update is applied

@@ -1,7 +1,8 @@
 """Coarse autograd nodes of the HIP path: one per tower pass, one for the logits.
 
 Each ``forward`` issues the HIP launches through the C ABI and keeps the activation stash
-(a leased workspace carved by the C++ tower runner); each ``backward`` runs the HIP backward
+(a leased workspace carved by the C++ tower runner) -- or, when grad mode was off at the call,
+runs the forward-only tower (``ce_tower_forward_infer``) and keeps nothing; each ``backward`` runs the HIP backward
 and accumulates parameter gradients directly into the model's flat gradient buffer (the
 ``nn.Parameter.grad`` views), returning ``None`` for the trigger input that only exists to put
 the node on the autograd tape.
@@ -24,13 +25,31 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.contiguous().float()
 
 
-def _tower_workspace(model, desc, batch: int, tag: str):
+def _tower_workspace(model, desc, batch: int, tag: str, infer: bool = False):
+    """Lease the tower's workspace: the activation stash + backward scratch, or -- ``infer`` -- the forward-only buffers.
+    ``model._lease_batch`` ({tag: samples}, set by the micro-batched step) sizes the lease for at least that many samples, so
+    that a shorter last chunk runs in the full chunk's buffer (the pool is keyed by byte count and never frees)."""
     from .model import _Lease
-    nbytes = lib().ce_tower_workspace_bytes(ctypes.byref(desc), c_int(batch))
+    fn = lib().ce_tower_infer_workspace_bytes if infer else lib().ce_tower_workspace_bytes
+    fn.restype = ctypes.c_size_t
+    hint = getattr(model, "_lease_batch", None)
+    nbytes = fn(ctypes.byref(desc), c_int(max(batch, hint.get(tag, 0)) if hint else batch))
     if nbytes == 0:
-        raise RuntimeError("ce_tower_workspace_bytes: " + lib().ce_last_error().decode())
+        raise RuntimeError(fn.__name__ + ": " + lib().ce_last_error().decode())
+    if infer:
+        tag = tag + ".infer"
     buf = model._pool.take(tag, int(nbytes), model._flat.device)
     return _Lease(model._pool, tag, buf)
+
+
+def _tower_forward_infer(model, desc, tag: str, batch: int, rows: int, cu, x0, x_out, sel):
+    """Tower forward that no backward will follow (``ce_tower_forward_infer``): nothing is stashed, the buffers go back to
+    the pool as soon as the launches are enqueued (the next lease of this tag is taken on the same stream, as the
+    training leases are)."""
+    lease = _tower_workspace(model, desc, batch, tag, infer=True)
+    check(lib().ce_tower_forward_infer(ctypes.byref(desc), c_int(batch), c_int(rows), ptr(cu), ptr(x0), ptr(lease.buf),
+                                       ptr(x_out), ptr(sel), stream()), f"ce_tower_forward_infer({tag})")
+    lease.release()
 
 
 def _publish_to_main(ctx):
@@ -218,7 +237,7 @@ class EncodeImageFn(torch.autograd.Function):
     """VisualTransformer.forward (model_clip.py:232-263) as one autograd node."""
 
     @staticmethod
-    def forward(ctx, image, trigger, model, use_grid: bool):
+    def forward(ctx, image, trigger, model, use_grid: bool, infer: bool = False):
         cl, s = lib(), stream()
         v = model.visual
         dev = model._flat.device
@@ -248,7 +267,6 @@ class EncodeImageFn(torch.autograd.Function):
         check(cl.ce_layernorm_fwd_t(ptr(xpre), c_int(L.T_F32), c_long(D), None, ptr(P["visual.ln_pre.weight"]),
                                     ptr(P["visual.ln_pre.bias"]), ptr(x0), c_int(ST), c_long(D), ptr(mean_pre), ptr(rstd_pre),
                                     c_int(M), c_int(D), c_float(1e-5), s), "ce_layernorm_fwd(ln_pre)")
-        lease = _tower_workspace(model, model._vdesc, B, "vision")
         if use_grid:
             rows, n = None, M
         else:                      # only the CLS row of each image is consumed (model_clip.py:256): pruned last block
@@ -258,9 +276,13 @@ class EncodeImageFn(torch.autograd.Function):
                 rows = cache[(B, T, dev)] = (torch.arange(B, device=dev, dtype=torch.int32) * T)
             n = B
         xN = _empty((n, D), sdt, dev)
-        check(cl.ce_tower_forward(ctypes.byref(model._vdesc), c_int(B), c_int(M), None, ptr(x0), ptr(lease.buf), ptr(xN),
-                                  ptr(rows), s),
-              "ce_tower_forward(vision)")
+        if infer:                  # grad mode was off at the call (CLIP.encode_image): no stash, nothing kept for a backward
+            _tower_forward_infer(model, model._vdesc, "vision", B, M, None, x0, xN, rows)
+        else:
+            lease = _tower_workspace(model, model._vdesc, B, "vision")
+            check(cl.ce_tower_forward(ctypes.byref(model._vdesc), c_int(B), c_int(M), None, ptr(x0), ptr(lease.buf), ptr(xN),
+                                      ptr(rows), s),
+                  "ce_tower_forward(vision)")
         hpost = _empty((n, D), torch.bfloat16, dev)
         mean_post, rstd_post = _empty((n,), torch.float32, dev), _empty((n,), torch.float32, dev)
         check(cl.ce_layernorm_fwd_t(ptr(xN), c_int(ST), c_long(D), None, ptr(P["visual.ln_post.weight"]),
@@ -271,6 +293,8 @@ class EncodeImageFn(torch.autograd.Function):
         check(cl.ce_gemm_nt(ptr(hpost), c_long(D), ptr(wp), c_long(D), c_int(n), c_int(E), c_int(D), c_int(L.EPI_F32),
                             None, None, c_long(0), ptr(feat), c_long(E), None, c_long(0), None, c_long(0), s),
               "ce_gemm_nt(visual.proj)")
+        if infer:
+            return feat.view(B, T, E) if use_grid else feat
         ctx.model, ctx.lease, ctx.use_grid, ctx.B = model, lease, use_grid, B
         ctx.stream16 = sdt == torch.float16
         ctx.main_stream = getattr(model, "_main_stream", None)
@@ -354,14 +378,14 @@ class EncodeImageFn(torch.autograd.Function):
         if model.grad_sync is not None:
             model.grad_sync(model, "visual")
         _publish_to_main(ctx)
-        return None, None, None, None
+        return None, None, None, None, None
 
 
 class EncodeTextFn(torch.autograd.Function):
     """CLIP.encode_text (model_clip.py:398-417) as one autograd node."""
 
     @staticmethod
-    def forward(ctx, text, trigger, model):
+    def forward(ctx, text, trigger, model, infer: bool = False):
         cl, s = lib(), stream()
         dev = model._flat.device
         if text.device != dev:
@@ -381,11 +405,14 @@ class EncodeTextFn(torch.autograd.Function):
         check(cl.ce_token_embed_t(ptr(text), ptr(pk.src), ptr(P["token_embedding.weight"]), ptr(P["positional_embedding"]),
                                   ptr(x0), c_int(ST), c_long(M), c_int(T), c_int(D), c_int(model.vocab_size), s),
               "ce_token_embed")
-        lease = _tower_workspace(model, model._tdesc, n, "text")
         rows = pk.sel                                      # EOT row of each caption (argmax token id, model_clip.py:415)
         xN = _empty((n, D), sdt, dev)                      # pruned last block: only the EOT rows are produced
-        check(cl.ce_tower_forward(ctypes.byref(model._tdesc), c_int(n), c_int(M), ptr(pk.cu), ptr(x0), ptr(lease.buf),
-                                  ptr(xN), ptr(rows), s), "ce_tower_forward(text)")
+        if infer:                  # grad mode was off at the call (CLIP.encode_text): no stash, nothing kept for a backward
+            _tower_forward_infer(model, model._tdesc, "text", n, M, pk.cu, x0, xN, rows)
+        else:
+            lease = _tower_workspace(model, model._tdesc, n, "text")
+            check(cl.ce_tower_forward(ctypes.byref(model._tdesc), c_int(n), c_int(M), ptr(pk.cu), ptr(x0), ptr(lease.buf),
+                                      ptr(xN), ptr(rows), s), "ce_tower_forward(text)")
         hfin = _empty((n, D), torch.bfloat16, dev)
         mean_f, rstd_f = _empty((n,), torch.float32, dev), _empty((n,), torch.float32, dev)
         check(cl.ce_layernorm_fwd_t(ptr(xN), c_int(ST), c_long(D), None, ptr(P["ln_final.weight"]), ptr(P["ln_final.bias"]),
@@ -396,6 +423,8 @@ class EncodeTextFn(torch.autograd.Function):
         check(cl.ce_gemm_nt(ptr(hfin), c_long(D), ptr(wp), c_long(D), c_int(n), c_int(E), c_int(D), c_int(L.EPI_F32),
                             None, None, c_long(0), ptr(feat), c_long(E), None, c_long(0), None, c_long(0), s),
               "ce_gemm_nt(text_projection)")
+        if infer:
+            return feat
         ctx.model, ctx.lease, ctx.n = model, lease, n
         ctx.stream16 = sdt == torch.float16
         ctx.main_stream = getattr(model, "_main_stream", None)
@@ -450,7 +479,7 @@ class EncodeTextFn(torch.autograd.Function):
         if model.grad_sync is not None:
             model.grad_sync(model, "text")
         _publish_to_main(ctx)
-        return None, None, None
+        return None, None, None, None
 
 
 def _sgemm(A, sam, sak, Bm, sbk, sbn, C, M, N, K, alpha_ptr=None, alpha=1.0, alpha_exp=0, beta=0.0):

@@ -239,7 +239,7 @@ class CLIP(nn.Module):
     _RUNTIME = ("_flat", "_flat_grad", "_flat16", "_offsets", "_ranges", "_layer_end", "_pmap", "_pool", "_trigger",
                 "_versions", "_w16", "_w16t", "_kp", "_kp_real", "_conv_pad", "_conv_gpad", "_cast_list", "_tjobs",
                 "_tjobs_bwd", "_adam_tiles_ok", "_wt_fresh", "_wt_event", "_aux_stream", "_mirror_fresh", "_mirror_versions", "_vdesc", "_tdesc", "_vblocks", "_tblocks",
-                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch")
+                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch", "_lease_batch")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -756,7 +756,8 @@ class CLIP(nn.Module):
         self._ready()
         self._note_pass("visual")
         from .functional import EncodeImageFn
-        return EncodeImageFn.apply(image, self._trigger, self, bool(use_grid))
+        # decided HERE: inside autograd.Function.forward grad mode is always off.  Without grad the tower keeps no stash.
+        return EncodeImageFn.apply(image, self._trigger, self, bool(use_grid), not torch.is_grad_enabled())
 
     def encode_text(self, text, lengths=None):
         """model_clip.py:398-417.  ``lengths`` (optional, host integers: tokens up to and including each caption's EOT) spares
@@ -766,7 +767,7 @@ class CLIP(nn.Module):
         from .functional import EncodeTextFn, attach_lengths
         if lengths is not None:
             attach_lengths(text, lengths)
-        return EncodeTextFn.apply(text, self._trigger, self)
+        return EncodeTextFn.apply(text, self._trigger, self, not torch.is_grad_enabled())
 
     def encode_both(self, image, text, use_grid: bool = False):
         """Image and text towers of one step.  They are independent until the logits, so with

@@ -42,8 +42,10 @@ enum {
                                * factor the backward needs, from the fp32 a; out2(bf16) = QuickGELU(a) = a s */
     CE_EPI_GELUGRAD_BF16 = 6, /* out(bf16) = acc * aux(bf16), aux = the derivative BIAS_GELU saved; out2 (nullable) is reused as
                                * a float[N] that receives += the column sums of out (bias gradient)      */
-    CE_EPI_BIAS_RESID_F16 = 7 /* out(f16)  = resid(f16) + acc + bias[n]: the residual add on an fp16 stream (CE_T_F16;
+    CE_EPI_BIAS_RESID_F16 = 7,/* out(f16)  = resid(f16) + acc + bias[n]: the residual add on an fp16 stream (CE_T_F16;
                                * resid / out point at IEEE half data, ldr / ldo in elements; stores saturate at 65504) */
+    CE_EPI_BIAS_QGELU_BF16 = 8/* out(bf16) = QuickGELU(acc + bias[n]): BIAS_GELU's out2 bit for bit (same tile variant at the same
+                               * M, N, K), without the derivative -- the forward that no backward follows; out2 unused */
 };
 
 /* Element types of residual-stream operands (ce_layernorm_*_t, ce_token_embed_t, ce_cast_t, ce_tower_desc.stream16).
@@ -370,6 +372,15 @@ size_t ce_tower_workspace_bytes(const ce_tower_desc* d, int batch);
  * cu_seqlens[b] .. cu_seqlens[b+1]-1; sel_rows then index the packed rows. */
 int ce_tower_forward(const ce_tower_desc* d, int batch, int rows, const int* cu_seqlens, const void* x0,
                      void* workspace, void* x_out, const int* sel_rows, void* stream);
+/* The same forward when NO backward follows (inference; the features-only first pass of a micro-batched step): the launches of
+ * ce_tower_forward in the same order with the same shapes, so x_out is bit-identical, but nothing is stashed -- every buffer
+ * is reused from block to block (two stream-typed buffers for x, one each of h, qkv, o, g, LayerNorm statistics, lse, the
+ * compact buffers of the pruned block, the fp8 scratch) and mlp.c_fc runs CE_EPI_BIAS_QGELU_BF16.  The workspace is
+ * ce_tower_infer_workspace_bytes(d, batch): 22 (fp16 stream) or 26 (fp32) x width bytes per row, 26 / 30 with the fp8 scratch,
+ * whatever d->layers is -- against 32-36 x width per row AND block plus 162 x width per row of backward rings.  x0 is not written. */
+size_t ce_tower_infer_workspace_bytes(const ce_tower_desc* d, int batch);
+int ce_tower_forward_infer(const ce_tower_desc* d, int batch, int rows, const int* cu_seqlens, const void* x0,
+                           void* workspace, void* x_out, const int* sel_rows, void* stream);
 /* dx (f32 [B*T, width]) = gradient w.r.t. x0.  Full mode (sel_rows NULL): dx holds the gradient w.r.t. x_out on
  * entry (in place).  Pruned mode: dx_sel (f32 [B, width]) is the gradient w.r.t. the [B, width] output and dx is
  * output only.  Parameter gradients are accumulated into the g_* buffers. */
@@ -458,14 +469,15 @@ int ce_region_nce_bwd(const float* region, const float* desc, const float* label
  * bytes} and resets.  Used by bench.py for the `roofline` object; off by default. ---- */
 #define CE_PROF_NT_FAMILIES 8
 enum {
-    CE_PROF_GEMM_NT0 = 0, /* + CE_PROF_NT_FAMILIES * epilogue id (0..7) + kernel family: 0 gemm_nt_kernel (128x128, register
+    CE_PROF_GEMM_NT0 = 0, /* + CE_PROF_NT_FAMILIES * epilogue id (0..7; CE_EPI_BIAS_QGELU_BF16: CE_PROF_GEMM_NT_QGELU) + kernel family: 0 gemm_nt_kernel (128x128, register
                            * staged), 1 gemm_nt256_kernel<.,.,2> (160x128, 4 waves), 2 gemm_nt256_kernel<.,.,4> (256 columns,
                            * 8 waves), 3 gemm_nt32_kernel (160x256x32), 4 gemm_nt8_kernel (fp8), 5 gemm_nt160lw_kernel (160x256,
                            * loader waves), 6 gemm_nt160p_kernel (its persistent form), 7 gemm_nt_skinny_kernel (M <= 512) -- one class per
                            * rocprofv3 kernel row */
     CE_PROF_GEMM_TN = 64, CE_PROF_ATTN_FWD = 65, CE_PROF_ATTN_BWD = 66, CE_PROF_LN_FWD = 67, CE_PROF_LN_BWD = 68,
     CE_PROF_COLSUM = 69, CE_PROF_OTHER = 70, CE_PROF_GEMM_TN2 = 71 /* gemm_tn2_kernel; CE_PROF_GEMM_TN = gemm_tn3_kernel */,
-    CE_PROF_NCLASS = 72
+    CE_PROF_GEMM_NT_QGELU = 72, /* + kernel family: the NT kernels with CE_EPI_BIAS_QGELU_BF16 (the ids up to 71 keep their meaning) */
+    CE_PROF_NCLASS = 80
 };
 void ce_profile_enable(int on);
 int ce_profile_collect(double* out, int max_classes);

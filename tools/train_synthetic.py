@@ -2,7 +2,11 @@
 """The reference's training loop (train.py:101-250 / engine.py:24-102) on the drop-in API, end to end on synthetic
 data: decoded uint8 images -> on-device preprocessing -> CLIP forward (hard-negative descriptions, per-batch labels as
 dataset_voa.py builds them) -> CriterionContrastive -> fused clip + Adam -> warm-up cosine schedule -> checkpoint in
-the reference's layout -> resume from it.  A smoke run of every host-side component together, not a benchmark."""
+the reference's layout -> resume from it.  A smoke run of every host-side component together, not a benchmark.
+
+``--micro-batch N`` runs every step in chunks of N images (engine.train_step(micro_batch=N): the step for batches whose
+activation stash does not fit)."""
+import argparse
 import os
 import sys
 import tempfile
@@ -32,6 +36,9 @@ def batch(rng, B, K, dev):
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--micro-batch", type=int, default=None, metavar="N", help="images per chunk of a step (default: unchunked)")
+    mb = ap.parse_args().micro_batch
     dev = torch.device("cuda", 0)
     cfg = {"optimizer": "adam", "lr": 1e-5, "weight_decay": 0.0, "momentum": 0.9, "lr_scheduler": "warmup",
            "max_epoch": 40, "warmup_epoch": 4, "lr_steps": [], "lr_gamma": 0.1, "task": "clipevent"}
@@ -45,7 +52,7 @@ def main():
     data = batch(rng, B, K, dev)                                                # one fixed batch: the loss must fall
     losses = []
     for it in range(20):
-        ld = train_step(model, criterion, optimizer, *data, check_finite=True)
+        ld = train_step(model, criterion, optimizer, *data, check_finite=True, micro_batch=mb)
         scheduler.step()
         losses.append(float(sum(v.detach() for v in ld.values())))
     print("loss:", " ".join(f"{v:.3f}" for v in losses[::3]), "lr", optimizer.param_groups[0]["lr"])
@@ -57,13 +64,13 @@ def main():
         optimizer2.load_state_dict(opt_state)
         scheduler2 = build_lr_scheduler(cfg, optimizer2, begin_epoch)
     assert begin_epoch == 20 and abs(optimizer2.param_groups[0]["lr"] - optimizer.param_groups[0]["lr"]) < 1e-12
-    a = train_step(model, criterion, optimizer, *data)
-    b = train_step(model2, criterion, optimizer2, *data)
+    a = train_step(model, criterion, optimizer, *data, micro_batch=mb)
+    b = train_step(model2, criterion, optimizer2, *data, micro_batch=mb)
     la, lb = float(sum(v.detach() for v in a.values())), float(sum(v.detach() for v in b.values()))
     print(f"resumed run continues: loss {la:.5f} vs {lb:.5f}")
     assert abs(la - lb) < 1e-3 * max(1.0, abs(la))
     new = batch(rng, B, K, dev)                                                 # a fresh ragged batch goes through too
-    ld = train_step(model2, criterion, optimizer2, *new)
+    ld = train_step(model2, criterion, optimizer2, *new, micro_batch=mb)
     scheduler2.step()
     assert all(torch.isfinite(v) for v in ld.values())
     # a longer stretch of fresh batches with no host synchronisation in the loop: host-side caption lengths, the run-ahead
@@ -71,11 +78,11 @@ def main():
     import time
     batches = [batch(rng, 32, K, dev) for _ in range(8)]
     for it in range(4):                                                         # new batch size: workspaces are allocated here
-        train_step(model2, criterion, optimizer2, *batches[it])
+        train_step(model2, criterion, optimizer2, *batches[it], micro_batch=mb)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(96):
-        ld = train_step(model2, criterion, optimizer2, *batches[it % 8])
+        ld = train_step(model2, criterion, optimizer2, *batches[it % 8], micro_batch=mb)
         scheduler2.step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / 96
