@@ -295,6 +295,196 @@ __global__ __launch_bounds__(256) void adam_segments_kernel(float* __restrict__ 
     }
 }
 
+// ---- clip + SGD with momentum (torch.optim.SGD: engine.py:136-140 behind engine.py:89's clip) ----------------------------------
+// One element.  As adam_elem: every kernel form updates through this function with the multiply-adds spelled out, so that the flat,
+// the tile and the segment kernel give the same bits.  `first`: no momentum buffer yet -- it becomes a copy of the decayed gradient
+// whatever the dampening is (torch).  mu == 0: `buf` is neither read nor written.
+__device__ __forceinline__ void sgd_elem(float& p, float g, float& buf, float coef, float wd, float mu, float one_minus_damp,
+                                         float lr, bool first, bool nesterov) {
+#pragma clang fp contract(off)
+    g = g * coef;
+    if (wd != 0.f) g = __builtin_fmaf(p, wd, g);
+    float upd = g;
+    if (mu != 0.f) {
+        buf = first ? g : __builtin_fmaf(buf, mu, g * one_minus_damp);
+        upd = nesterov ? __builtin_fmaf(buf, mu, g) : buf;
+    }
+    p = __builtin_fmaf(-lr, upd, p);
+}
+__device__ __forceinline__ void sgd_elem4(f32x4& p, f32x4 g, f32x4& buf, float coef, float wd, float mu, float one_minus_damp,
+                                          float lr, bool first, bool nesterov) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float pe = p[e], be = buf[e];
+        sgd_elem(pe, g[e], be, coef, wd, mu, one_minus_damp, lr, first, nesterov);
+        p[e] = pe; buf[e] = be;
+    }
+}
+
+// scalar arguments of the three SGD kernels
+struct sgd_args {
+    const float* sumsq;
+    float max_norm, lr, mu, one_minus_damp, wd;
+    int first, nesterov;
+};
+__device__ __forceinline__ float clip_coef(const float* __restrict__ sumsq, float max_norm) {
+    return sumsq ? fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f)) : 1.0f;
+}
+
+// MOM = false: momentum 0, `buf` is NULL and no momentum traffic is issued (8 B read + 6 B written per parameter);
+// MOM = true: 12 B read + 10 B written.  The access pattern is adam_kernel's.
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                  bf16_t* __restrict__ p16, long n, sgd_args a) {
+    const float coef = clip_coef(a.sumsq, a.max_norm);
+    const float mu = MOM ? a.mu : 0.f;
+    const bool first = a.first != 0, nesterov = a.nesterov != 0;
+    const long stride = gridDim.x * 2048L;
+    for (long i0 = blockIdx.x * 2048L + threadIdx.x * 4; i0 < n; i0 += stride) {
+        const long i1 = i0 + 1024;
+        if (i1 + 3 < n) {
+            f32x4 pv[2], gv[2], bv[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const long i = u ? i1 : i0;
+                pv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(p + i));
+                gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + i));
+                bv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (MOM) bv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(buf + i));
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const long i = u ? i1 : i0;
+                sgd_elem4(pv[u], gv[u], bv[u], coef, a.wd, mu, a.one_minus_damp, a.lr, first, nesterov);
+                CE_ADAM_ST(pv[u], reinterpret_cast<f32x4*>(p + i));
+                if (p16) {
+                    u32x2 pk = {pack_bf2(pv[u][0], pv[u][1]), pack_bf2(pv[u][2], pv[u][3])};
+                    *reinterpret_cast<u32x2*>(p16 + i) = pk;
+                }
+                if (MOM) CE_ADAM_ST(bv[u], reinterpret_cast<f32x4*>(buf + i));
+            }
+        } else {
+            for (int u = 0; u < 2; ++u) {
+                const long ib = u ? i1 : i0;
+                for (long k = ib; k < n && k < ib + 4; ++k) {
+                    float pk = p[k], bk = MOM ? buf[k] : 0.f;
+                    sgd_elem(pk, g[k], bk, coef, a.wd, mu, a.one_minus_damp, a.lr, first, nesterov);
+                    p[k] = pk;
+                    if (MOM) buf[k] = bk;
+                    if (p16) p16[k] = f2bf(pk);
+                }
+            }
+        }
+    }
+}
+
+// adam_tiles_kernel with the SGD update: one 64 x 64 tile of a bf16-mirrored matrix per workgroup, the new masters, the
+// momentum buffer, the row-major mirror and -- through the LDS transpose -- the W^T copy (12 B read + 12 B written per parameter)
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_tiles_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                        bf16_t* __restrict__ p16, const ce_transpose_job* __restrict__ jobs, int njobs,
+                                                        sgd_args a) {
+    __shared__ bf16_t tile[64][66];
+    const float coef = clip_coef(a.sumsq, a.max_norm);
+    const float mu = MOM ? a.mu : 0.f;
+    const bool first = a.first != 0, nesterov = a.nesterov != 0;
+    int j = 0;
+    const int b = blockIdx.x;
+    while (j + 1 < njobs && b >= jobs[j + 1].tile_start) ++j;      // block-uniform
+    const ce_transpose_job job = jobs[j];
+    const int t = b - job.tile_start;
+    const int tiles_c = (job.cols + 63) / 64;
+    const int r0 = (t / tiles_c) * 64, c0 = (t % tiles_c) * 64;
+    const long off = reinterpret_cast<const bf16_t*>(job.src) - p16;
+    bf16_t* dst = reinterpret_cast<bf16_t*>(job.dst);
+    // 64 rows x 16 four-element chunks; all twelve loads of a thread in flight before the first use
+    f32x4 pv[4], gv[4], bv[4];
+    bool ok[4];
+    long at[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int idx = threadIdx.x + k * 256;
+        const int r = idx >> 4, ch = idx & 15;
+        ok[k] = r0 + r < job.rows && c0 + ch * 4 < job.cols;
+        at[k] = off + (long)(r0 + r) * job.cols + c0 + ch * 4;
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        pv[k] = z; gv[k] = z; bv[k] = z;
+        if (ok[k]) {
+            pv[k] = CE_ADAM_LD(reinterpret_cast<f32x4*>(p + at[k]));
+            gv[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + at[k]));
+            if (MOM) bv[k] = CE_ADAM_LD(reinterpret_cast<f32x4*>(buf + at[k]));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int idx = threadIdx.x + k * 256;
+        const int r = idx >> 4, ch = idx & 15;
+        sgd_elem4(pv[k], gv[k], bv[k], coef, a.wd, mu, a.one_minus_damp, a.lr, first, nesterov);
+        const u32x2 pk = {pack_bf2(pv[k][0], pv[k][1]), pack_bf2(pv[k][2], pv[k][3])};
+        uint32_t* trow = reinterpret_cast<uint32_t*>(&tile[r][ch * 4]);
+        trow[0] = pk[0]; trow[1] = pk[1];
+        if (ok[k]) {
+            CE_ADAM_ST(pv[k], reinterpret_cast<f32x4*>(p + at[k]));
+            __builtin_nontemporal_store(pk, reinterpret_cast<u32x2*>(p16 + at[k]));
+            if (MOM) CE_ADAM_ST(bv[k], reinterpret_cast<f32x4*>(buf + at[k]));
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int idx = threadIdx.x + k * 256;                 // 64 output rows (source columns) x 8 chunks of 8 source rows
+        const int c = idx >> 3, ch = idx & 7;
+        if (c0 + c < job.cols && r0 + ch * 8 < job.rows) {
+            uint32_t w[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                w[e] = (uint32_t)tile[ch * 8 + 2 * e][c] | ((uint32_t)tile[ch * 8 + 2 * e + 1][c] << 16);
+            __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4*>(dst + (long)(c0 + c) * job.rows + r0 + ch * 8));
+        }
+    }
+}
+
+// adam_segments_kernel with the SGD update: one workgroup per [lo, hi) chunk of at most 2048 elements
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_segments_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                           bf16_t* __restrict__ p16, const long* __restrict__ table, sgd_args a) {
+    const float coef = clip_coef(a.sumsq, a.max_norm);
+    const float mu = MOM ? a.mu : 0.f;
+    const bool first = a.first != 0, nesterov = a.nesterov != 0;
+    const long lo = table[2 * blockIdx.x], hi = table[2 * blockIdx.x + 1];
+    f32x4 pv[2], gv[2], bv[2];
+    long at[2];
+    bool ok[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        at[u] = lo + threadIdx.x * 4 + u * 1024;
+        ok[u] = at[u] + 3 < hi;
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        pv[u] = z; gv[u] = z; bv[u] = z;
+        if (ok[u]) {
+            pv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(p + at[u]));
+            gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + at[u]));
+            if (MOM) bv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(buf + at[u]));
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (!ok[u]) continue;
+        sgd_elem4(pv[u], gv[u], bv[u], coef, a.wd, mu, a.one_minus_damp, a.lr, first, nesterov);
+        CE_ADAM_ST(pv[u], reinterpret_cast<f32x4*>(p + at[u]));
+        if (p16) *reinterpret_cast<u32x2*>(p16 + at[u]) = u32x2{pack_bf2(pv[u][0], pv[u][1]), pack_bf2(pv[u][2], pv[u][3])};
+        if (MOM) CE_ADAM_ST(bv[u], reinterpret_cast<f32x4*>(buf + at[u]));
+    }
+}
+
+// torch.optim.SGD's argument rules (plus: a momentum buffer must exist when momentum is used); 0 or -EINVAL with a message
+int sgd_check(const char* who, const float* buf, float momentum, float dampening, int nesterov) {
+    CE_CHECK_ARG(momentum >= 0.f, "%s: invalid momentum value %g", who, (double)momentum);
+    CE_CHECK_ARG(!nesterov || (momentum > 0.f && dampening == 0.f), "%s: nesterov momentum requires a momentum and zero dampening", who);
+    CE_CHECK_ARG(momentum == 0.f || buf, "%s: momentum %g needs a momentum buffer", who, (double)momentum);
+    return 0;
+}
+
 // Bias corrections in double, rounded once to fp32 -- as torch.optim.Adam takes them (Python floats).  In fp32, 1 - powf(beta2,
 // step) cancels: at step 2 (1 - 0.998) the rounding of powf is up to 1.5e-5 of the result, and the update inherits it.
 float adam_bc1(float beta1, int step) { return (float)(1.0 - pow((double)beta1, (double)step)); }
@@ -352,6 +542,47 @@ extern "C" int ce_adam_step_tiles(float* p, const float* g, float* m, float* v, 
     if (nsegments > 0)
         hipLaunchKernelGGL(adam_segments_kernel, dim3((unsigned)nsegments), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
                            segments_device, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_sgd_step(float* p, const float* g, float* buf, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+                           float momentum, float dampening, float weight_decay, int nesterov, int first_step, void* stream) {
+    CE_CHECK_ARG(n > 0, "ce_sgd_step: need n>0");
+    if (int rc = sgd_check("ce_sgd_step", buf, momentum, dampening, nesterov)) return rc;
+    CE_CHECK_ARG(p && g, "ce_sgd_step: null buffer");
+    const sgd_args a = {sumsq, max_norm, lr, momentum, 1.0f - dampening, weight_decay, first_step != 0, nesterov != 0};
+    long blocks = (n + 2047) / 2048;
+    static const long cap = getenv("CE_ADAM_BLOCKS") ? atol(getenv("CE_ADAM_BLOCKS")) : 4096;
+    if (blocks > cap) blocks = cap;
+    if (momentum > 0.f)
+        hipLaunchKernelGGL(sgd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, (bf16_t*)p_bf16, n, a);
+    else
+        hipLaunchKernelGGL(sgd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, (float*)nullptr,
+                           (bf16_t*)p_bf16, n, a);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_sgd_step_tiles(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                                 int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm,
+                                 float lr, float momentum, float dampening, float weight_decay, int nesterov, int first_step,
+                                 void* stream) {
+    if (int rc = sgd_check("ce_sgd_step_tiles", buf, momentum, dampening, nesterov)) return rc;
+    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "ce_sgd_step_tiles: nothing to update");
+    CE_CHECK_ARG(p && g && p_bf16, "ce_sgd_step_tiles: null buffer");
+    const sgd_args a = {sumsq, max_norm, lr, momentum, 1.0f - dampening, weight_decay, first_step != 0, nesterov != 0};
+    const bool mom = momentum > 0.f;
+    hipStream_t s = (hipStream_t)stream;
+    bf16_t* p16 = (bf16_t*)p_bf16;
+    if (jobs_device && njobs > 0 && total_tiles > 0) {
+        if (mom) hipLaunchKernelGGL(sgd_tiles_kernel<true>, dim3((unsigned)total_tiles), dim3(256), 0, s, p, g, buf, p16, jobs_device, njobs, a);
+        else hipLaunchKernelGGL(sgd_tiles_kernel<false>, dim3((unsigned)total_tiles), dim3(256), 0, s, p, g, (float*)nullptr, p16, jobs_device, njobs, a);
+    }
+    if (segments_device && nsegments > 0) {
+        if (mom) hipLaunchKernelGGL(sgd_segments_kernel<true>, dim3((unsigned)nsegments), dim3(256), 0, s, p, g, buf, p16, segments_device, a);
+        else hipLaunchKernelGGL(sgd_segments_kernel<false>, dim3((unsigned)nsegments), dim3(256), 0, s, p, g, (float*)nullptr, p16, segments_device, a);
+    }
     CE_LAUNCH_CHECK();
     return 0;
 }

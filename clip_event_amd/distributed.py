@@ -435,14 +435,16 @@ class GradSync:
 
 
 def consolidate(model, optimizer):
-    """COLLECTIVE (every rank calls it): after sharded optimiser steps, gather both Adam moments from their owners so that
-    ``optimizer.state_dict()`` -- the 'optimizer' entry of a checkpoint -- can be taken on any rank.  (The parameters
-    themselves are whole on every rank after every step.)  No-op when nothing is stale."""
+    """COLLECTIVE (every rank calls it): after sharded optimiser steps, gather the flat optimiser state (both Adam moments, the
+    one SGD momentum buffer: ``optimizer.state_buffers()``) from their owners so that ``optimizer.state_dict()`` -- the
+    'optimizer' entry of a checkpoint -- can be taken on any rank.  (The parameters themselves are whole on every rank after
+    every step.)  No-op when nothing is stale."""
     plan = getattr(getattr(model, "grad_sync", None), "plan", None)
     if plan is None or not getattr(optimizer, "_moments_stale", False):
         return
     W, r = world_size(), rank()
-    for buf in (optimizer.m, optimizer.v):
+    buffers = optimizer.state_buffers() if hasattr(optimizer, "state_buffers") else (optimizer.m, optimizer.v)
+    for buf in buffers:
         for lo, hi in plan.pieces:
             _all_gather_in_place(buf[lo:hi], W, r)
     optimizer._moments_stale = False

@@ -1,5 +1,5 @@
-"""The optimiser side of the step: fused clip_grad_norm_(.,1) + Adam over the model's flat
-buffers (reference engine.py:87-95, build_optimizer engine.py:129-151) -- two HIP launches per step, no host
+"""The optimiser side of the step: fused clip_grad_norm_(.,1) + Adam, or + SGD with momentum, over the
+model's flat buffers (reference engine.py:87-95, build_optimizer engine.py:129-151) -- two HIP launches per step, no host
 synchronisation -- and the learning-rate schedules of utils.py:310-416 / build_lr_scheduler engine.py:154-176
 (host arithmetic: one float per step)."""
 from __future__ import annotations
@@ -15,7 +15,40 @@ import torch
 from ._lib import check, lib, ptr, stream
 
 
-class FusedAdam(torch.optim.Optimizer):
+class _FusedFlatOptimizer(torch.optim.Optimizer):
+    """What the fused optimisers share: one param group over the model's flat buffers, the gradient zero-fill and the
+    device scalar of the gradient norm.  A subclass provides ``_state()`` (allocate the flat state buffers and ``sumsq``)."""
+
+    @property
+    def lr(self):
+        return self.param_groups[0]["lr"]
+
+    @property
+    def weight_decay(self):
+        return self.param_groups[0]["weight_decay"]
+
+    def zero_grad(self, set_to_none: bool = False):
+        self._state()
+        self.model._flat_grad.zero_()
+        self.model._attach_grads_fast()
+
+    def zero_grad_first_touch(self):
+        """``zero_grad`` for a caller that owns the whole step (engine.train_step): the block weight gradients are left
+        to be overwritten by the step's first backward pass (model.zero_grad_first_touch)."""
+        self._state()
+        self.model.zero_grad_first_touch()
+
+    def grad_norm(self) -> torch.Tensor:
+        """Device scalar: total L2 norm of the gradients as of the last ``step``."""
+        return self.sumsq.sqrt()
+
+    def _offset_of(self):
+        """Flat offset of every parameter of the group, in group order."""
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        return [self.model._offsets[names[id(p)]] for p in self.param_groups[0]["params"]]
+
+
+class FusedAdam(_FusedFlatOptimizer):
     """``torch.optim.Adam(params, lr, weight_decay)`` semantics (L2 decay added to the gradient)
     preceded by the global-norm clip of ``clip_grad_norm_(params, max_norm)``.  ``max_norm=None``
     disables clipping.
@@ -40,11 +73,8 @@ class FusedAdam(torch.optim.Optimizer):
         super().__init__([p for p in model.parameters() if p.requires_grad],
                          dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
 
-    # kept as attributes of the first (only) group so that schedulers and user code see one source of truth
-    @property
-    def lr(self):
-        return self.param_groups[0]["lr"]
-
+    # kept as attributes of the first (only) group so that schedulers and user code see one source of truth (lr and
+    # weight_decay: the base class)
     @property
     def betas(self):
         return self.param_groups[0]["betas"]
@@ -52,10 +82,6 @@ class FusedAdam(torch.optim.Optimizer):
     @property
     def eps(self):
         return self.param_groups[0]["eps"]
-
-    @property
-    def weight_decay(self):
-        return self.param_groups[0]["weight_decay"]
 
     def _state(self):
         m = self.model
@@ -65,20 +91,10 @@ class FusedAdam(torch.optim.Optimizer):
             self.v = torch.zeros_like(m._flat)
             self.sumsq = torch.zeros(1, dtype=torch.float32, device=m._flat.device)
 
-    def zero_grad(self, set_to_none: bool = False):
+    def state_buffers(self):
+        """The flat optimiser state tensors (what ``distributed.consolidate`` gathers after sharded steps)."""
         self._state()
-        self.model._flat_grad.zero_()
-        self.model._attach_grads_fast()
-
-    def zero_grad_first_touch(self):
-        """``zero_grad`` for a caller that owns the whole step (engine.train_step): the block weight gradients are left
-        to be overwritten by the step's first backward pass (model.zero_grad_first_touch)."""
-        self._state()
-        self.model.zero_grad_first_touch()
-
-    def grad_norm(self) -> torch.Tensor:
-        """Device scalar: total L2 norm of the gradients as of the last ``step``."""
-        return self.sumsq.sqrt()
+        return (self.m, self.v)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -185,6 +201,159 @@ class FusedAdam(torch.optim.Optimizer):
         self.step_count = steps.pop() if steps else 0
 
 
+class FusedSGD(_FusedFlatOptimizer):
+    """``torch.optim.SGD(params, lr, momentum, dampening, weight_decay, nesterov)`` semantics preceded by the global-norm clip
+    of ``clip_grad_norm_(params, max_norm)`` (engine.py:89-90 with engine.py:136-140's optimiser).  ``max_norm=None`` disables
+    clipping.
+
+    A real ``torch.optim.Optimizer`` like ``FusedAdam``: one param group that carries torch SGD's keys, ``state_dict()`` /
+    ``load_state_dict()`` in ``torch.optim.SGD``'s format (per-parameter ``momentum_buffer``; empty before the first step and
+    with momentum 0).  The momentum lives in ONE flat buffer next to the flat parameters -- none at all with momentum 0 -- and,
+    as in torch, "first step" means "no buffer yet", not a counter: the first step copies the decayed gradient into it whatever
+    the dampening is."""
+
+    def __init__(self, model, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
+                 nesterov: bool = False, max_norm=1.0):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        frozen = [n for n, p in model.named_parameters() if not p.requires_grad]
+        if frozen:
+            raise NotImplementedError("FusedSGD updates the whole flat parameter buffer; frozen parameters "
+                                      f"({frozen[:3]}...) need torch.optim.SGD over the trainable ones instead")
+        self.model = model
+        self.max_norm = max_norm
+        self.step_count = 0                # steps taken by THIS object (telemetry cadence); the arithmetic never reads it
+        self.sat_poll_every = int(os.environ.get("CE_SAT_POLL_EVERY", "16"))     # 0 = never
+        self.buf = self.sumsq = None
+        self._has_buf = False              # a momentum buffer exists: the next step is not the first
+        super().__init__([p for p in model.parameters() if p.requires_grad],
+                         dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                              maximize=False, foreach=None, differentiable=False, fused=None))
+
+    @property
+    def momentum(self):
+        return self.param_groups[0]["momentum"]
+
+    def _state(self):
+        m = self.model
+        m._ready()
+        flat = m._flat
+        if self.sumsq is None or self.sumsq.device != flat.device:
+            self.sumsq = torch.zeros(1, dtype=torch.float32, device=flat.device)
+        if self.momentum != 0 and (self.buf is None or self.buf.numel() != flat.numel() or self.buf.device != flat.device):
+            self.buf = torch.zeros_like(flat)
+            self._has_buf = False
+
+    def state_buffers(self):
+        """``(buf,)``, or ``()`` when there is no momentum."""
+        self._state()
+        return (self.buf,) if self.momentum != 0 else ()
+
+    def _poll(self):
+        # fp16 streams: as FusedAdam.step, but on every exit of step(), the sharded one included
+        m = self.model
+        if self.sat_poll_every and self.step_count % self.sat_poll_every == 0 and hasattr(m, "poll_stream16_saturation"):
+            m.poll_stream16_saturation()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        """clip + SGD: sum of squares of the whole gradient buffer, then the update with the clip coefficient applied on the fly --
+        by default in tiles that also leave the blocks' W^T operand copies behind (``ce_sgd_step_tiles``)."""
+        if closure is not None:
+            raise RuntimeError("FusedSGD.step takes no closure")
+        self._state()
+        m = self.model
+        m._settle_first_touch()         # a tower that saw no backward since zero_grad_first_touch
+        m.wait_transposes()             # the update rewrites the bf16 mirror an asynchronous W^T rebuild may still be reading
+        n = m._flat.numel()
+        s = stream()
+        self.step_count += 1
+        group = self.param_groups[0]
+        if group.get("maximize"):
+            raise NotImplementedError("FusedSGD: maximize is not supported")
+        lr, mu, damp, wd = (float(group[k]) for k in ("lr", "momentum", "dampening", "weight_decay"))
+        nesterov, first = int(bool(group["nesterov"])), int(not self._has_buf)
+        buf = self.buf if mu != 0 else None
+        sumsq = None
+        from . import distributed as D
+        plan = getattr(getattr(m, "grad_sync", None), "plan", None)
+        sharded = plan is not None and D.active()
+        if self.max_norm is not None:
+            sumsq = self.sumsq
+            if not sharded:
+                self.sumsq.zero_()
+                check(lib().ce_sumsq(ptr(m._flat_grad), c_long(n), ptr(self.sumsq), s), "ce_sumsq")
+        tail = (ptr(sumsq), c_float(self.max_norm or 0.0), c_float(lr), c_float(mu), c_float(damp), c_float(wd), c_int(nesterov),
+                c_int(first))
+
+        def sgd(lo, hi, st):
+            check(lib().ce_sgd_step(ptr(m._flat[lo:hi]), ptr(m._flat_grad[lo:hi]), ptr(buf[lo:hi]) if buf is not None else None,
+                                    ptr(m._flat16[lo:hi]), c_long(hi - lo), *tail, st), "ce_sgd_step")
+
+        if sharded:
+            # as FusedAdam: this rank updates its shard of every reduce-scattered piece (+ the replicated head range), the masters are
+            # all-gathered in place and the bf16 mirror is re-cast by the next refresh_operands; the momentum stays sharded
+            D.sharded_update(plan, m._flat, sumsq,
+                             lambda lo, hi: check(lib().ce_sumsq(ptr(m._flat_grad[lo:hi]), c_long(hi - lo), ptr(self.sumsq), s), "ce_sumsq"),
+                             lambda lo, hi: sgd(lo, hi, s))
+            self._moments_stale = buf is not None
+            m.mark_operands_stale(mirror_fresh=False)
+        elif getattr(m, "_adam_tiles_ok", False) and os.environ.get("CE_ADAM_TILES", "1") != "0":
+            tj, tn_, tt = m._tjobs_bwd
+            seg = m._adam_segment_table()
+            check(lib().ce_sgd_step_tiles(ptr(m._flat), ptr(m._flat_grad), ptr(buf), ptr(m._flat16), ptr(tj), c_int(tn_), c_int(tt),
+                                          ptr(seg), c_int(seg.shape[0]), *tail, s), "ce_sgd_step_tiles")
+            m.mark_operands_stale(mirror_fresh=True, wt_fresh=True)
+        else:
+            sgd(0, n, s)
+            m.mark_operands_stale(mirror_fresh=True)
+        self._has_buf = buf is not None
+        self._poll()
+
+    # ---- torch.optim.SGD-format state (checkpoint interop) ----
+    def state_dict(self):
+        self._state()
+        if getattr(self, "_moments_stale", False):
+            raise RuntimeError("the momentum buffer is sharded over the ranks (sharded optimiser step): call "
+                               "clip_event_amd.distributed.consolidate(model, optimizer) on EVERY rank before state_dict()")
+        state = {}
+        params = self.param_groups[0]["params"]
+        if self._has_buf and self.momentum != 0:
+            for i, (p, o) in enumerate(zip(params, self._offset_of())):
+                state[i] = {"momentum_buffer": self.buf[o:o + p.numel()].view(p.shape).clone()}
+        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
+        group["params"] = list(range(len(params)))
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        self._moments_stale = False          # (every rank loads the same tensors)
+        params = self.param_groups[0]["params"]
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(params):
+            raise ValueError("optimizer state does not match: expected one group of %d parameters" % len(params))
+        bufs = {int(k): st["momentum_buffer"] for k, st in sd["state"].items() if st.get("momentum_buffer") is not None}
+        if bufs and len(bufs) != len(params):
+            raise ValueError("only %d of %d parameters carry a momentum_buffer; the fused kernel keeps one buffer and one "
+                             "first-step flag for all of them" % (len(bufs), len(params)))
+        for k, v in groups[0].items():
+            if k != "params":
+                self.param_groups[0][k] = v
+        self._state()
+        self._has_buf = False
+        if bufs and self.momentum != 0:
+            with torch.no_grad():
+                self.buf.zero_()
+                for i, (p, o) in enumerate(zip(params, self._offset_of())):
+                    self.buf[o:o + p.numel()].copy_(bufs[i].reshape(-1))
+            self._has_buf = True
+
+
 def _warmup_factor_at(method: str, it: int, warmup_iters: int, warmup_factor: float) -> float:
     """utils.py:393-416: 1 after the warm-up; before it a constant, or a line from warmup_factor to 1."""
     if it >= warmup_iters:
@@ -230,9 +399,12 @@ class WarmupCosineLR(torch.optim.lr_scheduler._LRScheduler):
 
 
 def build_optimizer(cfg: dict, model, fused: bool = True):
-    """engine.py:129-151 (``cfg['optimizer']`` in {'sgd','adam'}); 'adam' returns the fused step, which also
-    performs engine.py:89's clip_grad_norm_(.,1)."""
+    """engine.py:129-151 (``cfg['optimizer']`` in {'sgd','adam'}); with ``fused`` both return the fused step, which also
+    performs engine.py:89's clip_grad_norm_(.,1).  A model with frozen parameters gets the stock SGD over the trainable ones
+    (the fused step updates the whole flat buffer)."""
     if cfg["optimizer"] == "sgd":
+        if fused and all(p.requires_grad for p in model.parameters()):
+            return FusedSGD(model, lr=cfg["lr"], momentum=cfg["momentum"], weight_decay=cfg["weight_decay"], max_norm=1.0)
         return torch.optim.SGD([p for p in model.parameters() if p.requires_grad], lr=cfg["lr"],
                                momentum=cfg["momentum"], weight_decay=cfg["weight_decay"])
     if cfg["optimizer"] == "adam":

@@ -321,6 +321,18 @@ int ce_multi_transpose_bf16(const ce_transpose_job* jobs_device, int njobs, int 
 int ce_adam_step_tiles(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
                        int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
                        float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
+/* clip_grad_norm_(.,max_norm) + torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov).step(), engine.py:89-90 with
+ * engine.py:136-140's optimiser: g = g * coef (coef as ce_adam_step: min(1, max_norm / (sqrt(*sumsq) + 1e-6)), 1 when sumsq is NULL),
+ * g += weight_decay * p, buf = first_step ? g : momentum * buf + (1 - dampening) * g, p -= lr * (nesterov ? g + momentum * buf : buf);
+ * with momentum == 0 the update is g, and buf may be NULL (it is neither read nor written).  first_step: no momentum buffer exists
+ * yet (torch keeps no step counter): buf is overwritten.  p_bf16 as for ce_adam_step.  -EINVAL for n <= 0, momentum < 0, nesterov
+ * with momentum <= 0 or dampening != 0 (torch's rule), buf == NULL with momentum > 0. */
+int ce_sgd_step(float* p, const float* g, float* buf, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+                float momentum, float dampening, float weight_decay, int nesterov, int first_step, void* stream);
+/* the same update, element for element, in ce_adam_step_tiles' form (jobs / segments as there): also writes the W^T copies */
+int ce_sgd_step_tiles(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                      int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
+                      float momentum, float dampening, float weight_decay, int nesterov, int first_step, void* stream);
 
 /* ---- transformer tower runner (tower.cpp): the 12x ResidualAttentionBlock loop of
  * Transformer.forward (model_clip.py:171-211) and its backward, all launches issued from C++ ---- */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the HBM-bound kernels at the step's shapes with COLD operands: every call works on the next of
 NSETS buffer sets (together larger than the 256 MiB Infinity Cache), as in the step, where a kernel's inputs were written
-tens of kernels earlier.  Prints us per call and GB/s on the algorithmic bytes.   python tools/bench_hbm.py [ln adam attn]"""
+tens of kernels earlier.  Prints us per call and GB/s on the algorithmic bytes.   python tools/bench_hbm.py [ln adam sgd attn]"""
 import os
 import sys
 from ctypes import c_float, c_int, c_long
@@ -86,6 +86,72 @@ def bench_adam():
     print(f"zero    n={n}: {t * 1e6:7.1f} us  {n * 4 / t / 1e9:7.0f} GB/s", flush=True)
 
 
+_TILED = {}
+
+
+def _tiled_model():
+    """The ViT-B/32 model's own flat buffers, transpose-job table and segment table (the layout the step's tiled update
+    runs over) with a gradient and both optimisers' state buffers."""
+    if not _TILED:
+        from clip_event_amd import synthetic as S
+        from clip_event_amd.optim import FusedAdam
+        m = S.synthetic_model("vit_b32", seed=0).to(DEV)
+        opt = FusedAdam(m, lr=1e-6)
+        opt.zero_grad()
+        assert m._adam_tiles_ok
+        m._flat_grad.copy_(torch.randn_like(m._flat_grad) * 1e-3)
+        _TILED.update(m=m, a=opt.m, b=opt.v, ss=torch.zeros(1, device=DEV), seg=m._adam_segment_table())
+    return _TILED
+
+
+def bench_adam_tiles():
+    t = _tiled_model()
+    m, seg, (tj, tn_, tt) = t["m"], t["seg"], t["m"]._tjobs_bwd
+    n = sum(p.numel() for p in m.parameters())
+
+    def adam():
+        check(lib().ce_adam_step_tiles(ptr(m._flat), ptr(m._flat_grad), ptr(t["a"]), ptr(t["b"]), ptr(m._flat16), ptr(tj), c_int(tn_),
+                                       c_int(tt), ptr(seg), c_int(seg.shape[0]), ptr(t["ss"]), c_float(1.0), c_float(1e-6), c_float(0.9),
+                                       c_float(0.999), c_float(1e-8), c_float(0.0), c_int(3), stream()), "adam tiles")
+
+    dt = timeit([adam], iters=10, warm=2)
+    print(f"adam tiles n={n}: {dt * 1e6:7.1f} us  {n * 32 / dt / 1e9:7.0f} GB/s   (30 B + 2 B of W^T per parameter)", flush=True)
+    return dt
+
+
+def bench_sgd():
+    """clip + SGD with momentum 0.9: the flat kernel on buffers of its own (12 B read + 10 B written per parameter) and the tiled
+    form over the model's layout (+ 2 B of W^T), beside the tiled Adam update measured in the same run."""
+    n = 151_277_312
+    p = torch.randn(n, device=DEV) * 0.02
+    g = torch.randn(n, device=DEV) * 1e-3
+    buf = torch.zeros(n, device=DEV)
+    p16 = torch.empty(n, device=DEV, dtype=torch.bfloat16)
+    ss = torch.zeros(1, device=DEV)
+
+    def sgd():
+        check(lib().ce_sgd_step(ptr(p), ptr(g), ptr(buf), ptr(p16), c_long(n), ptr(ss), c_float(1.0), c_float(1e-6), c_float(0.9),
+                                c_float(0.0), c_float(0.0), c_int(0), c_int(0), stream()), "sgd")
+
+    dt = timeit([sgd], iters=10, warm=2)
+    print(f"sgd     n={n}: {dt * 1e6:7.1f} us  {n * 22 / dt / 1e9:7.0f} GB/s", flush=True)
+    del p, g, buf, p16
+    t = _tiled_model()
+    m, seg, (tj, tn_, tt) = t["m"], t["seg"], t["m"]._tjobs_bwd
+    n = sum(q.numel() for q in m.parameters())
+
+    def sgd_tiles():
+        check(lib().ce_sgd_step_tiles(ptr(m._flat), ptr(m._flat_grad), ptr(t["a"]), ptr(m._flat16), ptr(tj), c_int(tn_), c_int(tt),
+                                      ptr(seg), c_int(seg.shape[0]), ptr(t["ss"]), c_float(1.0), c_float(1e-6), c_float(0.9), c_float(0.0),
+                                      c_float(0.0), c_int(0), c_int(0), stream()), "sgd tiles")
+
+    for _ in range(2):                      # the two tiled updates in alternation: same box, same minute
+        t_adam = bench_adam_tiles()
+        dt = timeit([sgd_tiles], iters=10, warm=2)
+        print(f"sgd tiles  n={n}: {dt * 1e6:7.1f} us  {n * 24 / dt / 1e9:7.0f} GB/s   ({dt / t_adam:.2f} of the tiled Adam update; bytes: 24 / 32 = 0.75)",
+              flush=True)
+
+
 def bench_attn():
     for name, B, Ltok, H, causal in (("image", 256, 50, 12, False), ("text", 256, 77, 8, True)):
         sets = []
@@ -104,10 +170,12 @@ def bench_attn():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["ln", "adam", "attn"]
+    which = sys.argv[1:] or ["ln", "adam", "sgd", "attn"]
     if "ln" in which:
         bench_ln()
     if "adam" in which:
         bench_adam()
+    if "sgd" in which:
+        bench_sgd()
     if "attn" in which:
         bench_attn()

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The reference's training loop (train.py:101-250 / engine.py:24-102) on the drop-in API, end to end on synthetic
 data: decoded uint8 images -> on-device preprocessing -> CLIP forward (hard-negative descriptions, per-batch labels as
-dataset_voa.py builds them) -> CriterionContrastive -> fused clip + Adam -> warm-up cosine schedule -> checkpoint in
+dataset_voa.py builds them) -> CriterionContrastive -> fused clip + Adam (``--optimizer sgd``: fused clip + SGD with momentum,
+the reference's other optimiser) -> warm-up cosine schedule -> checkpoint in
 the reference's layout -> resume from it.  A smoke run of every host-side component together, not a benchmark.
 
 ``--micro-batch N`` runs every step in chunks of N images (engine.train_step(micro_batch=N): the step for batches whose
@@ -38,9 +39,12 @@ def batch(rng, B, K, dev):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--micro-batch", type=int, default=None, metavar="N", help="images per chunk of a step (default: unchunked)")
-    mb = ap.parse_args().micro_batch
+    ap.add_argument("--optimizer", choices=("adam", "sgd"), default="adam", help="cfg['optimizer'] of engine.py:129-151")
+    args = ap.parse_args()
+    mb = args.micro_batch
     dev = torch.device("cuda", 0)
-    cfg = {"optimizer": "adam", "lr": 1e-5, "weight_decay": 0.0, "momentum": 0.9, "lr_scheduler": "warmup",
+    # (SGD's clipped step is lr x a unit-norm gradient: it needs a far larger lr than Adam's per-element lr to move the loss)
+    cfg = {"optimizer": args.optimizer, "lr": 1e-5 if args.optimizer == "adam" else 0.05, "weight_decay": 0.0, "momentum": 0.9, "lr_scheduler": "warmup",
            "max_epoch": 40, "warmup_epoch": 4, "lr_steps": [], "lr_gamma": 0.1, "task": "clipevent"}
     B, K = 16, 3
     rng = np.random.default_rng(0)
