@@ -37,6 +37,31 @@ class TransposeJob(ctypes.Structure):
                 ("tile_start", ctypes.c_int), ("pad_", ctypes.c_int)]
 
 
+class NTPlan(ctypes.Structure):
+    """``ce_nt_plan`` of include/clip_event_hip.h; ``kernel`` indexes ``NT_KERNELS``."""
+    _fields_ = [(name, ctypes.c_int) for name in ("kernel", "tm", "ts", "tall_panels", "tiles_m", "tiles_n", "tile_chunk",
+                                                   "workgroups", "block", "lds_bytes", "wants_tile_queue", "taken")]
+
+
+NT_KERNELS = ("NT128", "NT256x2", "NT256x4", "NT32", "NT160_RING", "LW", "PERSIST", "SKINNY")
+
+
+def gemm_nt_plan(M: int, N: int, K: int, epilogue: int, fp8: bool = False, *, lda=None, ldb=None, ldo=None, ldo2=None,
+                 ldaux=None, ldr=None) -> NTPlan:
+    """The launch ``ce_gemm_nt`` (``fp8``: the loader-wave path of ``ce_gemm_nt_fp8``) would make under the process's current
+    knobs (``ce_gemm_nt_plan``: host arithmetic, no GPU).  Leading dimensions default to those of contiguous operands; an
+    operand the epilogue does not have has 0."""
+    c_long = ctypes.c_long
+    has_out2 = epilogue in (EPI_BIAS_GELU, EPI_GELUGRAD_BF16)
+    has_resid = epilogue in (EPI_BIAS_RESID_F32, EPI_BIAS_RESID_F16)
+    lds = [K if lda is None else lda, K if ldb is None else ldb, N if ldo is None else ldo,
+           (N if has_out2 else 0) if ldo2 is None else ldo2, (N if epilogue == EPI_GELUGRAD_BF16 else 0) if ldaux is None else ldaux,
+           (N if has_resid else 0) if ldr is None else ldr]
+    plan = NTPlan()
+    check(lib().ce_gemm_nt_plan(M, N, K, epilogue, int(fp8), *[c_long(v) for v in lds], ctypes.byref(plan)), "ce_gemm_nt_plan")
+    return plan
+
+
 def lib() -> ctypes.CDLL:
     """Load the shared library once; fail loudly when it has not been built."""
     global _lib

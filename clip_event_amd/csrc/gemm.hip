@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "nt_plan.hpp"
 #include "../../include/clip_event_hip.h"
 
 #ifndef CE_DIAG_TN3
@@ -1933,31 +1934,32 @@ __global__ void probe_tr16_kernel(const uint16_t* image, int n_elems, const int*
     out[threadIdx.x] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + byte_off[threadIdx.x]));
 }
 
-int nt_variant() {   // CE_GEMM_NT=128|256 forces a tile; default: pick per shape
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("CE_GEMM_NT");
-        v = e ? atoi(e) : 0;
-    }
-    return v;
-}
+// ------------------------------------------------------------------------------------------
+// NT launch: nt_plan (nt_plan.cpp) decides, dispatch launches what it decided
+// ------------------------------------------------------------------------------------------
+static_assert(NT_PLAN_LDS[NT_NT128] == NT_LDS_BYTES && NT_PLAN_LDS[NT_NT256x2] == N2H_LDS_BYTES && NT_PLAN_LDS[NT_NT256x4] == N2_LDS_BYTES &&
+              NT_PLAN_LDS[NT_NT32] == N3_LDS_BYTES && NT_PLAN_LDS[NT_NT160_RING] == N4_LDS_BYTES && NT_PLAN_LDS[NT_LW] == N4_LDS_BYTES &&
+              NT_PLAN_LDS[NT_PERSIST] == N4P_LDS_BYTES && NT_PLAN_LDS[NT_SKINNY] == SK_LDS_BYTES &&
+              NT_PLAN_BLOCK[NT_LW] == 64 * (8 + N4_LOADERS), "nt_plan.hpp is out of step with the kernels");
 
-int g_last_tall = 0, g_last_ts = 0;   // two-height plan of the latest persistent launch (ce_gemm_nt_last_plan)
-int g_force_chunk = -2;      // ce_gemm_nt_tune(1000 + ...): walk of the persistent kernel (-2: CE_NT_CHUNK / default)
-int g_force_tm = -1;
-int force_tm() {   // CE_GEMM_TM / ce_gemm_nt_tune(): 3..8 = tile height (x32 rows) of the 256-column kernel, 32 = the
-                   // 160x256x32 two-workgroup kernel, 104 = 160x128 four-wave tile, 160 = three-stage ring; 0 = auto
-    if (g_force_tm < 0) {
-        const char* e = getenv("CE_GEMM_TM");
-        g_force_tm = e ? atoi(e) : 0;
-    }
-    return g_force_tm;
+// The process's knobs: what ce_gemm_nt_tune / ce_gemm_set_cu_budget / ce_gemm_set_dynamic_tiles set, over the environment's
+// values, read once when the library is loaded.
+int env_int(const char* name, int otherwise) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : otherwise;
 }
+NTKnobs knobs_from_env() {
+    NTKnobs k;
+    k.cus = env_int("CE_GEMM_CUS", 256);
+    k.dynamic = env_int("CE_NT_DYNAMIC", 0);
+    k.env_chunk = env_int("CE_NT_CHUNK", 0);
+    k.env_pgrid = env_int("CE_NT_PGRID", 0);
+    k.env_mixed = env_int("CE_NT_MIXED", 1);
+    return k;
+}
+NTKnobs g_knobs = knobs_from_env();
+NTPlan g_last_plan;      // of the latest launch (ce_gemm_nt_last_plan)
 
-// Tile-variant cost model, fitted to tools/tune_nt.py sweeps (M 8k..20k, both towers' N/K; unit = 0.137 us at
-// K = 512, scales with K): one round of 32*TM-row tiles on the 256 CUs costs 28 + 10*TM (the K loop is
-// LDS-read bound: a fixed share for the 256-column B fragments plus TM A fragments per k-step); the
-// 160x256x32 kernel keeps two workgroups per CU: a co-resident pair costs 146, a lone one 78.
 // Tile queues of the persistent kernel's DYNAMIC tile list (NTArgs.tile_queue): one zero-initialised counter per launch, taken from a
 // ring per stream; the ring is re-zeroed on its stream when it wraps, behind every launch that used it.  CE_NT_DYNAMIC = 1 (or
 // ce_gemm_set_dynamic_tiles) turns the dynamic list on for persistent launches with >= 3 K iterations on the launch-wide walk.
@@ -1965,7 +1967,6 @@ struct TileQueueRing { unsigned int* dev = nullptr; int next = 0; };
 constexpr int TQ_RING = 1024;
 std::mutex g_tq_mu;
 std::map<hipStream_t, TileQueueRing> g_tq;
-int g_dynamic = getenv("CE_NT_DYNAMIC") ? atoi(getenv("CE_NT_DYNAMIC")) : 0;
 unsigned int* next_tile_queue(hipStream_t s) {
     std::lock_guard<std::mutex> lk(g_tq_mu);
     TileQueueRing& r = g_tq[s];
@@ -1980,386 +1981,85 @@ unsigned int* next_tile_queue(hipStream_t s) {
     return r.dev + r.next++;
 }
 
-// CU budget of the NT launch policies (ce_gemm_set_cu_budget / CE_GEMM_CUS, default 256 = the whole chip).  Every NT kernel here
-// puts ONE 156 KiB workgroup on a CU and sizes its grid to fill the chip exactly once (one-round launches: 226-240 tiles;
-// persistent launches: 256 workgroups), so a single CU held by another stream's kernel -- an RCCL channel during a gradient
-// all-reduce -- leaves one workgroup without a home until a whole tile list has finished: measured with a 1-CU "hog"
-// (ce_cu_hog) every such launch takes 1.6-1.75x as long.  A budget below 256 sizes the one-round and the persistent
-// grids for that many CUs, so that the rest may be taken.
-int g_cus = getenv("CE_GEMM_CUS") ? atoi(getenv("CE_GEMM_CUS")) : 256;
-// epilogues for which the persistent kernel is also built with two tile heights (launch_nt)
-constexpr bool nt_two_heights(int epi) {
-    return epi == CE_EPI_BIAS_GELU || epi == CE_EPI_GELUGRAD_BF16 || epi == CE_EPI_BIAS_BF16 || epi == CE_EPI_BF16 ||
-           epi == CE_EPI_BIAS_RESID_F16 || epi == CE_EPI_BIAS_RESID_F32 || epi == CE_EPI_BIAS_QGELU_BF16;
-}
-inline int cu_budget() { return g_cus >= 32 && g_cus <= 256 ? g_cus : 256; }
-inline long nt256_cost(long tiles, int tm) { return ((tiles + cu_budget() - 1) / cu_budget()) * (28 + 10 * tm); }
-// Two tile heights for one persistent launch (gemm_nt160p_kernel<EPI, TM, F8, TS>): n_tall row panels of 32 TM rows, the rest in panels
-// of 32 TS, chosen so that the longest per-workgroup list (tall tiles first, round-robin over G workgroups) is shortest under the
-// launch policy's cost model (32 tm + 48 per tile).  `uniform` = the best single height's cost; true when a split beats it by >=
-// min_gain per cent.
-inline bool two_height_plan(long M, long tn, long G, int TM, long uniform, int min_gain, long& b_tall, long& b_short, int& b_ts) {
-    const long ct = 32 * TM + 48;
-    auto span = [&](long n_tall, int ts, long n_short) {      // cost of the longest list
-        const long T = n_tall * tn, S = n_short * tn, q = T / G, r = T % G;
-        auto shorts = [&](long d) { return d < S ? (S - 1 - d) / G + 1 : 0; };   // short tiles of the workgroup d places behind r
-        const long cs = 32 * ts + 48;
-        long worst = q * ct + shorts(0) * cs;                  // workgroup r: q tall tiles, the most short ones
-        if (r > 0) worst = std::max(worst, (q + 1) * ct + shorts(G - r) * cs);   // workgroup 0: q + 1 tall
-        return worst;
-    };
-    long best = uniform;
-    b_tall = -1; b_short = 0; b_ts = 0;
-    for (int ts = TM - 1; ts >= 1; --ts)
-        for (long n_tall = M / (32 * TM); n_tall >= 1; --n_tall) {
-            const long rest = M - n_tall * 32 * TM;
-            if (rest <= 0) continue;
-            const long n_short = (rest + 32 * ts - 1) / (32 * ts);
-            const long c = span(n_tall, ts, n_short);
-            if (c < best || (c == best && b_tall < 0)) { best = c; b_tall = n_tall; b_short = n_short; b_ts = ts; }
-        }
-    return b_tall > 0 && best * 100 <= uniform * (100 - min_gain);
-}
-inline long nt32_cost(long tiles) {
-    const long n = (tiles + 255) / 256;
-    return (n / 2) * 146 + (n % 2) * 78;
-}
-
-template <int EPI, int TM>
-void launch_nt128(NTArgs& a, hipStream_t stream) {      // (32 TM) x 128 tile, 4 waves, two workgroups per CU
+// One instantiation: raise its dynamic LDS limit once, then launch (forward runs on the caller's thread, backward on autograd's).
+template <auto Kernel>
+void launch_kernel(const NTPlan& p, const NTArgs& a, hipStream_t stream) {
     static std::once_flag attr;
-    std::call_once(attr, [] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt256_kernel<EPI, TM, 2>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, N2H_LDS_BYTES);
+    std::call_once(attr, [&] {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds_bytes);
     });
-    a.tiles_m = ce_div_up(a.M, 32 * TM);
-    hipLaunchKernelGGL((gemm_nt256_kernel<EPI, TM, 2>), dim3(a.tiles_m * a.tiles_n), dim3(256), N2H_LDS_BYTES, stream, a);
+    hipLaunchKernelGGL(Kernel, dim3(p.workgroups), dim3(p.block), p.lds_bytes, stream, a);
 }
 
-template <int EPI, int TM>
-void launch_nt256(NTArgs& a, hipStream_t stream) {
-    static std::once_flag attr;       // forward runs on the caller's thread, backward on autograd's
-    std::call_once(attr, [] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt256_kernel<EPI, TM, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, N2_LDS_BYTES);
-    });
-    a.tiles_m = ce_div_up(a.M, 32 * TM);
-    hipLaunchKernelGGL((gemm_nt256_kernel<EPI, TM, 4>), dim3(a.tiles_m * a.tiles_n), dim3(512), N2_LDS_BYTES, stream, a);
+// (kernel, tm, ts) -> instantiation: the one place that names the NT kernels for launch.  The e4m3 operand form (F8) exists for
+// the two loader-wave families only (tile heights 3..5 one-round, 3..4 persistent: 160-row tiles spill there); the two-height
+// form for the epilogues of nt_two_heights.  The cases stand in the order in which the code object has always held the kernels
+// (the compiler emits them as they are named here).  False: no such instantiation.
+template <int EPI, int F8>
+bool dispatch(const NTPlan& p, const NTArgs& a, hipStream_t s) {
+#define CE_NT_CASE_IF(COND, KERNEL, TM, TS, ...) \
+    case key(KERNEL, TM, TS): if constexpr (COND) { launch_kernel<__VA_ARGS__>(p, a, s); return true; } break
+#define CE_NT_CASE(KERNEL, TM, ...) CE_NT_CASE_IF(true, KERNEL, TM, 0, __VA_ARGS__)
+    constexpr auto key = [](int kernel, int tm, int ts) { return 128 * kernel + 8 * tm + ts; };
+    constexpr bool two = nt_two_heights(EPI);
+    if constexpr (F8) {
+        switch (key(p.kernel, p.tm, p.ts)) {
+            CE_NT_CASE(NT_LW, 5, gemm_nt160lw_kernel<EPI, 5, 1>);
+            CE_NT_CASE(NT_LW, 4, gemm_nt160lw_kernel<EPI, 4, 1>);
+            CE_NT_CASE(NT_LW, 3, gemm_nt160lw_kernel<EPI, 3, 1>);
+            CE_NT_CASE(NT_PERSIST, 4, gemm_nt160p_kernel<EPI, 4, 1>);
+            CE_NT_CASE_IF(two, NT_PERSIST, 4, 1, gemm_nt160p_kernel<EPI, 4, 1, 1>);
+            CE_NT_CASE_IF(two, NT_PERSIST, 4, 2, gemm_nt160p_kernel<EPI, 4, 1, 2>);
+            CE_NT_CASE_IF(two, NT_PERSIST, 4, 3, gemm_nt160p_kernel<EPI, 4, 1, 3>);
+            CE_NT_CASE(NT_PERSIST, 3, gemm_nt160p_kernel<EPI, 3, 1>);
+        }
+    } else {
+        switch (key(p.kernel, p.tm, p.ts)) {
+            CE_NT_CASE(NT_NT128, 4, gemm_nt_kernel<EPI>);
+            CE_NT_CASE(NT_NT256x2, 5, gemm_nt256_kernel<EPI, 5, 2>);
+            CE_NT_CASE(NT_NT32, 5, gemm_nt32_kernel<EPI>);
+            CE_NT_CASE(NT_NT160_RING, 5, gemm_nt160_kernel<EPI>);
+            CE_NT_CASE(NT_LW, 5, gemm_nt160lw_kernel<EPI, 5>);
+            CE_NT_CASE(NT_LW, 4, gemm_nt160lw_kernel<EPI, 4>);
+            CE_NT_CASE(NT_LW, 3, gemm_nt160lw_kernel<EPI, 3>);
+            CE_NT_CASE(NT_PERSIST, 5, gemm_nt160p_kernel<EPI, 5>);
+            CE_NT_CASE(NT_PERSIST, 4, gemm_nt160p_kernel<EPI, 4>);
+            CE_NT_CASE(NT_PERSIST, 3, gemm_nt160p_kernel<EPI, 3>);
+            CE_NT_CASE_IF(two, NT_PERSIST, 5, 1, gemm_nt160p_kernel<EPI, 5, 0, 1>);
+            CE_NT_CASE_IF(two, NT_PERSIST, 5, 2, gemm_nt160p_kernel<EPI, 5, 0, 2>);
+            CE_NT_CASE_IF(two, NT_PERSIST, 5, 3, gemm_nt160p_kernel<EPI, 5, 0, 3>);
+            CE_NT_CASE_IF(two, NT_PERSIST, 5, 4, gemm_nt160p_kernel<EPI, 5, 0, 4>);
+            CE_NT_CASE(NT_NT256x2, 3, gemm_nt256_kernel<EPI, 3, 2>);
+            CE_NT_CASE(NT_NT256x2, 4, gemm_nt256_kernel<EPI, 4, 2>);
+            CE_NT_CASE(NT_NT256x4, 3, gemm_nt256_kernel<EPI, 3, 4>);
+            CE_NT_CASE(NT_NT256x4, 4, gemm_nt256_kernel<EPI, 4, 4>);
+            CE_NT_CASE(NT_NT256x4, 5, gemm_nt256_kernel<EPI, 5, 4>);
+            CE_NT_CASE(NT_NT256x4, 6, gemm_nt256_kernel<EPI, 6, 4>);
+            CE_NT_CASE(NT_NT256x4, 7, gemm_nt256_kernel<EPI, 7, 4>);
+            CE_NT_CASE(NT_NT256x4, 8, gemm_nt256_kernel<EPI, 8, 4>);
+            CE_NT_CASE(NT_SKINNY, 2, gemm_nt_skinny_kernel<EPI>);
+        }
+    }
+#undef CE_NT_CASE
+#undef CE_NT_CASE_IF
+    return false;
 }
 
-template <int EPI>
+// Plan, tag, fill in the tiling, launch.  F8: e4m3 operands with per-row scales sa / sb applied in the epilogue; returns 1 when
+// the shape is not one the loader-wave kernels take (the caller falls back).
+template <int EPI, int F8>
 int launch_nt(NTArgs a, hipStream_t stream) {
-    static std::once_flag attr_set;
-    std::call_once(attr_set, [] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt256_kernel<EPI, 5, 2>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, N2H_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt32_kernel<EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, N3_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160_kernel<EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, N4_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160lw_kernel<EPI, 5>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, N4_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160lw_kernel<EPI, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, N4_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160lw_kernel<EPI, 3>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, N4_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 5>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 4>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 3>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-        if constexpr (nt_two_heights(EPI)) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 5, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 5, 0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 5, 0, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 5, 0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-        }
-    });
-    const double out_b = epi_traffic_bytes(EPI);
-    CeProfScope prof(nt_prof_class(EPI), 2.0 * a.M * a.N * a.K, 2.0 * ((double)a.M * a.K + (double)a.N * a.K) + out_b * a.M * a.N, stream);
-    const int force = nt_variant();
-    const bool can256 = (a.K % N2_BK == 0) && a.N % 8 == 0 && a.ldo % 8 == 0 && a.ldo2 % 8 == 0 && a.ldaux % 8 == 0;
-    const bool want256 = force == 256 || (force == 0 && a.M >= 1024 && a.N >= 256);
-    if (can256 && want256) {
-        a.tiles_n = ce_div_up(a.N, N2_BN);
-        // pick the tile height by wave quantisation: cost ~ (rounds over 256 CUs) x (cost of one tile-round)
-        const int f = force_tm();
-        const long t5 = (long)ce_div_up(a.M, 160) * a.tiles_n;
-        int best = 8;
-        long best_cost = -1;
-        if (f >= 3 && f <= 8) {
-            best = f;
-        } else {
-            for (int tm = 8; tm >= 3; --tm) {
-                const long cost = nt256_cost((long)ce_div_up(a.M, 32 * tm) * a.tiles_n, tm);
-                if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = tm; }
-            }
-        }
-        const bool use32 = f == 32 || (f == 0 && a.K % N3_BK == 0 && nt32_cost(t5) < best_cost);
-        // Where the cost model picks a 256-column tile with one workgroup per CU and the tiles fit one resident round
-        // (N = width GEMMs: 240 tiles of 160x256), use the loader-wave kernel (gemm_nt160lw_kernel: -2.7 % on the step
-        // against the 160x128 pair below, which was itself 0.5-2 % ahead of the plain 8-wave tile because a workgroup of
-        // the OTHER tower's GEMM could share the CU).  CE_NT_POLICY: bit 0 = treat single-round launches specially
-        // (default), bit 4 = with the loader-wave kernel (default; without it the 160x128 four-wave pair), bits 5, 6 = the
-        // persistent loader-wave kernel for multi-round launches (below; default), bit 1 = also
-        // instead of the two-workgroup 160x256x32 kernel (slower), bit 2 = pick the 160x128 family's tile height 96..160 by
-        // rounds over the 512 slots (slower in the step), bit 3 = also for multi-round launches (noise).
-        static int policy = getenv("CE_NT_POLICY") ? atoi(getenv("CE_NT_POLICY")) : 113;
-        const long half_tiles = (long)ce_div_up(a.M, 160) * ce_div_up(a.N, 128);
-        const bool half = f == 104 || (f >= 203 && f <= 205) ||
-                          (f == 0 && (half_tiles <= 2 * cu_budget() || (policy & 8)) && ((policy & 1) && !use32 || (policy & 2) && use32));
-        // the loader-wave kernels address their epilogue operands with 32-bit buffer offsets (EpiBuf): every one must span < 2 GiB
-        const auto span = [&](long ld, long esz) { return (long)a.M * ld * esz; };
-        const bool fits31 = span(a.ldo, epi_out_bytes(EPI)) < (1l << 31) && span(a.ldo2, 2) < (1l << 31) && span(a.ldaux, 2) < (1l << 31) &&
-                            span(a.ldr, 4) < (1l << 31);
-        const bool lw = fits31 && (f == 161 || (half && f == 0 && (policy & 16)));       // one 160x256 loader-wave workgroup per CU
-        prof.retag(nt_prof_class(EPI) + (lw ? 5 : (half || f == 104 ? 1 : (use32 ? 3 : 2))));
-        // multi-round launches: the persistent loader-wave kernel.  Bit 5 = for the light epilogues (qkv forward: 726 ->
-        // 810 TF/s), bit 6 = also for the GELU epilogues (as kernels about equal to the two-workgroup 160x256x32 kernel
-        // since their epilogues lost the division and the backward's transcendentals).  Both on by default: B = 256 step
-        // 14.15 -> 14.00 (bit 5) -> 13.96 ms (bits 5 + 6), config 4 at B = 64 32.3 -> 31.9 -> 31.5 ms.
-        constexpr bool light_epi = EPI == CE_EPI_BF16 || EPI == CE_EPI_F32 || EPI == CE_EPI_BIAS_BF16 || EPI == CE_EPI_BIAS_F32;
-        const bool pers = !lw && fits31 && a.K >= 2 * N4_BK && ((f >= 163 && f <= 165) || f == 162 ||
-                                                     (f == 0 && !half && ((policy & 32) && light_epi || (policy & 64))));
-        // (A two-group "ping-pong" persistent kernel -- 128x256x64 tiles, one group of four waves multiplying while the other
-        //  issues the ring's LDS-DMAs and works through the previous tile's epilogue -- was built, parity-tested and measured in
-        //  round 3: BIAS_GELU 63.1 vs 55.4 us per launch, qkv 41.0 vs 35.3, step 12.77 vs 12.40 ms, slower in both versions; it
-        //  was removed in round 4.  DESIGN 6b keeps the post-mortem.)
-        if (pers) {
-            // tile height by the longest per-CU tile list: rows of tile work + ~48 rows' worth of epilogue per tile
-            int ptm = 5;
-            if (f >= 163 && f <= 165) ptm = f - 160;
-            else {
-                long bc = -1;
-                for (int tm = 5; tm >= 3; --tm) {
-                    const long tiles = (long)ce_div_up(a.M, 32 * tm) * a.tiles_n;
-                    const long cost = ((tiles + cu_budget() - 1) / cu_budget()) * (32 * tm + 48);
-                    if (bc < 0 || cost < bc) { bc = cost; ptm = tm; }
-                }
-            }
-            a.tiles_m = ce_div_up(a.M, 32 * ptm);
-            static const int strip = getenv("CE_NT_STRIP") ? atoi(getenv("CE_NT_STRIP")) : 0;   // column strips: measured no better (0 / 3 / 6 equal, 4 slower)
-            a.tile_strip = strip;
-            // XCD-owned walk (persist_walk): CE_NT_CHUNK = 0 (default) the launch-wide walk, -1 = chunks of tiles_m / 8 row
-            // panels, n > 0 = chunks of n.  OFF: with sc1 output stores it takes the c_fc GEMM's fetch from 166.8 to 68.3 MB
-            // (algorithmic 24.4; the floor of any 8-way partition is 57) and qkv's from 105.5 to 53.5 MB
-            // (profiles/r03_pmc_fetch_xcd_walk.txt) and the kernels do not get faster: BIAS_GELU 1.30 -> 1.32 ms/step, qkv
-            // 0.945 -> 0.96; with plain stores 1.37 -> 1.46 and 0.92 -> 1.00.  These launches are not bound by operand re-fetch.
-            static const int chunk = getenv("CE_NT_CHUNK") ? atoi(getenv("CE_NT_CHUNK")) : 0;
-            const int ch = g_force_chunk > -2 ? g_force_chunk : chunk;
-            a.tile_chunk = strip > 0 ? 0 : (ch < 0 ? (a.tiles_m >= 8 ? a.tiles_m / 8 : 1) : ch);   // floor: a chunk never spans three XCDs
-            const long tiles = (long)a.tiles_m * a.tiles_n;
-            // CE_NT_PGRID workgroups walk the tile list (default 256 = one per CU).  More, shorter lists = finer scheduling
-            // granularity when some CUs are held by another stream's kernels (or by RCCL): a workgroup that starts late then
-            // delays the launch by a shorter list.
-            static const int pgrid_env = getenv("CE_NT_PGRID") ? atoi(getenv("CE_NT_PGRID")) : 0;
-            const int pgrid = pgrid_env > 0 ? pgrid_env : cu_budget();
-            const dim3 grid((unsigned)(tiles < pgrid ? tiles : pgrid)), block(64 * (8 + N4_LOADERS));
-            // dynamic tile list (off by default): only where a workgroup walks more than one tile, with >= 3 K iterations
-            // (the fetched id is published by the barrier of iteration 1 and needed from iteration nk - 2) on the launch-wide walk
-            a.tile_queue = (g_dynamic && tiles > (long)grid.x && a.K >= 3 * N4_BK && a.tile_chunk == 0) ? next_tile_queue(stream) : nullptr;
-            prof.retag(nt_prof_class(EPI) + 6);
-            // TWO TILE HEIGHTS (gemm_nt160p_kernel<EPI, 5, 0, TS>): n_tall row panels of 160 rows, the rest in panels of 32 TS, chosen so
-            // that the longest per-workgroup list (tall tiles first, round-robin over the grid) is shortest under the same cost
-            // model; taken when it beats the best single height by >= 3 %.  12800 x 3072: 960 tiles of 160 rows = 3.75 rounds -> 3
-            // rounds of 160 + one of 128.  CE_NT_MIXED=0 switches it off.
-            g_last_tall = g_last_ts = 0;
-            constexpr bool mixed_epi = nt_two_heights(EPI);
-            if constexpr (mixed_epi) {
-                static const int mixed = getenv("CE_NT_MIXED") ? atoi(getenv("CE_NT_MIXED")) : 1;
-                if (mixed && f == 0 && strip == 0 && a.tile_chunk == 0 && a.M >= 320) {
-                    const long G = pgrid, tn = a.tiles_n;
-                    long uniform = -1;
-                    for (int tm = 5; tm >= 3; --tm) {
-                        const long tiles_u = (long)ce_div_up(a.M, 32 * tm) * tn;
-                        const long c = ((tiles_u + G - 1) / G) * (32 * tm + 48);
-                        if (uniform < 0 || c < uniform) uniform = c;
-                    }
-                    long b_tall, b_short;
-                    int b_ts;
-                    static const int min_gain = getenv("CE_NT_MIXED_GAIN") ? atoi(getenv("CE_NT_MIXED_GAIN")) : 3;   // per cent
-                    if (two_height_plan(a.M, tn, G, 5, uniform, min_gain, b_tall, b_short, b_ts)) {
-                        a.tall_panels = (int)b_tall;
-                        g_last_tall = (int)b_tall; g_last_ts = b_ts;
-                        a.tiles_m = (int)(b_tall + b_short);
-                        const long tiles2 = (long)a.tiles_m * a.tiles_n;
-                        const dim3 grid2((unsigned)(tiles2 < pgrid ? tiles2 : pgrid));
-                        a.tile_queue = (g_dynamic && tiles2 > (long)grid2.x && a.K >= 3 * N4_BK) ? next_tile_queue(stream) : nullptr;
-                        switch (b_ts) {
-                            case 1: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 5, 0, 1>), grid2, block, N4P_LDS_BYTES, stream, a); break;
-                            case 2: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 5, 0, 2>), grid2, block, N4P_LDS_BYTES, stream, a); break;
-                            case 3: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 5, 0, 3>), grid2, block, N4P_LDS_BYTES, stream, a); break;
-                            default: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 5, 0, 4>), grid2, block, N4P_LDS_BYTES, stream, a); break;
-                        }
-                        CE_LAUNCH_CHECK();
-                        return 0;
-                    }
-                }
-            }
-            switch (ptm) {
-                case 3: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 3>), grid, block, N4P_LDS_BYTES, stream, a); break;
-                case 4: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 4>), grid, block, N4P_LDS_BYTES, stream, a); break;
-                default: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 5>), grid, block, N4P_LDS_BYTES, stream, a); break;
-            }
-        } else if (lw) {
-            // shortest tile whose launch still fits one round of the 256 CUs (the text tower's N = 512 has two tile columns)
-            int ltm = 5;
-            static const int lw_tm = getenv("CE_NT_LW_TM") ? atoi(getenv("CE_NT_LW_TM")) : 0;
-            if (lw_tm >= 3 && lw_tm <= 5) ltm = lw_tm;
-            else
-                for (int tm = 4; tm >= 3; --tm)
-                    if ((long)ce_div_up(a.M, 32 * tm) * a.tiles_n <= cu_budget()) ltm = tm;
-            a.tiles_m = ce_div_up(a.M, 32 * ltm);
-            const dim3 grid(a.tiles_m * a.tiles_n), block(64 * (8 + N4_LOADERS));
-            switch (ltm) {
-                case 3: hipLaunchKernelGGL((gemm_nt160lw_kernel<EPI, 3>), grid, block, N4_LDS_BYTES, stream, a); break;
-                case 4: hipLaunchKernelGGL((gemm_nt160lw_kernel<EPI, 4>), grid, block, N4_LDS_BYTES, stream, a); break;
-                default: hipLaunchKernelGGL((gemm_nt160lw_kernel<EPI, 5>), grid, block, N4_LDS_BYTES, stream, a); break;
-            }
-        } else if (half) {
-            a.tiles_n = ce_div_up(a.N, 128);
-            int htm = 5;
-            if (f >= 203 && f <= 205) htm = f - 200;
-            else if (f == 0 && (policy & 4)) {        // tile height by rounds over the 512 slots
-                long bc = -1;
-                for (int tm = 5; tm >= 3; --tm) {
-                    const long tiles = (long)ce_div_up(a.M, 32 * tm) * a.tiles_n;
-                    const long cost = ((tiles + 511) / 512) * (28 + 10 * tm);
-                    if (bc < 0 || cost < bc) { bc = cost; htm = tm; }
-                }
-            }
-            switch (htm) {
-                case 3: launch_nt128<EPI, 3>(a, stream); break;
-                case 4: launch_nt128<EPI, 4>(a, stream); break;
-                default: launch_nt128<EPI, 5>(a, stream); break;
-            }
-        } else if (use32) {
-            a.tiles_m = ce_div_up(a.M, N3_BM);
-            hipLaunchKernelGGL(gemm_nt32_kernel<EPI>, dim3(a.tiles_m * a.tiles_n), dim3(512), N3_LDS_BYTES, stream, a);
-        } else if (f == 104) {   // 160x128, two workgroups per CU: measured equal to the 8-wave 160x256 tile, kept as an option
-            a.tiles_m = ce_div_up(a.M, 160);
-            a.tiles_n = ce_div_up(a.N, 128);
-            hipLaunchKernelGGL((gemm_nt256_kernel<EPI, 5, 2>), dim3(a.tiles_m * a.tiles_n), dim3(256), N2H_LDS_BYTES, stream, a);
-        } else if (f == 160) {   // three-stage ring: measured 6 % slower than the two-stage loop (the K loop is
-                                 // LDS-bandwidth bound, not DMA-latency bound); kept as an option
-            a.tiles_m = ce_div_up(a.M, 160);
-            hipLaunchKernelGGL(gemm_nt160_kernel<EPI>, dim3(a.tiles_m * a.tiles_n), dim3(512), N4_LDS_BYTES, stream, a);
-        } else {
-            switch (best) {
-                case 3: launch_nt256<EPI, 3>(a, stream); break;
-                case 4: launch_nt256<EPI, 4>(a, stream); break;
-                case 5: launch_nt256<EPI, 5>(a, stream); break;
-                case 6: launch_nt256<EPI, 6>(a, stream); break;
-                case 7: launch_nt256<EPI, 7>(a, stream); break;
-                default: launch_nt256<EPI, 8>(a, stream); break;
-            }
-        }
-    } else if (static const int skinny = getenv("CE_NT_SKINNY") ? atoi(getenv("CE_NT_SKINNY")) : 1;
-               skinny && force == 0 && a.M <= 512 && a.K % 256 == 0 && a.N % 8 == 0 && a.ldo % 8 == 0 && a.ldo2 % 8 == 0 &&
-               a.ldaux % 8 == 0 && a.ldr % 4 == 0) {
-        static std::once_flag sk_attr;
-        std::call_once(sk_attr, [] {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_skinny_kernel<EPI>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, SK_LDS_BYTES);
-        });
-        a.tiles_m = ce_div_up(a.M, 64);
-        a.tiles_n = ce_div_up(a.N, 64);
-        prof.retag(nt_prof_class(EPI) + 7);
-        hipLaunchKernelGGL(gemm_nt_skinny_kernel<EPI>, dim3(a.tiles_m * a.tiles_n), dim3(512), SK_LDS_BYTES, stream, a);
-    } else {
-        hipLaunchKernelGGL(gemm_nt_kernel<EPI>, dim3(a.tiles_m * a.tiles_n), dim3(256), NT_LDS_BYTES, stream, a);
-        if (EPI == CE_EPI_GELUGRAD_BF16 && a.out2) {   // the 128^2 kernel has no fused column sums
-            CE_LAUNCH_CHECK();
-            return ce_colsum_bf16(a.out, a.ldo, reinterpret_cast<float*>(a.out2), a.M, a.N, stream);
-        }
-    }
+    const NTPlan p = nt_plan(NTShape{a.M, a.N, a.K, a.lda, a.ldb, a.ldo, a.ldo2, a.ldaux, a.ldr}, EPI, F8, g_knobs);
+    if (!p.taken) return 1;
+    g_last_plan = p;
+    const double operand_bytes = (F8 ? 1.0 : 2.0) * ((double)a.M * a.K + (double)a.N * a.K);
+    CeProfScope prof(nt_prof_class(EPI) + p.family, 2.0 * a.M * a.N * a.K, operand_bytes + epi_traffic_bytes(EPI) * a.M * a.N, stream);
+    a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.tall_panels = p.tall_panels; a.tile_chunk = p.tile_chunk;
+    a.tile_queue = p.wants_tile_queue ? next_tile_queue(stream) : nullptr;
+    CE_CHECK_ARG((dispatch<EPI, F8>(p, a, stream)), "ce_gemm_nt: no kernel %d with tile heights %d, %d (epilogue %d, fp8 %d)", (int)p.kernel,
+                 p.tm, p.ts, EPI, F8);
     CE_LAUNCH_CHECK();
-    return 0;
-}
-
-// e4m3 operands (per-row scales sa / sb applied in the epilogue) on the loader-wave kernels: the tile policy of launch_nt for
-// these two families -- one resident round -> gemm_nt160lw_kernel at the shortest tile that still fits the round, more ->
-// the persistent gemm_nt160p_kernel.  Returns 1 when the shape is not one these kernels take (the caller falls back).
-template <int EPI>
-int launch_nt_f8(NTArgs a, hipStream_t stream) {
-    static std::once_flag attr_set;
-    std::call_once(attr_set, [] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160lw_kernel<EPI, 5, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, N4_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160lw_kernel<EPI, 4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, N4_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160lw_kernel<EPI, 3, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, N4_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-        if constexpr (nt_two_heights(EPI)) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 4, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 4, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 4, 1, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-        }
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt160p_kernel<EPI, 3, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, N4P_LDS_BYTES);
-    });
-    if (!(a.M >= 1024 && a.N >= 256 && a.K % 128 == 0 && a.K >= 256 && a.N % 8 == 0 && a.lda % 16 == 0 && a.ldb % 16 == 0 &&
-          a.ldo % 8 == 0 && a.ldo2 % 8 == 0 && a.ldaux % 8 == 0))
-        return 1;
-    if ((long)a.M * a.ldo * epi_out_bytes(EPI) >= (1l << 31) || (long)a.M * a.ldo2 * 2 >= (1l << 31) || (long)a.M * a.ldaux * 2 >= (1l << 31) ||
-        (long)a.M * a.ldr * 4 >= (1l << 31))
-        return 1;                                  // 32-bit epilogue offsets (EpiBuf)
-    const double out_b = epi_traffic_bytes(EPI);
-    CeProfScope prof(nt_prof_class(EPI) + 4, 2.0 * a.M * a.N * a.K, 1.0 * ((double)a.M * a.K + (double)a.N * a.K) + out_b * a.M * a.N, stream);
-    a.tiles_n = ce_div_up(a.N, N4_BN);
-    const long half_tiles = (long)ce_div_up(a.M, 160) * ce_div_up(a.N, 128);
-    const dim3 block(64 * (8 + N4_LOADERS));
-    if (half_tiles <= 2 * cu_budget()) {           // one resident round of 160 x 256 tiles
-        int ltm = 5;
-        for (int tm = 4; tm >= 3; --tm)
-            if ((long)ce_div_up(a.M, 32 * tm) * a.tiles_n <= cu_budget()) ltm = tm;
-        a.tiles_m = ce_div_up(a.M, 32 * ltm);
-        const dim3 grid(a.tiles_m * a.tiles_n);
-        switch (ltm) {
-            case 3: hipLaunchKernelGGL((gemm_nt160lw_kernel<EPI, 3, 1>), grid, block, N4_LDS_BYTES, stream, a); break;
-            case 4: hipLaunchKernelGGL((gemm_nt160lw_kernel<EPI, 4, 1>), grid, block, N4_LDS_BYTES, stream, a); break;
-            default: hipLaunchKernelGGL((gemm_nt160lw_kernel<EPI, 5, 1>), grid, block, N4_LDS_BYTES, stream, a); break;
-        }
-    } else {
-        int ptm = 4;                               // 160-row tiles spill in the e4m3 form (32-byte fragments)
-        long bc = -1;
-        for (int tm = 4; tm >= 3; --tm) {
-            const long tiles = (long)ce_div_up(a.M, 32 * tm) * a.tiles_n;
-            const long cost = ((tiles + cu_budget() - 1) / cu_budget()) * (32 * tm + 48);
-            if (bc < 0 || cost < bc) { bc = cost; ptm = tm; }
-        }
-        a.tiles_m = ce_div_up(a.M, 32 * ptm);
-        a.tile_strip = 0;
-        a.tile_chunk = 0;
-        const long tiles = (long)a.tiles_m * a.tiles_n;
-        const dim3 grid((unsigned)(tiles < cu_budget() ? tiles : cu_budget()));
-        g_last_tall = g_last_ts = 0;
-        if constexpr (nt_two_heights(EPI)) {       // two tile heights (128-row panels + a shorter tail height), as launch_nt
-            static const int mixed = getenv("CE_NT_MIXED") ? atoi(getenv("CE_NT_MIXED")) : 1;
-            static const int min_gain = getenv("CE_NT_MIXED_GAIN") ? atoi(getenv("CE_NT_MIXED_GAIN")) : 3;
-            long b_tall, b_short;
-            int b_ts;
-            if (mixed && a.M >= 256 && two_height_plan(a.M, a.tiles_n, cu_budget(), 4, bc, min_gain, b_tall, b_short, b_ts)) {
-                a.tall_panels = (int)b_tall;
-                g_last_tall = (int)b_tall; g_last_ts = b_ts;
-                a.tiles_m = (int)(b_tall + b_short);
-                const long tiles2 = (long)a.tiles_m * a.tiles_n;
-                const dim3 grid2((unsigned)(tiles2 < cu_budget() ? tiles2 : cu_budget()));
-                switch (b_ts) {
-                    case 1: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 4, 1, 1>), grid2, block, N4P_LDS_BYTES, stream, a); break;
-                    case 2: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 4, 1, 2>), grid2, block, N4P_LDS_BYTES, stream, a); break;
-                    default: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 4, 1, 3>), grid2, block, N4P_LDS_BYTES, stream, a); break;
-                }
-                CE_LAUNCH_CHECK();
-                return 0;
-            }
-        }
-        switch (ptm) {
-            case 3: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 3, 1>), grid, block, N4P_LDS_BYTES, stream, a); break;
-            default: hipLaunchKernelGGL((gemm_nt160p_kernel<EPI, 4, 1>), grid, block, N4P_LDS_BYTES, stream, a); break;
-        }
-    }
-    CE_LAUNCH_CHECK();
+    if (p.needs_colsum_pass && a.out2) return ce_colsum_bf16(a.out, a.ldo, reinterpret_cast<float*>(a.out2), a.M, a.N, stream);
     return 0;
 }
 
@@ -2369,48 +2069,56 @@ int launch_nt_f8(NTArgs a, hipStream_t stream) {
 extern "C" int ce__gemm_nt_fp8_lw(const void* A8, long lda, const float* sa, const void* B8, long ldb, const float* sb, int M, int N,
                                   int K, int epilogue, const float* bias, const void* resid, long ldr, void* out, long ldo,
                                   void* out2, long ldo2, const void* aux, long ldaux, void* stream) {
-    static const int off = getenv("CE_FP8_LW") ? atoi(getenv("CE_FP8_LW")) == 0 : 0;
-    if (off) return 1;
     NTArgs a;
     a.A = (const bf16_t*)A8; a.lda = lda; a.B = (const bf16_t*)B8; a.ldb = ldb;
     a.M = M; a.N = N; a.K = K; a.bias = bias; a.resid = (const float*)resid; a.ldr = ldr;
     a.out = out; a.ldo = ldo; a.out2 = (bf16_t*)out2; a.ldo2 = ldo2; a.aux = (const bf16_t*)aux; a.ldaux = ldaux;
     a.sa = sa; a.sb = sb;
-    a.tiles_m = a.tiles_n = 0;
     hipStream_t s = (hipStream_t)stream;
     switch (epilogue) {
-        case CE_EPI_BF16: return launch_nt_f8<CE_EPI_BF16>(a, s);
-        case CE_EPI_BIAS_BF16: return launch_nt_f8<CE_EPI_BIAS_BF16>(a, s);
-        case CE_EPI_BIAS_RESID_F32: return launch_nt_f8<CE_EPI_BIAS_RESID_F32>(a, s);
-        case CE_EPI_BIAS_RESID_F16: return launch_nt_f8<CE_EPI_BIAS_RESID_F16>(a, s);
-        case CE_EPI_BIAS_GELU: return launch_nt_f8<CE_EPI_BIAS_GELU>(a, s);
-        case CE_EPI_BIAS_QGELU_BF16: return launch_nt_f8<CE_EPI_BIAS_QGELU_BF16>(a, s);
-        case CE_EPI_GELUGRAD_BF16: return launch_nt_f8<CE_EPI_GELUGRAD_BF16>(a, s);
+        case CE_EPI_BF16: return launch_nt<CE_EPI_BF16, 1>(a, s);
+        case CE_EPI_BIAS_BF16: return launch_nt<CE_EPI_BIAS_BF16, 1>(a, s);
+        case CE_EPI_BIAS_RESID_F32: return launch_nt<CE_EPI_BIAS_RESID_F32, 1>(a, s);
+        case CE_EPI_BIAS_RESID_F16: return launch_nt<CE_EPI_BIAS_RESID_F16, 1>(a, s);
+        case CE_EPI_BIAS_GELU: return launch_nt<CE_EPI_BIAS_GELU, 1>(a, s);
+        case CE_EPI_BIAS_QGELU_BF16: return launch_nt<CE_EPI_BIAS_QGELU_BF16, 1>(a, s);
+        case CE_EPI_GELUGRAD_BF16: return launch_nt<CE_EPI_GELUGRAD_BF16, 1>(a, s);
         default: return 1;
     }
 }
 
 extern "C" int ce_gemm_set_dynamic_tiles(int on) {
-    g_dynamic = on < 0 ? (getenv("CE_NT_DYNAMIC") ? atoi(getenv("CE_NT_DYNAMIC")) : 0) : (on != 0);
+    g_knobs.dynamic = on < 0 ? knobs_from_env().dynamic : (on != 0);
     return 0;
 }
 
 extern "C" int ce_gemm_set_cu_budget(int cus) {
     CE_CHECK_ARG(cus == 0 || (cus >= 32 && cus <= 256), "ce_gemm_set_cu_budget: 32..256 CUs, or 0 for the default (CE_GEMM_CUS / 256)");
-    g_cus = cus ? cus : (getenv("CE_GEMM_CUS") ? atoi(getenv("CE_GEMM_CUS")) : 256);
+    g_knobs.cus = cus ? cus : knobs_from_env().cus;
     return 0;
 }
 
-// two-height plan of the most recent persistent NT launch (tests): tall panels, short height in 32-row units (0, 0: one height)
+// what the launch policy would do with this problem under the process's current knobs; launches nothing
+extern "C" int ce_gemm_nt_plan(int M, int N, int K, int epilogue, int fp8, long lda, long ldb, long ldo, long ldo2, long ldaux,
+                               long ldr, ce_nt_plan* out) {
+    CE_CHECK_ARG(out && M > 0 && N > 0 && K > 0, "ce_gemm_nt_plan: empty problem M=%d N=%d K=%d, or no result struct", M, N, K);
+    CE_CHECK_ARG(epilogue >= CE_EPI_BF16 && epilogue <= CE_EPI_BIAS_QGELU_BF16, "ce_gemm_nt_plan: unknown epilogue %d", epilogue);
+    const NTPlan p = nt_plan(NTShape{M, N, K, lda, ldb, ldo, ldo2, ldaux, ldr}, epilogue, fp8 != 0, g_knobs);
+    *out = ce_nt_plan{p.kernel, p.tm, p.ts, p.tall_panels, p.tiles_m, p.tiles_n, p.tile_chunk, p.workgroups, p.block, p.lds_bytes,
+                      p.wants_tile_queue, p.taken};
+    return 0;
+}
+
+// two-height plan of the most recent NT launch (tests): tall panels, short height in 32-row units (0, 0: one height)
 extern "C" int ce_gemm_nt_last_plan(int* tall_panels, int* short_tm) {
-    if (tall_panels) *tall_panels = g_last_tall;
-    if (short_tm) *short_tm = g_last_ts;
+    if (tall_panels) *tall_panels = g_last_plan.tall_panels;
+    if (short_tm) *short_tm = g_last_plan.ts;
     return 0;
 }
 
 extern "C" void ce_gemm_nt_tune(int variant) {
-    if (variant >= 1000 && variant < 2000) g_force_chunk = variant - 1001;   // 1000: auto chunks, 1001: off, 1001 + n: n panels
-    else g_force_tm = variant;
+    if (variant >= 1000 && variant < 2000) g_knobs.force_chunk = variant - 1001;   // 1000: auto chunks, 1001: off, 1001 + n: n panels
+    else g_knobs.force_tile = variant < 0 ? 0 : variant;
 }
 
 extern "C" int ce_gemm_nt(const void* A, long lda, const void* B, long ldb, int M, int N, int K, int epilogue,
@@ -2425,32 +2133,31 @@ extern "C" int ce_gemm_nt(const void* A, long lda, const void* B, long ldb, int 
     a.A = (const bf16_t*)A; a.lda = lda; a.B = (const bf16_t*)B; a.ldb = ldb;
     a.M = M; a.N = N; a.K = K; a.bias = bias; a.resid = (const float*)resid; a.ldr = ldr;
     a.out = out; a.ldo = ldo; a.out2 = (bf16_t*)out2; a.ldo2 = ldo2; a.aux = (const bf16_t*)aux; a.ldaux = ldaux;
-    a.tiles_m = ce_div_up(M, NT_BM); a.tiles_n = ce_div_up(N, NT_BN);
     hipStream_t s = (hipStream_t)stream;
     switch (epilogue) {
-        case CE_EPI_BF16: return launch_nt<CE_EPI_BF16>(a, s);
-        case CE_EPI_F32: return launch_nt<CE_EPI_F32>(a, s);
+        case CE_EPI_BF16: return launch_nt<CE_EPI_BF16, 0>(a, s);
+        case CE_EPI_F32: return launch_nt<CE_EPI_F32, 0>(a, s);
         case CE_EPI_BIAS_BF16:
             CE_CHECK_ARG(bias, "ce_gemm_nt: bias epilogue without bias");
-            return launch_nt<CE_EPI_BIAS_BF16>(a, s);
+            return launch_nt<CE_EPI_BIAS_BF16, 0>(a, s);
         case CE_EPI_BIAS_F32:
             CE_CHECK_ARG(bias, "ce_gemm_nt: bias epilogue without bias");
-            return launch_nt<CE_EPI_BIAS_F32>(a, s);
+            return launch_nt<CE_EPI_BIAS_F32, 0>(a, s);
         case CE_EPI_BIAS_RESID_F32:
             CE_CHECK_ARG(bias && resid && ldr >= N && ldr % 4 == 0, "ce_gemm_nt: residual epilogue needs bias+resid");
-            return launch_nt<CE_EPI_BIAS_RESID_F32>(a, s);
+            return launch_nt<CE_EPI_BIAS_RESID_F32, 0>(a, s);
         case CE_EPI_BIAS_RESID_F16:
             CE_CHECK_ARG(bias && resid && ldr >= N && ldr % 8 == 0 && ldo % 8 == 0, "ce_gemm_nt: fp16 residual epilogue needs bias+resid, ldr/ldo multiples of 8");
-            return launch_nt<CE_EPI_BIAS_RESID_F16>(a, s);
+            return launch_nt<CE_EPI_BIAS_RESID_F16, 0>(a, s);
         case CE_EPI_BIAS_GELU:
             CE_CHECK_ARG(bias && out2 && ldo2 >= N && ldo2 % 4 == 0, "ce_gemm_nt: gelu epilogue needs bias+out2");
-            return launch_nt<CE_EPI_BIAS_GELU>(a, s);
+            return launch_nt<CE_EPI_BIAS_GELU, 0>(a, s);
         case CE_EPI_BIAS_QGELU_BF16:
             CE_CHECK_ARG(bias, "ce_gemm_nt: QuickGELU epilogue without bias");
-            return launch_nt<CE_EPI_BIAS_QGELU_BF16>(a, s);
+            return launch_nt<CE_EPI_BIAS_QGELU_BF16, 0>(a, s);
         case CE_EPI_GELUGRAD_BF16:
             CE_CHECK_ARG(aux && ldaux >= N && ldaux % 4 == 0, "ce_gemm_nt: gelu-grad epilogue needs aux");
-            return launch_nt<CE_EPI_GELUGRAD_BF16>(a, s);
+            return launch_nt<CE_EPI_GELUGRAD_BF16, 0>(a, s);
         default: CE_CHECK_ARG(false, "ce_gemm_nt: unknown epilogue %d", epilogue);
     }
     return 0;

@@ -53,7 +53,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 // tile index -> (tm, tn) in column strips of p.tile_strip tile columns, row-major inside a strip: the 32 consecutive
 // tiles an XCD holds in one round of the persistent kernel are then 8 row panels x 4 column panels (12 A/B panels through
-// its L2) instead of 2.7 x 12 (15 panels, the 12 of B re-read every round).  Measured: no gain in the step (CE_NT_STRIP, off).
+// its L2) instead of 2.7 x 12 (15 panels, the 12 of B re-read every round).  Measured: no gain in the step (0 / 3 / 6 equal, 4 slower); the launcher passes 0.
 __device__ __forceinline__ void strip_tile_coords(const NTArgs& p, int tile, int& tm, int& tn) {
     const int gw = p.tile_strip;
     if (gw <= 0 || gw >= p.tiles_n) {

@@ -496,14 +496,27 @@ int ce_profile_collect(double* out, int max_classes);
 int ce_profile_num_classes(void);
 const char* ce_profile_class_name(int cls);
 
-/* tuning hook (tools/, tests/): force the NT tile variant -- 0 auto, 3..8 rows/32 of the 256-column kernel,
- * 32 = 160x256x32 two-workgroup kernel, 104 = 160x128 four-wave, 160 = three-stage ring, 161 = loader waves (one tile
- * per workgroup), 162 = persistent loader waves (163..165: with 96/128/160-row tiles); 1000..1999 = tile walk of the
- * persistent kernel: 1000 XCD-owned chunks of tiles_m / 8 row panels, 1001 launch-wide (default), 1001 + n chunks of n */
+/* tuning hook (tools/, tests/), the only way to force an NT tile variant (bf16 path; the e4m3 path ignores it) -- 0 auto,
+ * 3..8 rows/32 of the 256-column kernel, 32 = 160x256x32 two-workgroup kernel, 104 = 160x128 four-wave (203..205: with
+ * 96/128/160-row tiles), 160 = three-stage ring, 161 = loader waves (one tile per workgroup), 162 = persistent loader waves
+ * (163..165: with 96/128/160-row tiles); 1000..1999 = tile walk of the persistent kernel: 1000 XCD-owned chunks of
+ * tiles_m / 8 row panels, 1001 launch-wide (default, or CE_NT_CHUNK), 1001 + n chunks of n */
 void ce_gemm_nt_tune(int variant);
-/* the two-height tile plan of the most recent persistent NT launch (tests): row panels of 160 rows, height of the others in
- * 32-row units; 0, 0 when the launch used one height */
+/* the two-height tile plan of the most recent NT launch (tests): row panels of the tall height (160 rows; e4m3: 128), height of
+ * the others in 32-row units; 0, 0 when the launch used one height */
 int ce_gemm_nt_last_plan(int* tall_panels, int* short_tm);
+/* What the NT launch policy does with a problem under the process's current knobs (ce_gemm_nt_tune, ce_gemm_set_cu_budget,
+ * ce_gemm_set_dynamic_tiles, the environment): pure host arithmetic, launches nothing, needs no GPU.  kernel: 0 gemm_nt_kernel
+ * (128x128), 1 gemm_nt256_kernel<.,tm,2>, 2 gemm_nt256_kernel<.,tm,4>, 3 gemm_nt32_kernel, 4 gemm_nt160_kernel (ring),
+ * 5 gemm_nt160lw_kernel<.,tm>, 6 gemm_nt160p_kernel<.,tm,.,ts> (persistent), 7 gemm_nt_skinny_kernel; tm / ts: tile heights in
+ * 32-row units, ts > 0 = row panels tall_panels.. are 32 ts rows; tiles_m, tiles_n, tall_panels, tile_chunk: the kernel's tiling
+ * arguments; workgroups, block, lds_bytes: the launch; fp8 != 0: the e4m3 launcher, whose taken == 0 means that it falls back
+ * to gemm_nt8_kernel (every other field is then 0). */
+typedef struct { int kernel, tm, ts, tall_panels, tiles_m, tiles_n, tile_chunk,
+                 workgroups, block, lds_bytes, wants_tile_queue, taken; } ce_nt_plan;
+int ce_gemm_nt_plan(int M, int N, int K, int epilogue, int fp8,
+                    long lda, long ldb, long ldo, long ldo2, long ldaux, long ldr,
+                    ce_nt_plan* out);
 /* tuning hook (tools/ only): 0 auto, 4/5/6/8 = tile height (x32 rows) of the 256-column kernel, 105 = 160x128 tile */
 void ce_gemm_nt_fp8_tune(int variant);
 
