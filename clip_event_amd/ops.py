@@ -210,3 +210,30 @@ def gemm_nt_mx8(a8, sa8, b8, sb8, epilogue: int, *, bias=None, resid=None, aux=N
                                ptr(out), c_long(out.stride(0)), ptr(out2), c_long(out2.stride(0) if epilogue == L.EPI_BIAS_GELU else 0),
                                ptr(aux), c_long(aux.stride(0) if aux is not None else 0), stream()), "ce_gemm_nt_mx8")
     return (out, out2) if epilogue == L.EPI_BIAS_GELU else out
+
+
+def score_topk(q: torch.Tensor, keys: torch.Tensor, k: int, logit_scale=None, target=None, splits: int = 0):
+    """Best ``k`` keys of every query without the [nq, nk] matrix (``ce_score_topk``): ``(values [nq,k] f32, indices [nq,k]
+    int64, lse [nq] f32, rank [nq] int64 or None)``.  ``q`` / ``keys`` are used as given (normalise them first);
+    ``logit_scale`` a device scalar (the score is exp(logit_scale) <q, key>) or None; ``target`` int64 [nq] or None."""
+    import ctypes
+    assert q.dtype == torch.float32 and keys.dtype == torch.float32 and q.is_cuda and keys.is_cuda
+    assert q.dim() == 2 and keys.dim() == 2 and q.stride(1) == 1 and keys.stride(1) == 1 and q.shape[1] == keys.shape[1]
+    nq, E = q.shape
+    nk = keys.shape[0]
+    if target is not None:
+        assert target.dtype == torch.int64 and target.is_cuda and target.is_contiguous() and target.numel() == nq
+    if logit_scale is not None:
+        assert logit_scale.dtype == torch.float32 and logit_scale.is_cuda and logit_scale.numel() == 1
+    cl = lib()
+    cl.ce_score_topk_workspace_bytes.restype = ctypes.c_size_t
+    nbytes = int(cl.ce_score_topk_workspace_bytes(c_int(nq), c_int(nk), c_int(k), c_int(splits)))
+    ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=q.device)
+    top_val = torch.empty(nq, max(k, 0), dtype=torch.float32, device=q.device)
+    top_idx = torch.empty(nq, max(k, 0), dtype=torch.int64, device=q.device)
+    lse = torch.empty(nq, dtype=torch.float32, device=q.device)
+    rank = None if target is None else torch.empty(nq, dtype=torch.int64, device=q.device)
+    check(cl.ce_score_topk(ptr(q), c_long(q.stride(0)), c_int(nq), ptr(keys), c_long(keys.stride(0)), c_int(nk), c_int(E),
+                           ptr(logit_scale), ptr(target), c_int(k), c_int(splits), ptr(top_val), ptr(top_idx), ptr(lse), ptr(rank),
+                           ptr(ws), stream()), "ce_score_topk")
+    return top_val, top_idx, lse, rank

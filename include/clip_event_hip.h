@@ -441,6 +441,26 @@ int ce_infonce_bwd(const float* q, long ldq, const int64_t* sel, int nq, const f
                    const float* logit_scale, const int64_t* labels, const float* lse, const float* grad, float* dq, float* dk,
                    float* dlogit_scale, void* stream);
 
+/* Scoring without the [nq, nk] logits matrix (retrieval.hip): best-k keys per query, log-sum-exp and the rank of one target,
+ * on the similarity sweep of ce_infonce_fwd.  q [nq,E], keys [nk,E] are used as given (the caller normalises them:
+ * ce_l2norm_fwd).  score(r, c) = s <q_r, keys_c>, s = exp(*logit_scale) (logit_scale nullable: s = 1).  Candidates are
+ * ordered by score descending, then key index ascending.
+ *   top_val / top_idx [nq,k]: the first k keys in that order, padded with -inf / -1 when nk < k;  1 <= k <= CE_TOPK_MAX
+ *   lse [nq] (nullable): log sum_c exp(score(r, c))
+ *   rank [nq] (nullable; needs target): 0-based position of key target[r] in that order; a target outside 0..nk-1 gives -1
+ *        and is never dereferenced
+ * Every score comes from one instruction sequence whatever its place in a tile, a split or the grid: bit-identical key rows
+ * tie exactly, rank[r] < k implies top_idx[r, rank[r]] == target[r], and top_val / top_idx / rank do not depend on `splits`
+ * (0 = chosen by the launcher so that few queries still fill the chip, else 1..CE_INFONCE_MAX_SPLITS, clamped to the number
+ * of 32-key blocks).  workspace = ce_score_topk_workspace_bytes(nq, nk, k, splits) bytes of scratch (0 for arguments
+ * ce_score_topk refuses).  fp32 on v_mfma_f32_32x32x2_f32; E a multiple of 128, 128..1024.  No allocation, no
+ * synchronisation. */
+#define CE_TOPK_MAX 16
+size_t ce_score_topk_workspace_bytes(int nq, int nk, int k, int splits);
+int ce_score_topk(const float* q, long ldq, int nq, const float* keys, long ldk, int nk, int E, const float* logit_scale,
+                  const int64_t* target, int k, int splits, float* top_val, int64_t* top_idx, float* lse, int64_t* rank,
+                  void* workspace, void* stream);
+
 /* Small-batch contrastive head in three launches: feature normalisation, logits_per_image / logits_per_text over the batch
  * (model_clip.py:496-521), CriterionContrastive 'ce' with index_pos (model_clip.py:633-662) and the whole backward down to the raw
  * features, in fp32 -- for the sizes where the head between the towers' forward and backward is pure launch latency (config 2:
