@@ -58,61 +58,140 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
     const float denom = sqrtf(v) / bc2_sqrt + eps;
     p = __builtin_fmaf(-lr_bc1, m / denom, p);
 }
-__device__ __forceinline__ void adam_elem4(f32x4& p, f32x4 g, f32x4& m, f32x4& v, float coef, float wd, float b1, float b2,
-                                           float lr_bc1, float bc2_sqrt, float eps) {
+
+// One element of clip + SGD with momentum (torch.optim.SGD: engine.py:136-140 behind engine.py:89's clip).  As adam_elem:
+// every kernel form updates through this function with the multiply-adds spelled out, so that the flat, the tile and the segment
+// kernel give the same bits.  `first`: no momentum buffer yet -- it becomes a copy of the decayed gradient
+// whatever the dampening is (torch).  mu == 0: `buf` is neither read nor written.
+__device__ __forceinline__ void sgd_elem(float& p, float g, float& buf, float coef, float wd, float mu, float one_minus_damp,
+                                         float lr, bool first, bool nesterov) {
+#pragma clang fp contract(off)
+    g = g * coef;
+    if (wd != 0.f) g = __builtin_fmaf(p, wd, g);
+    float upd = g;
+    if (mu != 0.f) {
+        buf = first ? g : __builtin_fmaf(buf, mu, g * one_minus_damp);
+        upd = nesterov ? __builtin_fmaf(buf, mu, g) : buf;
+    }
+    p = __builtin_fmaf(-lr, upd, p);
+}
+
+__device__ __forceinline__ float clip_coef(const float* __restrict__ sumsq, float max_norm) {
+    return sumsq ? fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f)) : 1.0f;
+}
+
+// ---- update rules ----------------------------------------------------------------------------------------------------------------
+// A rule is what the three traversals below are instantiated with: NS, the number of fp32 state streams beside p and g; Args, the
+// by-value kernel argument; a device constructor that derives the per-launch scalars (the clip coefficient among them); and
+// elem(p, g, state), one element.  `state` has max(NS, 1) slots, so that a rule without state still has something to pass on.
+struct AdamRule {
+    static constexpr int NS = 2;                   // m, v
+    struct Args {
+        const float* sumsq;
+        float max_norm, lr, b1, b2, eps, wd, bc1, bc2_sqrt;
+    };
+    float coef, wd, b1, b2, lr_bc1, bc2_sqrt, eps;
+    __device__ explicit AdamRule(const Args& a)
+        : coef(clip_coef(a.sumsq, a.max_norm)), wd(a.wd), b1(a.b1), b2(a.b2), lr_bc1(a.lr / a.bc1), bc2_sqrt(a.bc2_sqrt), eps(a.eps) {}
+    __device__ __forceinline__ void elem(float& p, float g, float (&s)[2]) const {
+        adam_elem(p, g, s[0], s[1], coef, wd, b1, b2, lr_bc1, bc2_sqrt, eps);
+    }
+};
+
+struct sgd_args {
+    const float* sumsq;
+    float max_norm, lr, mu, one_minus_damp, wd;
+    int first, nesterov;
+};
+// MOM = false: momentum 0, no momentum buffer and no momentum traffic (flat form: 8 B read + 6 B written per parameter);
+// MOM = true: 12 B read + 10 B written
+template <bool MOM>
+struct SgdRule {
+    static constexpr int NS = MOM ? 1 : 0;         // the momentum buffer
+    using Args = sgd_args;
+    float coef, wd, mu, one_minus_damp, lr;
+    bool first, nesterov;
+    __device__ explicit SgdRule(const Args& a)
+        : coef(clip_coef(a.sumsq, a.max_norm)), wd(a.wd), mu(MOM ? a.mu : 0.f), one_minus_damp(a.one_minus_damp), lr(a.lr),
+          first(a.first != 0), nesterov(a.nesterov != 0) {}
+    __device__ __forceinline__ void elem(float& p, float g, float (&s)[1]) const {
+        sgd_elem(p, g, s[0], coef, wd, mu, one_minus_damp, lr, first, nesterov);
+    }
+};
+
+template <class Rule>
+constexpr int kSlots = Rule::NS > 0 ? Rule::NS : 1;
+
+// the four lanes of a 16-byte chunk through Rule::elem
+template <class Rule>
+__device__ __forceinline__ void elem4(const Rule& rule, f32x4& p, f32x4 g, f32x4 (&s)[kSlots<Rule>]) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        float pe = p[e], me = m[e], ve = v[e];
-        adam_elem(pe, g[e], me, ve, coef, wd, b1, b2, lr_bc1, bc2_sqrt, eps);
-        p[e] = pe; m[e] = me; v[e] = ve;
+        float pe = p[e], se[kSlots<Rule>];
+#pragma unroll
+        for (int k = 0; k < kSlots<Rule>; ++k) se[k] = s[k][e];
+        rule.elem(pe, g[e], se);
+        p[e] = pe;
+#pragma unroll
+        for (int k = 0; k < kSlots<Rule>; ++k) s[k][e] = se[k];
     }
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, bf16_t* __restrict__ p16, long n,
-                                                   const float* __restrict__ sumsq, float max_norm, float lr, float b1,
-                                                   float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-    float coef = 1.0f;
-    if (sumsq) {
-        const float norm = sqrtf(*sumsq);
-        coef = fminf(1.0f, max_norm / (norm + 1e-6f));
-    }
-    // two 16-byte chunks per lane and iteration, all eight loads issued before the first use: the pass is pure streaming
-    // (16 B read + 14 B written per parameter) and wants as many bytes in flight as the registers allow
+// ---- the traversals --------------------------------------------------------------------------------------------------------------
+// Each is one kernel template over the rule.  The state streams are the kernel parameters s0, s1 (NULL beyond Rule::NS; parameters
+// rather than an array so that they keep __restrict__) and are named only under `k < Rule::NS`: a rule with NS == 0 issues no
+// state traffic at all.  Cache policy: p and the state through CE_ADAM_LD / CE_ADAM_ST, g always nontemporal.
+
+// the request for one 16-byte chunk of every stream at element offset `at`: p, g, then the state streams
+template <class Rule>
+__device__ __forceinline__ void load_chunk(float* p, const float* g, float* const (&st)[2], long at, f32x4& pv, f32x4& gv,
+                                           f32x4 (&sv)[kSlots<Rule>]) {
+    pv = CE_ADAM_LD(reinterpret_cast<f32x4*>(p + at));
+    gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + at));
+#pragma unroll
+    for (int k = 0; k < Rule::NS; ++k) sv[k] = CE_ADAM_LD(reinterpret_cast<f32x4*>(st[k] + at));
+}
+template <class Rule>
+__device__ __forceinline__ void store_state(float* const (&st)[2], long at, const f32x4 (&sv)[kSlots<Rule>]) {
+#pragma unroll
+    for (int k = 0; k < Rule::NS; ++k) CE_ADAM_ST(sv[k], reinterpret_cast<f32x4*>(st[k] + at));
+}
+__device__ __forceinline__ u32x2 pack_bf4(const f32x4& v) { return u32x2{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])}; }
+
+// Flat: grid-stride over [0, n).  Two 16-byte chunks per lane and iteration, every load issued before the first use: the pass is
+// pure streaming (Adam: 16 B read + 14 B written per parameter) and wants as many bytes in flight as the registers allow.
+template <class Rule>
+__global__ __launch_bounds__(256) void optim_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
+                                                         float* __restrict__ s1, bf16_t* __restrict__ p16, long n,
+                                                         typename Rule::Args a) {
+    const Rule rule(a);
+    float* const st[2] = {s0, s1};
     const long stride = gridDim.x * 2048L;
     for (long i0 = blockIdx.x * 2048L + threadIdx.x * 4; i0 < n; i0 += stride) {
         const long i1 = i0 + 1024;
         if (i1 + 3 < n) {
-            f32x4 pv[2], gv[2], mv[2], vv[2];
+            f32x4 pv[2], gv[2], sv[2][kSlots<Rule>] = {};
+#pragma unroll
+            for (int u = 0; u < 2; ++u) load_chunk<Rule>(p, g, st, u ? i1 : i0, pv[u], gv[u], sv[u]);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const long i = u ? i1 : i0;
-                pv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(p + i));
-                gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + i));
-                mv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(m + i));
-                vv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(v + i));
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const long i = u ? i1 : i0;
-                adam_elem4(pv[u], gv[u], mv[u], vv[u], coef, wd, b1, b2, lr / bc1, bc2_sqrt, eps);
+                elem4(rule, pv[u], gv[u], sv[u]);
                 CE_ADAM_ST(pv[u], reinterpret_cast<f32x4*>(p + i));
-                if (p16) {
-                    u32x2 pk = {pack_bf2(pv[u][0], pv[u][1]), pack_bf2(pv[u][2], pv[u][3])};
-                    *reinterpret_cast<u32x2*>(p16 + i) = pk;
-                }
-                CE_ADAM_ST(mv[u], reinterpret_cast<f32x4*>(m + i));
-                CE_ADAM_ST(vv[u], reinterpret_cast<f32x4*>(v + i));
+                if (p16) *reinterpret_cast<u32x2*>(p16 + i) = pack_bf4(pv[u]);
+                store_state<Rule>(st, i, sv[u]);
             }
         } else {
             for (int u = 0; u < 2; ++u) {
                 const long ib = u ? i1 : i0;
                 for (long k = ib; k < n && k < ib + 4; ++k) {
-                    float pk = p[k], mk = m[k], vk = v[k];
-                    adam_elem(pk, g[k], mk, vk, coef, wd, b1, b2, lr / bc1, bc2_sqrt, eps);
+                    float pk = p[k], sk[kSlots<Rule>] = {};
+#pragma unroll
+                    for (int q = 0; q < Rule::NS; ++q) sk[q] = st[q][k];
+                    rule.elem(pk, g[k], sk);
                     p[k] = pk;
-                    m[k] = mk;
-                    v[k] = vk;
+#pragma unroll
+                    for (int q = 0; q < Rule::NS; ++q) st[q][k] = sk[q];
                     if (p16) p16[k] = f2bf(pk);
                 }
             }
@@ -128,20 +207,53 @@ __global__ __launch_bounds__(256) void zero_segments_kernel(float* __restrict__ 
         __builtin_nontemporal_store(f32x4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f32x4*>(base + i));
 }
 
-// dst[c][r] = src[r][c] for a table of bf16 matrices, one launch: the transposed operand copies of every
-// weight (input-gradient GEMMs read W^T) are rebuilt from the bf16 mirror the Adam kernel wrote.
-__global__ __launch_bounds__(256) void multi_transpose_kernel(const ce_transpose_job* __restrict__ jobs, int njobs) {
-    // 64 x 64 tile through LDS; global accesses are 16 bytes per lane on both sides when rows/cols are multiples
-    // of 8 (every weight here), 2 bytes per lane otherwise.  Row stride 66 elements = 33 dwords: the 8 rows a lane
-    // gathers for one 16-byte transposed store sit in 8 different banks.
-    __shared__ bf16_t tile[64][66];
+// ---- 64 x 64 tiles of a table of bf16 matrices -----------------------------------------------------------------------------------
+// The tile a workgroup owns: its job and the tile's first row and column.
+struct tile_at {
+    ce_transpose_job job;
+    int r0, c0;
+};
+__device__ __forceinline__ tile_at find_tile(const ce_transpose_job* __restrict__ jobs, int njobs) {
     int j = 0;
     const int b = blockIdx.x;
     while (j + 1 < njobs && b >= jobs[j + 1].tile_start) ++j;      // block-uniform
     const ce_transpose_job job = jobs[j];
     const int t = b - job.tile_start;
     const int tiles_c = (job.cols + 63) / 64;
-    const int r0 = (t / tiles_c) * 64, c0 = (t % tiles_c) * 64;
+    return {job, (t / tiles_c) * 64, (t % tiles_c) * 64};
+}
+
+// The LDS tile ([source row][source column]; row stride 66 elements = 33 dwords: the 8 rows a lane gathers for one 16-byte
+// transposed store sit in 8 different banks) written to job.dst ([cols][rows]), 16 bytes per lane.  rows, cols multiples of 8.
+template <bool NT>
+__device__ __forceinline__ void store_tile_transposed(const bf16_t (&tile)[64][66], const tile_at& t) {
+    bf16_t* dst = reinterpret_cast<bf16_t*>(t.job.dst);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int idx = threadIdx.x + k * 256;                 // 64 output rows (source columns) x 8 chunks of 8 source rows
+        const int c = idx >> 3, ch = idx & 7;
+        if (t.c0 + c < t.job.cols && t.r0 + ch * 8 < t.job.rows) {
+            uint32_t w[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                w[e] = (uint32_t)tile[ch * 8 + 2 * e][c] | ((uint32_t)tile[ch * 8 + 2 * e + 1][c] << 16);
+            const u32x4 v = {w[0], w[1], w[2], w[3]};
+            u32x4* out = reinterpret_cast<u32x4*>(dst + (long)(t.c0 + c) * t.job.rows + t.r0 + ch * 8);
+            if (NT) __builtin_nontemporal_store(v, out);
+            else *out = v;
+        }
+    }
+}
+
+// dst[c][r] = src[r][c] for a table of bf16 matrices, one launch: the transposed operand copies of every
+// weight (input-gradient GEMMs read W^T) are rebuilt from the bf16 mirror the optimiser kernels wrote.
+__global__ __launch_bounds__(256) void multi_transpose_kernel(const ce_transpose_job* __restrict__ jobs, int njobs) {
+    // 64 x 64 tile through LDS; global accesses are 16 bytes per lane on both sides when rows/cols are multiples
+    // of 8 (every weight here), 2 bytes per lane otherwise.
+    __shared__ bf16_t tile[64][66];
+    const tile_at t = find_tile(jobs, njobs);
+    const ce_transpose_job& job = t.job;
+    const int r0 = t.r0, c0 = t.c0;
     const bf16_t* src = reinterpret_cast<const bf16_t*>(job.src);
     bf16_t* dst = reinterpret_cast<bf16_t*>(job.dst);
     const bool wide = (job.rows % 8 == 0) && (job.cols % 8 == 0) &&
@@ -158,19 +270,7 @@ __global__ __launch_bounds__(256) void multi_transpose_kernel(const ce_transpose
             trow[0] = v[0]; trow[1] = v[1]; trow[2] = v[2]; trow[3] = v[3];
         }
         __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int idx = threadIdx.x + k * 256;                 // 64 output rows (source columns) x 8 chunks
-            const int c = idx >> 3, ch = idx & 7;
-            if (c0 + c < job.cols && r0 + ch * 8 < job.rows) {
-                uint32_t w[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    w[e] = (uint32_t)tile[ch * 8 + 2 * e][c] | ((uint32_t)tile[ch * 8 + 2 * e + 1][c] << 16);
-                u32x4 v = {w[0], w[1], w[2], w[3]};
-                *reinterpret_cast<u32x4*>(dst + (long)(c0 + c) * job.rows + r0 + ch * 8) = v;
-            }
-        }
+        store_tile_transposed<false>(tile, t);
         return;
     }
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;        // 64 x 4
@@ -187,293 +287,76 @@ __global__ __launch_bounds__(256) void multi_transpose_kernel(const ce_transpose
     }
 }
 
-// clip + Adam over a table of bf16-mirrored MATRICES, one 64 x 64 tile per workgroup: the update of `adam_kernel` element for
+// Tiles: the update over a table of bf16-mirrored MATRICES, one 64 x 64 tile per workgroup: the flat kernel's update element for
 // element, and with it BOTH operand copies of the new weights -- the row-major bf16 mirror and, through an LDS transpose of the
 // tile, the W^T copy the input-gradient GEMMs read (`job.dst`, [cols][rows]) -- so that no separate transpose pass re-reads the
 // mirror (`multi_transpose_kernel`: 0.17 GB read + a launch beside the next forward's first kernels).  `job.src` points into the
 // flat mirror `p16`: its offset there is the matrix's offset in every flat buffer.  rows, cols multiples of 8.
-__global__ __launch_bounds__(256) void adam_tiles_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                         float* __restrict__ v, bf16_t* __restrict__ p16,
-                                                         const ce_transpose_job* __restrict__ jobs, int njobs,
-                                                         const float* __restrict__ sumsq, float max_norm, float lr, float b1, float b2,
-                                                         float eps, float wd, float bc1, float bc2_sqrt) {
+template <class Rule>
+__global__ __launch_bounds__(256) void optim_tiles_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
+                                                          float* __restrict__ s1, bf16_t* __restrict__ p16,
+                                                          const ce_transpose_job* __restrict__ jobs, int njobs, typename Rule::Args a) {
     __shared__ bf16_t tile[64][66];
-    float coef = 1.0f;
-    if (sumsq) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f));
-    int j = 0;
-    const int b = blockIdx.x;
-    while (j + 1 < njobs && b >= jobs[j + 1].tile_start) ++j;      // block-uniform
-    const ce_transpose_job job = jobs[j];
-    const int t = b - job.tile_start;
-    const int tiles_c = (job.cols + 63) / 64;
-    const int r0 = (t / tiles_c) * 64, c0 = (t % tiles_c) * 64;
-    const long off = reinterpret_cast<const bf16_t*>(job.src) - p16;
-    bf16_t* dst = reinterpret_cast<bf16_t*>(job.dst);
-    // 64 rows x 16 four-element chunks; all sixteen loads of a thread in flight before the first use
-    f32x4 pv[4], gv[4], mv[4], vv[4];
+    const Rule rule(a);
+    float* const st[2] = {s0, s1};
+    const tile_at t = find_tile(jobs, njobs);
+    const long off = reinterpret_cast<const bf16_t*>(t.job.src) - p16;
+    // 64 rows x 16 four-element chunks; all loads of a thread (Adam: sixteen) in flight before the first use
+    f32x4 pv[4] = {}, gv[4] = {}, sv[4][kSlots<Rule>] = {};
     bool ok[4];
     long at[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int idx = threadIdx.x + k * 256;
         const int r = idx >> 4, ch = idx & 15;
-        ok[k] = r0 + r < job.rows && c0 + ch * 4 < job.cols;
-        at[k] = off + (long)(r0 + r) * job.cols + c0 + ch * 4;
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        pv[k] = z; gv[k] = z; mv[k] = z; vv[k] = z;
-        if (ok[k]) {
-            pv[k] = CE_ADAM_LD(reinterpret_cast<f32x4*>(p + at[k]));
-            gv[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + at[k]));
-            mv[k] = CE_ADAM_LD(reinterpret_cast<f32x4*>(m + at[k]));
-            vv[k] = CE_ADAM_LD(reinterpret_cast<f32x4*>(v + at[k]));
-        }
+        ok[k] = t.r0 + r < t.job.rows && t.c0 + ch * 4 < t.job.cols;
+        at[k] = off + (long)(t.r0 + r) * t.job.cols + t.c0 + ch * 4;
+        if (ok[k]) load_chunk<Rule>(p, g, st, at[k], pv[k], gv[k], sv[k]);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int idx = threadIdx.x + k * 256;
         const int r = idx >> 4, ch = idx & 15;
-        adam_elem4(pv[k], gv[k], mv[k], vv[k], coef, wd, b1, b2, lr / bc1, bc2_sqrt, eps);
-        const u32x2 pk = {pack_bf2(pv[k][0], pv[k][1]), pack_bf2(pv[k][2], pv[k][3])};
+        elem4(rule, pv[k], gv[k], sv[k]);
+        const u32x2 pk = pack_bf4(pv[k]);
         uint32_t* trow = reinterpret_cast<uint32_t*>(&tile[r][ch * 4]);
         trow[0] = pk[0]; trow[1] = pk[1];
         if (ok[k]) {
             CE_ADAM_ST(pv[k], reinterpret_cast<f32x4*>(p + at[k]));
             __builtin_nontemporal_store(pk, reinterpret_cast<u32x2*>(p16 + at[k]));       // (nt on the mirror and on W^T: 1034 -> 986 us for
-                                                                                          //  the ViT-B/32 step in a loop of its own)
-            CE_ADAM_ST(mv[k], reinterpret_cast<f32x4*>(m + at[k]));
-            CE_ADAM_ST(vv[k], reinterpret_cast<f32x4*>(v + at[k]));
+                                                                                          //  the ViT-B/32 Adam step in a loop of its own)
+            store_state<Rule>(st, at[k], sv[k]);
         }
     }
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int idx = threadIdx.x + k * 256;                 // 64 output rows (source columns) x 8 chunks of 8 source rows
-        const int c = idx >> 3, ch = idx & 7;
-        if (c0 + c < job.cols && r0 + ch * 8 < job.rows) {
-            uint32_t w[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                w[e] = (uint32_t)tile[ch * 8 + 2 * e][c] | ((uint32_t)tile[ch * 8 + 2 * e + 1][c] << 16);
-            __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4*>(dst + (long)(c0 + c) * job.rows + r0 + ch * 8));
-        }
-    }
+    store_tile_transposed<true>(tile, t);
 }
 
-// the same update over a table of [lo, hi) chunks of the flat buffers (everything that is not one of the matrices above): one
-// workgroup per chunk of at most 2048 elements, both 16-byte pieces of a thread requested before the first use (as adam_kernel)
-__global__ __launch_bounds__(256) void adam_segments_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                            float* __restrict__ v, bf16_t* __restrict__ p16, const long* __restrict__ table,
-                                                            const float* __restrict__ sumsq, float max_norm, float lr, float b1, float b2,
-                                                            float eps, float wd, float bc1, float bc2_sqrt) {
-    float coef = 1.0f;
-    if (sumsq) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f));
+// Segments: the same update over a table of [lo, hi) chunks of the flat buffers (everything that is not one of the matrices
+// above): one workgroup per chunk of at most 2048 elements, both 16-byte pieces of a thread requested before the first use
+template <class Rule>
+__global__ __launch_bounds__(256) void optim_segments_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
+                                                             float* __restrict__ s1, bf16_t* __restrict__ p16,
+                                                             const long* __restrict__ table, typename Rule::Args a) {
+    const Rule rule(a);
+    float* const st[2] = {s0, s1};
     const long lo = table[2 * blockIdx.x], hi = table[2 * blockIdx.x + 1];
-    f32x4 pv[2], gv[2], mv[2], vv[2];
+    f32x4 pv[2] = {}, gv[2] = {}, sv[2][kSlots<Rule>] = {};
     long at[2];
     bool ok[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         at[u] = lo + threadIdx.x * 4 + u * 1024;
         ok[u] = at[u] + 3 < hi;
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        pv[u] = z; gv[u] = z; mv[u] = z; vv[u] = z;
-        if (ok[u]) {
-            pv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(p + at[u]));
-            gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + at[u]));
-            mv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(m + at[u]));
-            vv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(v + at[u]));
-        }
+        if (ok[u]) load_chunk<Rule>(p, g, st, at[u], pv[u], gv[u], sv[u]);
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         if (!ok[u]) continue;
-        adam_elem4(pv[u], gv[u], mv[u], vv[u], coef, wd, b1, b2, lr / bc1, bc2_sqrt, eps);
+        elem4(rule, pv[u], gv[u], sv[u]);
         CE_ADAM_ST(pv[u], reinterpret_cast<f32x4*>(p + at[u]));
-        if (p16) *reinterpret_cast<u32x2*>(p16 + at[u]) = u32x2{pack_bf2(pv[u][0], pv[u][1]), pack_bf2(pv[u][2], pv[u][3])};
-        CE_ADAM_ST(mv[u], reinterpret_cast<f32x4*>(m + at[u]));
-        CE_ADAM_ST(vv[u], reinterpret_cast<f32x4*>(v + at[u]));
-    }
-}
-
-// ---- clip + SGD with momentum (torch.optim.SGD: engine.py:136-140 behind engine.py:89's clip) ----------------------------------
-// One element.  As adam_elem: every kernel form updates through this function with the multiply-adds spelled out, so that the flat,
-// the tile and the segment kernel give the same bits.  `first`: no momentum buffer yet -- it becomes a copy of the decayed gradient
-// whatever the dampening is (torch).  mu == 0: `buf` is neither read nor written.
-__device__ __forceinline__ void sgd_elem(float& p, float g, float& buf, float coef, float wd, float mu, float one_minus_damp,
-                                         float lr, bool first, bool nesterov) {
-#pragma clang fp contract(off)
-    g = g * coef;
-    if (wd != 0.f) g = __builtin_fmaf(p, wd, g);
-    float upd = g;
-    if (mu != 0.f) {
-        buf = first ? g : __builtin_fmaf(buf, mu, g * one_minus_damp);
-        upd = nesterov ? __builtin_fmaf(buf, mu, g) : buf;
-    }
-    p = __builtin_fmaf(-lr, upd, p);
-}
-__device__ __forceinline__ void sgd_elem4(f32x4& p, f32x4 g, f32x4& buf, float coef, float wd, float mu, float one_minus_damp,
-                                          float lr, bool first, bool nesterov) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float pe = p[e], be = buf[e];
-        sgd_elem(pe, g[e], be, coef, wd, mu, one_minus_damp, lr, first, nesterov);
-        p[e] = pe; buf[e] = be;
-    }
-}
-
-// scalar arguments of the three SGD kernels
-struct sgd_args {
-    const float* sumsq;
-    float max_norm, lr, mu, one_minus_damp, wd;
-    int first, nesterov;
-};
-__device__ __forceinline__ float clip_coef(const float* __restrict__ sumsq, float max_norm) {
-    return sumsq ? fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f)) : 1.0f;
-}
-
-// MOM = false: momentum 0, `buf` is NULL and no momentum traffic is issued (8 B read + 6 B written per parameter);
-// MOM = true: 12 B read + 10 B written.  The access pattern is adam_kernel's.
-template <bool MOM>
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                  bf16_t* __restrict__ p16, long n, sgd_args a) {
-    const float coef = clip_coef(a.sumsq, a.max_norm);
-    const float mu = MOM ? a.mu : 0.f;
-    const bool first = a.first != 0, nesterov = a.nesterov != 0;
-    const long stride = gridDim.x * 2048L;
-    for (long i0 = blockIdx.x * 2048L + threadIdx.x * 4; i0 < n; i0 += stride) {
-        const long i1 = i0 + 1024;
-        if (i1 + 3 < n) {
-            f32x4 pv[2], gv[2], bv[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const long i = u ? i1 : i0;
-                pv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(p + i));
-                gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + i));
-                bv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (MOM) bv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(buf + i));
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const long i = u ? i1 : i0;
-                sgd_elem4(pv[u], gv[u], bv[u], coef, a.wd, mu, a.one_minus_damp, a.lr, first, nesterov);
-                CE_ADAM_ST(pv[u], reinterpret_cast<f32x4*>(p + i));
-                if (p16) {
-                    u32x2 pk = {pack_bf2(pv[u][0], pv[u][1]), pack_bf2(pv[u][2], pv[u][3])};
-                    *reinterpret_cast<u32x2*>(p16 + i) = pk;
-                }
-                if (MOM) CE_ADAM_ST(bv[u], reinterpret_cast<f32x4*>(buf + i));
-            }
-        } else {
-            for (int u = 0; u < 2; ++u) {
-                const long ib = u ? i1 : i0;
-                for (long k = ib; k < n && k < ib + 4; ++k) {
-                    float pk = p[k], bk = MOM ? buf[k] : 0.f;
-                    sgd_elem(pk, g[k], bk, coef, a.wd, mu, a.one_minus_damp, a.lr, first, nesterov);
-                    p[k] = pk;
-                    if (MOM) buf[k] = bk;
-                    if (p16) p16[k] = f2bf(pk);
-                }
-            }
-        }
-    }
-}
-
-// adam_tiles_kernel with the SGD update: one 64 x 64 tile of a bf16-mirrored matrix per workgroup, the new masters, the
-// momentum buffer, the row-major mirror and -- through the LDS transpose -- the W^T copy (12 B read + 12 B written per parameter)
-template <bool MOM>
-__global__ __launch_bounds__(256) void sgd_tiles_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                        bf16_t* __restrict__ p16, const ce_transpose_job* __restrict__ jobs, int njobs,
-                                                        sgd_args a) {
-    __shared__ bf16_t tile[64][66];
-    const float coef = clip_coef(a.sumsq, a.max_norm);
-    const float mu = MOM ? a.mu : 0.f;
-    const bool first = a.first != 0, nesterov = a.nesterov != 0;
-    int j = 0;
-    const int b = blockIdx.x;
-    while (j + 1 < njobs && b >= jobs[j + 1].tile_start) ++j;      // block-uniform
-    const ce_transpose_job job = jobs[j];
-    const int t = b - job.tile_start;
-    const int tiles_c = (job.cols + 63) / 64;
-    const int r0 = (t / tiles_c) * 64, c0 = (t % tiles_c) * 64;
-    const long off = reinterpret_cast<const bf16_t*>(job.src) - p16;
-    bf16_t* dst = reinterpret_cast<bf16_t*>(job.dst);
-    // 64 rows x 16 four-element chunks; all twelve loads of a thread in flight before the first use
-    f32x4 pv[4], gv[4], bv[4];
-    bool ok[4];
-    long at[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int idx = threadIdx.x + k * 256;
-        const int r = idx >> 4, ch = idx & 15;
-        ok[k] = r0 + r < job.rows && c0 + ch * 4 < job.cols;
-        at[k] = off + (long)(r0 + r) * job.cols + c0 + ch * 4;
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        pv[k] = z; gv[k] = z; bv[k] = z;
-        if (ok[k]) {
-            pv[k] = CE_ADAM_LD(reinterpret_cast<f32x4*>(p + at[k]));
-            gv[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + at[k]));
-            if (MOM) bv[k] = CE_ADAM_LD(reinterpret_cast<f32x4*>(buf + at[k]));
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int idx = threadIdx.x + k * 256;
-        const int r = idx >> 4, ch = idx & 15;
-        sgd_elem4(pv[k], gv[k], bv[k], coef, a.wd, mu, a.one_minus_damp, a.lr, first, nesterov);
-        const u32x2 pk = {pack_bf2(pv[k][0], pv[k][1]), pack_bf2(pv[k][2], pv[k][3])};
-        uint32_t* trow = reinterpret_cast<uint32_t*>(&tile[r][ch * 4]);
-        trow[0] = pk[0]; trow[1] = pk[1];
-        if (ok[k]) {
-            CE_ADAM_ST(pv[k], reinterpret_cast<f32x4*>(p + at[k]));
-            __builtin_nontemporal_store(pk, reinterpret_cast<u32x2*>(p16 + at[k]));
-            if (MOM) CE_ADAM_ST(bv[k], reinterpret_cast<f32x4*>(buf + at[k]));
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int idx = threadIdx.x + k * 256;                 // 64 output rows (source columns) x 8 chunks of 8 source rows
-        const int c = idx >> 3, ch = idx & 7;
-        if (c0 + c < job.cols && r0 + ch * 8 < job.rows) {
-            uint32_t w[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                w[e] = (uint32_t)tile[ch * 8 + 2 * e][c] | ((uint32_t)tile[ch * 8 + 2 * e + 1][c] << 16);
-            __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4*>(dst + (long)(c0 + c) * job.rows + r0 + ch * 8));
-        }
-    }
-}
-
-// adam_segments_kernel with the SGD update: one workgroup per [lo, hi) chunk of at most 2048 elements
-template <bool MOM>
-__global__ __launch_bounds__(256) void sgd_segments_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                           bf16_t* __restrict__ p16, const long* __restrict__ table, sgd_args a) {
-    const float coef = clip_coef(a.sumsq, a.max_norm);
-    const float mu = MOM ? a.mu : 0.f;
-    const bool first = a.first != 0, nesterov = a.nesterov != 0;
-    const long lo = table[2 * blockIdx.x], hi = table[2 * blockIdx.x + 1];
-    f32x4 pv[2], gv[2], bv[2];
-    long at[2];
-    bool ok[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        at[u] = lo + threadIdx.x * 4 + u * 1024;
-        ok[u] = at[u] + 3 < hi;
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        pv[u] = z; gv[u] = z; bv[u] = z;
-        if (ok[u]) {
-            pv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(p + at[u]));
-            gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + at[u]));
-            if (MOM) bv[u] = CE_ADAM_LD(reinterpret_cast<f32x4*>(buf + at[u]));
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        if (!ok[u]) continue;
-        sgd_elem4(pv[u], gv[u], bv[u], coef, a.wd, mu, a.one_minus_damp, a.lr, first, nesterov);
-        CE_ADAM_ST(pv[u], reinterpret_cast<f32x4*>(p + at[u]));
-        if (p16) *reinterpret_cast<u32x2*>(p16 + at[u]) = u32x2{pack_bf2(pv[u][0], pv[u][1]), pack_bf2(pv[u][2], pv[u][3])};
-        if (MOM) CE_ADAM_ST(bv[u], reinterpret_cast<f32x4*>(buf + at[u]));
+        if (p16) *reinterpret_cast<u32x2*>(p16 + at[u]) = pack_bf4(pv[u]);
+        store_state<Rule>(st, at[u], sv[u]);
     }
 }
 
@@ -489,6 +372,34 @@ int sgd_check(const char* who, const float* buf, float momentum, float dampening
 // step) cancels: at step 2 (1 - 0.998) the rounding of powf is up to 1.5e-5 of the result, and the update inherits it.
 float adam_bc1(float beta1, int step) { return (float)(1.0 - pow((double)beta1, (double)step)); }
 float adam_bc2_sqrt(float beta2, int step) { return (float)sqrt(1.0 - pow((double)beta2, (double)step)); }
+
+AdamRule::Args adam_args(const float* sumsq, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step) {
+    return {sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, adam_bc1(beta1, step), adam_bc2_sqrt(beta2, step)};
+}
+
+// ---- launchers: one per form, for every rule (arguments are checked by the callers) ------------------------------------------------
+unsigned flat_blocks(long n) {
+    static const long cap = getenv("CE_ADAM_BLOCKS") ? atol(getenv("CE_ADAM_BLOCKS")) : 4096;
+    const long blocks = (n + 2047) / 2048;
+    return (unsigned)(blocks > cap ? cap : blocks);
+}
+template <class Rule>
+void launch_flat(float* p, const float* g, float* s0, float* s1, void* p_bf16, long n, const typename Rule::Args& a, void* stream) {
+    hipLaunchKernelGGL(optim_flat_kernel<Rule>, dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, s0, s1,
+                       (bf16_t*)p_bf16, n, a);
+}
+
+// the matrices of the job table in tiles, then the [lo, hi) table in segments; either table may be empty
+template <class Rule>
+void launch_tiles(float* p, const float* g, float* s0, float* s1, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                  int total_tiles, const long* segments_device, int nsegments, const typename Rule::Args& a, void* stream) {
+    if (jobs_device && njobs > 0 && total_tiles > 0)
+        hipLaunchKernelGGL(optim_tiles_kernel<Rule>, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, p, g, s0, s1,
+                           (bf16_t*)p_bf16, jobs_device, njobs, a);
+    if (segments_device && nsegments > 0)
+        hipLaunchKernelGGL(optim_segments_kernel<Rule>, dim3((unsigned)nsegments), dim3(256), 0, (hipStream_t)stream, p, g, s0, s1,
+                           (bf16_t*)p_bf16, segments_device, a);
+}
 
 }  // namespace
 
@@ -515,16 +426,12 @@ extern "C" int ce_sumsq(const float* g, long n, float* out, void* stream) {
     return 0;
 }
 
+
 extern "C" int ce_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* sumsq,
                             float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                             void* stream) {
     CE_CHECK_ARG(n > 0 && step >= 1, "ce_adam_step: need n>0 and step>=1");
-    const float bc1 = adam_bc1(beta1, step), bc2_sqrt = adam_bc2_sqrt(beta2, step);
-    long blocks = (n + 2047) / 2048;
-    static const long cap = getenv("CE_ADAM_BLOCKS") ? atol(getenv("CE_ADAM_BLOCKS")) : 4096;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n, sumsq,
-                       max_norm, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt);
+    launch_flat<AdamRule>(p, g, m, v, p_bf16, n, adam_args(sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step), stream);
     CE_LAUNCH_CHECK();
     return 0;
 }
@@ -535,13 +442,8 @@ extern "C" int ce_adam_step_tiles(float* p, const float* g, float* m, float* v, 
                                   void* stream) {
     CE_CHECK_ARG(p && g && m && v && p_bf16 && step >= 1, "ce_adam_step_tiles: null buffer or step < 1");
     CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "ce_adam_step_tiles: nothing to update");
-    const float bc1 = adam_bc1(beta1, step), bc2_sqrt = adam_bc2_sqrt(beta2, step);
-    if (njobs > 0)
-        hipLaunchKernelGGL(adam_tiles_kernel, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
-                           jobs_device, njobs, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt);
-    if (nsegments > 0)
-        hipLaunchKernelGGL(adam_segments_kernel, dim3((unsigned)nsegments), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
-                           segments_device, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt);
+    launch_tiles<AdamRule>(p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                           adam_args(sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step), stream);
     CE_LAUNCH_CHECK();
     return 0;
 }
@@ -552,14 +454,8 @@ extern "C" int ce_sgd_step(float* p, const float* g, float* buf, void* p_bf16, l
     if (int rc = sgd_check("ce_sgd_step", buf, momentum, dampening, nesterov)) return rc;
     CE_CHECK_ARG(p && g, "ce_sgd_step: null buffer");
     const sgd_args a = {sumsq, max_norm, lr, momentum, 1.0f - dampening, weight_decay, first_step != 0, nesterov != 0};
-    long blocks = (n + 2047) / 2048;
-    static const long cap = getenv("CE_ADAM_BLOCKS") ? atol(getenv("CE_ADAM_BLOCKS")) : 4096;
-    if (blocks > cap) blocks = cap;
-    if (momentum > 0.f)
-        hipLaunchKernelGGL(sgd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, (bf16_t*)p_bf16, n, a);
-    else
-        hipLaunchKernelGGL(sgd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, (float*)nullptr,
-                           (bf16_t*)p_bf16, n, a);
+    if (momentum > 0.f) launch_flat<SgdRule<true>>(p, g, buf, nullptr, p_bf16, n, a, stream);
+    else launch_flat<SgdRule<false>>(p, g, nullptr, nullptr, p_bf16, n, a, stream);
     CE_LAUNCH_CHECK();
     return 0;
 }
@@ -572,17 +468,10 @@ extern "C" int ce_sgd_step_tiles(float* p, const float* g, float* buf, void* p_b
     CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "ce_sgd_step_tiles: nothing to update");
     CE_CHECK_ARG(p && g && p_bf16, "ce_sgd_step_tiles: null buffer");
     const sgd_args a = {sumsq, max_norm, lr, momentum, 1.0f - dampening, weight_decay, first_step != 0, nesterov != 0};
-    const bool mom = momentum > 0.f;
-    hipStream_t s = (hipStream_t)stream;
-    bf16_t* p16 = (bf16_t*)p_bf16;
-    if (jobs_device && njobs > 0 && total_tiles > 0) {
-        if (mom) hipLaunchKernelGGL(sgd_tiles_kernel<true>, dim3((unsigned)total_tiles), dim3(256), 0, s, p, g, buf, p16, jobs_device, njobs, a);
-        else hipLaunchKernelGGL(sgd_tiles_kernel<false>, dim3((unsigned)total_tiles), dim3(256), 0, s, p, g, (float*)nullptr, p16, jobs_device, njobs, a);
-    }
-    if (segments_device && nsegments > 0) {
-        if (mom) hipLaunchKernelGGL(sgd_segments_kernel<true>, dim3((unsigned)nsegments), dim3(256), 0, s, p, g, buf, p16, segments_device, a);
-        else hipLaunchKernelGGL(sgd_segments_kernel<false>, dim3((unsigned)nsegments), dim3(256), 0, s, p, g, (float*)nullptr, p16, segments_device, a);
-    }
+    if (momentum > 0.f)
+        launch_tiles<SgdRule<true>>(p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
+    else
+        launch_tiles<SgdRule<false>>(p, g, nullptr, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
     CE_LAUNCH_CHECK();
     return 0;
 }

@@ -16,9 +16,29 @@ from ._lib import check, lib, ptr, stream
 
 
 class _FusedFlatOptimizer(torch.optim.Optimizer):
-    """What the fused optimisers share: one param group over the model's flat buffers, the gradient zero-fill and the
-    device scalar of the gradient norm.  A subclass provides ``_state()`` (allocate the flat state buffers and ``sumsq``)."""
+    """What the fused optimisers share: one param group over the model's flat buffers, the gradient zero-fill, the device
+    scalar of the gradient norm, the whole of ``step()`` and the frames of ``state_dict()`` / ``load_state_dict()``.
 
+    A subclass names its two entry points (``_flat_op(p, g, *state, p16, n, *args, stream)`` on a range of the flat buffers,
+    ``_tiles_op(p, g, *state, p16, jobs, njobs, tiles, segments, nsegments, *args, stream)``) and its torch counterpart
+    (``_stock``), and provides ``_state()`` (allocate the flat state buffers and ``sumsq``), ``_step_args(sumsq)`` (the state
+    buffers the kernels take and the rule's scalar arguments) and ``_after_step(sharded)`` (what to note once the step is
+    launched)."""
+
+    def __init__(self, model, max_norm, defaults):
+        name = type(self).__name__
+        frozen = [n for n, p in model.named_parameters() if not p.requires_grad]
+        if frozen:
+            raise NotImplementedError(f"{name} updates the whole flat parameter buffer; frozen parameters "
+                                      f"({frozen[:3]}...) need {self._stock} over the trainable ones instead")
+        self.model = model
+        self.max_norm = max_norm
+        self.step_count = 0                # steps taken by THIS object (Adam's bias correction; the telemetry cadence)
+        self.sat_poll_every = int(os.environ.get("CE_SAT_POLL_EVERY", "16"))     # 0 = never
+        self.sumsq = None
+        super().__init__([p for p in model.parameters() if p.requires_grad], defaults)
+
+    # kept as attributes of the first (only) group so that schedulers and user code see one source of truth
     @property
     def lr(self):
         return self.param_groups[0]["lr"]
@@ -42,10 +62,91 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         """Device scalar: total L2 norm of the gradients as of the last ``step``."""
         return self.sumsq.sqrt()
 
+    @torch.no_grad()
+    def step(self, closure=None):
+        """clip + update (engine.py:87-95): sum of squares of the whole gradient buffer, then the update with the clip coefficient
+        applied on the fly -- by default in tiles that also leave the blocks' W^T operand copies behind (``_tiles_op``)."""
+        if closure is not None:
+            raise RuntimeError(f"{type(self).__name__}.step takes no closure")
+        self._state()
+        m = self.model
+        m._settle_first_touch()         # a tower that saw no backward since zero_grad_first_touch
+        m.wait_transposes()             # the update rewrites the bf16 mirror an asynchronous W^T rebuild may still be reading
+        n = m._flat.numel()
+        s = stream()
+        self.step_count += 1
+        from . import distributed as D
+        plan = getattr(getattr(m, "grad_sync", None), "plan", None)
+        sharded = plan is not None and D.active()
+        sumsq = self.sumsq if self.max_norm is not None else None
+        state, args = self._step_args(sumsq)
+
+        def sum_squares(lo, hi):
+            check(lib().ce_sumsq(ptr(m._flat_grad[lo:hi]), c_long(hi - lo), ptr(self.sumsq), s), "ce_sumsq")
+
+        def update(lo, hi):
+            check(getattr(lib(), self._flat_op)(ptr(m._flat[lo:hi]), ptr(m._flat_grad[lo:hi]),
+                                                *(ptr(b if b is None else b[lo:hi]) for b in state),      # (None: SGD without momentum)
+                                                ptr(m._flat16[lo:hi]), c_long(hi - lo), *args, s), self._flat_op)
+
+        if sharded:
+            # sharded step (distributed.ShardPlan; DESIGN 5 lever 2): the gradient pieces arrived reduce-SCATTERED, this rank updates
+            # its shard of every piece (+ the replicated head range), the fp32 masters are completed by an all-gather in place and
+            # the bf16 operand mirror is re-cast from them by the next refresh_operands; the optimiser state stays sharded
+            D.sharded_update(plan, m._flat, sumsq, sum_squares, update)
+            m.mark_operands_stale(mirror_fresh=False)
+        else:
+            if sumsq is not None:
+                sumsq.zero_()
+                sum_squares(0, n)
+            if getattr(m, "_adam_tiles_ok", False) and os.environ.get("CE_ADAM_TILES", "1") != "0":
+                # the block weights tile by tile, which also writes their W^T operand copies (no transpose pass at the start of the
+                # next step); everything else by the chunk table of the first-touch zero-fill (= the complement of the block weights)
+                tj, tn_, tt = m._tjobs_bwd
+                seg = m._adam_segment_table()
+                check(getattr(lib(), self._tiles_op)(ptr(m._flat), ptr(m._flat_grad), *(ptr(b) for b in state), ptr(m._flat16), ptr(tj),
+                                                     c_int(tn_), c_int(tt), ptr(seg), c_int(seg.shape[0]), *args, s), self._tiles_op)
+                m.mark_operands_stale(mirror_fresh=True, wt_fresh=True)
+            else:
+                update(0, n)
+                m.mark_operands_stale(mirror_fresh=True)
+        self._after_step(sharded)
+        # fp16 streams: look at the clamp counters every few steps, without a synchronisation (the copy started by one poll is
+        # examined by the next); raises model.Stream16Saturation.  On every exit of step(), the sharded one included.
+        if self.sat_poll_every and self.step_count % self.sat_poll_every == 0 and hasattr(m, "poll_stream16_saturation"):
+            m.poll_stream16_saturation()
+
     def _offset_of(self):
         """Flat offset of every parameter of the group, in group order."""
         names = {id(p): n for n, p in self.model.named_parameters()}
         return [self.model._offsets[names[id(p)]] for p in self.param_groups[0]["params"]]
+
+    def _pieces(self, buf):
+        """The piece of the flat buffer ``buf`` that belongs to each parameter of the group, in group order, in its shape."""
+        return [buf[o:o + p.numel()].view(p.shape) for p, o in zip(self.param_groups[0]["params"], self._offset_of())]
+
+    # ---- torch-format state (checkpoint interop): the frames; a subclass fills in the per-parameter state ----
+    def _state_dict_of(self, state):
+        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
+        group["params"] = list(range(len(self.param_groups[0]["params"])))
+        return {"state": state, "param_groups": [group]}
+
+    def _refuse_sharded_state(self, what):
+        if getattr(self, "_moments_stale", False):
+            raise RuntimeError(f"the {what} sharded over the ranks (sharded optimiser step): call "
+                               "clip_event_amd.distributed.consolidate(model, optimizer) on EVERY rank before state_dict()")
+
+    def _matching_group(self, sd):
+        """The one param group of ``sd``, after checking that it is ours."""
+        params, groups = self.param_groups[0]["params"], sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(params):
+            raise ValueError("optimizer state does not match: expected one group of %d parameters" % len(params))
+        return groups[0]
+
+    def _adopt_group(self, group):
+        for k, v in group.items():
+            if k != "params":
+                self.param_groups[0][k] = tuple(v) if k == "betas" else v
 
 
 class FusedAdam(_FusedFlatOptimizer):
@@ -59,22 +160,13 @@ class FusedAdam(_FusedFlatOptimizer):
     ``exp_avg_sq``): the ``'optimizer'`` entry of a reference checkpoint (engine.py:202-218) loads here and vice
     versa.  The moments themselves live in two flat buffers next to the flat parameters."""
 
+    _flat_op, _tiles_op, _stock = "ce_adam_step", "ce_adam_step_tiles", "torch.optim.Adam"
+
     def __init__(self, model, lr: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  max_norm=1.0):
-        frozen = [n for n, p in model.named_parameters() if not p.requires_grad]
-        if frozen:
-            raise NotImplementedError("FusedAdam updates the whole flat parameter buffer; frozen parameters "
-                                      f"({frozen[:3]}...) need torch.optim.Adam over the trainable ones instead")
-        self.model = model
-        self.max_norm = max_norm
-        self.step_count = 0
-        self.sat_poll_every = int(os.environ.get("CE_SAT_POLL_EVERY", "16"))     # 0 = never
-        self.m = self.v = self.sumsq = None
-        super().__init__([p for p in model.parameters() if p.requires_grad],
-                         dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+        self.m = self.v = None
+        super().__init__(model, max_norm, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
 
-    # kept as attributes of the first (only) group so that schedulers and user code see one source of truth (lr and
-    # weight_decay: the base class)
     @property
     def betas(self):
         return self.param_groups[0]["betas"]
@@ -96,105 +188,35 @@ class FusedAdam(_FusedFlatOptimizer):
         self._state()
         return (self.m, self.v)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        """clip + Adam (engine.py:87-95): sum of squares of the whole gradient buffer, then the update with the clip coefficient
-        applied on the fly -- by default in tiles that also leave the blocks' W^T operand copies behind (``ce_adam_step_tiles``)."""
-        if closure is not None:
-            raise RuntimeError("FusedAdam.step takes no closure")
-        self._state()
-        m = self.model
-        m._settle_first_touch()         # a tower that saw no backward since zero_grad_first_touch
-        m.wait_transposes()             # Adam rewrites the bf16 mirror an asynchronous W^T rebuild may still be reading
-        n = m._flat.numel()
-        s = stream()
-        self.step_count += 1
-        lr = float(self.param_groups[0]["lr"])
-        sumsq = None
-        from . import distributed as D
-        plan = getattr(getattr(m, "grad_sync", None), "plan", None)
-        sharded = plan is not None and D.active()
-        if self.max_norm is not None:
-            sumsq = self.sumsq
-            if not sharded:
-                self.sumsq.zero_()
-                check(lib().ce_sumsq(ptr(m._flat_grad), c_long(n), ptr(self.sumsq), s), "ce_sumsq")
+    def _step_args(self, sumsq):
+        return (self.m, self.v), (ptr(sumsq), c_float(self.max_norm or 0.0), c_float(float(self.lr)), c_float(self.betas[0]),
+                                  c_float(self.betas[1]), c_float(self.eps), c_float(self.weight_decay), c_int(self.step_count))
 
-        def adam(lo, hi, st):
-            check(lib().ce_adam_step(ptr(m._flat[lo:hi]), ptr(m._flat_grad[lo:hi]), ptr(self.m[lo:hi]), ptr(self.v[lo:hi]),
-                                     ptr(m._flat16[lo:hi]), c_long(hi - lo), ptr(sumsq), c_float(self.max_norm or 0.0), c_float(lr),
-                                     c_float(self.betas[0]), c_float(self.betas[1]), c_float(self.eps), c_float(self.weight_decay),
-                                     c_int(self.step_count), st), "ce_adam_step")
-
+    def _after_step(self, sharded):
         if sharded:
-            # sharded step (distributed.ShardPlan; DESIGN 5 lever 2): the gradient pieces arrived reduce-SCATTERED, this rank updates
-            # its shard of every piece (+ the replicated head range), the fp32 masters are completed by an all-gather in place and
-            # the bf16 operand mirror is re-cast from them by the next refresh_operands
-            D.sharded_update(plan, m._flat, sumsq,
-                             lambda lo, hi: check(lib().ce_sumsq(ptr(m._flat_grad[lo:hi]), c_long(hi - lo), ptr(self.sumsq), s), "ce_sumsq"),
-                             lambda lo, hi: adam(lo, hi, s))
             self._moments_stale = True
-            m.mark_operands_stale(mirror_fresh=False)
-            return
-        if getattr(m, "_adam_tiles_ok", False) and os.environ.get("CE_ADAM_TILES", "1") != "0":
-            # the block weights tile by tile, which also writes their W^T operand copies (no transpose pass at the start of the
-            # next step); everything else by the chunk table of the first-touch zero-fill (= the complement of the block weights)
-            tj, tn_, tt = m._tjobs_bwd
-            seg = m._adam_segment_table()
-            check(lib().ce_adam_step_tiles(ptr(m._flat), ptr(m._flat_grad), ptr(self.m), ptr(self.v), ptr(m._flat16), ptr(tj), c_int(tn_),
-                                           c_int(tt), ptr(seg), c_int(seg.shape[0]), ptr(sumsq), c_float(self.max_norm or 0.0), c_float(lr),
-                                           c_float(self.betas[0]), c_float(self.betas[1]), c_float(self.eps), c_float(self.weight_decay),
-                                           c_int(self.step_count), s), "ce_adam_step_tiles")
-            m.mark_operands_stale(mirror_fresh=True, wt_fresh=True)
-        else:
-            adam(0, n, s)
-            m.mark_operands_stale(mirror_fresh=True)
-        # fp16 streams: look at the clamp counters every few steps, without a synchronisation (the copy started by one poll is
-        # examined by the next); raises model.Stream16Saturation
-        if self.sat_poll_every and self.step_count % self.sat_poll_every == 0 and hasattr(m, "poll_stream16_saturation"):
-            m.poll_stream16_saturation()
 
-    # ---- torch.optim.Adam-format state (checkpoint interop) ----
     def state_dict(self):
         self._state()
-        m = self.model
-        if getattr(self, "_moments_stale", False):
-            raise RuntimeError("the Adam moments are sharded over the ranks (sharded optimiser step): call "
-                               "clip_event_amd.distributed.consolidate(model, optimizer) on EVERY rank before state_dict()")
+        self._refuse_sharded_state("Adam moments are")
         state = {}
-        params = self.param_groups[0]["params"]
-        names = {id(p): n for n, p in m.named_parameters()}
-        for i, p in enumerate(params):
-            o = m._offsets[names[id(p)]]
-            if self.step_count > 0:
-                state[i] = {"step": torch.tensor(float(self.step_count)),
-                            "exp_avg": self.m[o:o + p.numel()].view(p.shape).clone(),
-                            "exp_avg_sq": self.v[o:o + p.numel()].view(p.shape).clone()}
-        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
-        group["params"] = list(range(len(params)))
-        return {"state": state, "param_groups": [group]}
+        if self.step_count > 0:
+            for i, (m, v) in enumerate(zip(self._pieces(self.m), self._pieces(self.v))):
+                state[i] = {"step": torch.tensor(float(self.step_count)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+        return self._state_dict_of(state)
 
     def load_state_dict(self, sd):
         self._moments_stale = False          # (every rank loads the same tensors)
         self._state()
-        m = self.model
-        params = self.param_groups[0]["params"]
-        groups = sd["param_groups"]
-        if len(groups) != 1 or len(groups[0]["params"]) != len(params):
-            raise ValueError("optimizer state does not match: expected one group of %d parameters" % len(params))
-        for k, v in groups[0].items():
-            if k != "params":
-                self.param_groups[0][k] = tuple(v) if k == "betas" else v
-        names = {id(p): n for n, p in m.named_parameters()}
+        self._adopt_group(self._matching_group(sd))
         self.m.zero_()
         self.v.zero_()
+        m, v = self._pieces(self.m), self._pieces(self.v)
         steps = set()
         with torch.no_grad():
             for key, st in sd["state"].items():
-                p = params[int(key)]
-                o = m._offsets[names[id(p)]]
-                self.m[o:o + p.numel()].copy_(st["exp_avg"].reshape(-1))
-                self.v[o:o + p.numel()].copy_(st["exp_avg_sq"].reshape(-1))
+                m[int(key)].copy_(st["exp_avg"].reshape(m[int(key)].shape))
+                v[int(key)].copy_(st["exp_avg_sq"].reshape(v[int(key)].shape))
                 steps.add(int(st["step"]))
         if len(steps) > 1:
             raise ValueError("per-parameter step counts differ; the fused kernel keeps one")
@@ -209,8 +231,10 @@ class FusedSGD(_FusedFlatOptimizer):
     A real ``torch.optim.Optimizer`` like ``FusedAdam``: one param group that carries torch SGD's keys, ``state_dict()`` /
     ``load_state_dict()`` in ``torch.optim.SGD``'s format (per-parameter ``momentum_buffer``; empty before the first step and
     with momentum 0).  The momentum lives in ONE flat buffer next to the flat parameters -- none at all with momentum 0 -- and,
-    as in torch, "first step" means "no buffer yet", not a counter: the first step copies the decayed gradient into it whatever
-    the dampening is."""
+    as in torch, "first step" means "no buffer yet", not a counter (the arithmetic never reads ``step_count``): the first step
+    copies the decayed gradient into it whatever the dampening is."""
+
+    _flat_op, _tiles_op, _stock = "ce_sgd_step", "ce_sgd_step_tiles", "torch.optim.SGD"
 
     def __init__(self, model, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
                  nesterov: bool = False, max_norm=1.0):
@@ -222,19 +246,10 @@ class FusedSGD(_FusedFlatOptimizer):
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        frozen = [n for n, p in model.named_parameters() if not p.requires_grad]
-        if frozen:
-            raise NotImplementedError("FusedSGD updates the whole flat parameter buffer; frozen parameters "
-                                      f"({frozen[:3]}...) need torch.optim.SGD over the trainable ones instead")
-        self.model = model
-        self.max_norm = max_norm
-        self.step_count = 0                # steps taken by THIS object (telemetry cadence); the arithmetic never reads it
-        self.sat_poll_every = int(os.environ.get("CE_SAT_POLL_EVERY", "16"))     # 0 = never
-        self.buf = self.sumsq = None
+        self.buf = None
         self._has_buf = False              # a momentum buffer exists: the next step is not the first
-        super().__init__([p for p in model.parameters() if p.requires_grad],
-                         dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
-                              maximize=False, foreach=None, differentiable=False, fused=None))
+        super().__init__(model, max_norm, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                               nesterov=nesterov, maximize=False, foreach=None, differentiable=False, fused=None))
 
     @property
     def momentum(self):
@@ -255,102 +270,43 @@ class FusedSGD(_FusedFlatOptimizer):
         self._state()
         return (self.buf,) if self.momentum != 0 else ()
 
-    def _poll(self):
-        # fp16 streams: as FusedAdam.step, but on every exit of step(), the sharded one included
-        m = self.model
-        if self.sat_poll_every and self.step_count % self.sat_poll_every == 0 and hasattr(m, "poll_stream16_saturation"):
-            m.poll_stream16_saturation()
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        """clip + SGD: sum of squares of the whole gradient buffer, then the update with the clip coefficient applied on the fly --
-        by default in tiles that also leave the blocks' W^T operand copies behind (``ce_sgd_step_tiles``)."""
-        if closure is not None:
-            raise RuntimeError("FusedSGD.step takes no closure")
-        self._state()
-        m = self.model
-        m._settle_first_touch()         # a tower that saw no backward since zero_grad_first_touch
-        m.wait_transposes()             # the update rewrites the bf16 mirror an asynchronous W^T rebuild may still be reading
-        n = m._flat.numel()
-        s = stream()
-        self.step_count += 1
+    def _step_args(self, sumsq):
         group = self.param_groups[0]
         if group.get("maximize"):
             raise NotImplementedError("FusedSGD: maximize is not supported")
         lr, mu, damp, wd = (float(group[k]) for k in ("lr", "momentum", "dampening", "weight_decay"))
-        nesterov, first = int(bool(group["nesterov"])), int(not self._has_buf)
-        buf = self.buf if mu != 0 else None
-        sumsq = None
-        from . import distributed as D
-        plan = getattr(getattr(m, "grad_sync", None), "plan", None)
-        sharded = plan is not None and D.active()
-        if self.max_norm is not None:
-            sumsq = self.sumsq
-            if not sharded:
-                self.sumsq.zero_()
-                check(lib().ce_sumsq(ptr(m._flat_grad), c_long(n), ptr(self.sumsq), s), "ce_sumsq")
-        tail = (ptr(sumsq), c_float(self.max_norm or 0.0), c_float(lr), c_float(mu), c_float(damp), c_float(wd), c_int(nesterov),
-                c_int(first))
+        return (self.buf if mu != 0 else None,), (ptr(sumsq), c_float(self.max_norm or 0.0), c_float(lr), c_float(mu), c_float(damp),
+                                                  c_float(wd), c_int(int(bool(group["nesterov"]))), c_int(int(not self._has_buf)))
 
-        def sgd(lo, hi, st):
-            check(lib().ce_sgd_step(ptr(m._flat[lo:hi]), ptr(m._flat_grad[lo:hi]), ptr(buf[lo:hi]) if buf is not None else None,
-                                    ptr(m._flat16[lo:hi]), c_long(hi - lo), *tail, st), "ce_sgd_step")
-
+    def _after_step(self, sharded):
         if sharded:
-            # as FusedAdam: this rank updates its shard of every reduce-scattered piece (+ the replicated head range), the masters are
-            # all-gathered in place and the bf16 mirror is re-cast by the next refresh_operands; the momentum stays sharded
-            D.sharded_update(plan, m._flat, sumsq,
-                             lambda lo, hi: check(lib().ce_sumsq(ptr(m._flat_grad[lo:hi]), c_long(hi - lo), ptr(self.sumsq), s), "ce_sumsq"),
-                             lambda lo, hi: sgd(lo, hi, s))
-            self._moments_stale = buf is not None
-            m.mark_operands_stale(mirror_fresh=False)
-        elif getattr(m, "_adam_tiles_ok", False) and os.environ.get("CE_ADAM_TILES", "1") != "0":
-            tj, tn_, tt = m._tjobs_bwd
-            seg = m._adam_segment_table()
-            check(lib().ce_sgd_step_tiles(ptr(m._flat), ptr(m._flat_grad), ptr(buf), ptr(m._flat16), ptr(tj), c_int(tn_), c_int(tt),
-                                          ptr(seg), c_int(seg.shape[0]), *tail, s), "ce_sgd_step_tiles")
-            m.mark_operands_stale(mirror_fresh=True, wt_fresh=True)
-        else:
-            sgd(0, n, s)
-            m.mark_operands_stale(mirror_fresh=True)
-        self._has_buf = buf is not None
-        self._poll()
+            self._moments_stale = self.momentum != 0       # the momentum stays sharded
+        self._has_buf = self.momentum != 0
 
-    # ---- torch.optim.SGD-format state (checkpoint interop) ----
     def state_dict(self):
         self._state()
-        if getattr(self, "_moments_stale", False):
-            raise RuntimeError("the momentum buffer is sharded over the ranks (sharded optimiser step): call "
-                               "clip_event_amd.distributed.consolidate(model, optimizer) on EVERY rank before state_dict()")
+        self._refuse_sharded_state("momentum buffer is")
         state = {}
-        params = self.param_groups[0]["params"]
         if self._has_buf and self.momentum != 0:
-            for i, (p, o) in enumerate(zip(params, self._offset_of())):
-                state[i] = {"momentum_buffer": self.buf[o:o + p.numel()].view(p.shape).clone()}
-        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
-        group["params"] = list(range(len(params)))
-        return {"state": state, "param_groups": [group]}
+            state = {i: {"momentum_buffer": b.clone()} for i, b in enumerate(self._pieces(self.buf))}
+        return self._state_dict_of(state)
 
     def load_state_dict(self, sd):
         self._moments_stale = False          # (every rank loads the same tensors)
         params = self.param_groups[0]["params"]
-        groups = sd["param_groups"]
-        if len(groups) != 1 or len(groups[0]["params"]) != len(params):
-            raise ValueError("optimizer state does not match: expected one group of %d parameters" % len(params))
+        group = self._matching_group(sd)
         bufs = {int(k): st["momentum_buffer"] for k, st in sd["state"].items() if st.get("momentum_buffer") is not None}
         if bufs and len(bufs) != len(params):
             raise ValueError("only %d of %d parameters carry a momentum_buffer; the fused kernel keeps one buffer and one "
                              "first-step flag for all of them" % (len(bufs), len(params)))
-        for k, v in groups[0].items():
-            if k != "params":
-                self.param_groups[0][k] = v
+        self._adopt_group(group)
         self._state()
         self._has_buf = False
         if bufs and self.momentum != 0:
             with torch.no_grad():
                 self.buf.zero_()
-                for i, (p, o) in enumerate(zip(params, self._offset_of())):
-                    self.buf[o:o + p.numel()].copy_(bufs[i].reshape(-1))
+                for i, b in enumerate(self._pieces(self.buf)):
+                    b.copy_(bufs[i].reshape(b.shape))
             self._has_buf = True
 
 

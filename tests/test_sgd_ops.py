@@ -182,38 +182,3 @@ def test_sgd_step_tiles_against_fp64():
         assert bool((p16[N:] == 4.0).all())
         for (off, r, c), wt in zip(TILE_MATS, wts):
             assert _same_bits(wt, p16[off:off + r * c].view(r, c).t()), (r, c)
-
-
-@gpu
-def test_sgd_tiled_flat_and_segment_forms_are_bit_identical():
-    """The three kernel forms update through one element function: the flat kernel, the tile + segment launch and a launch of
-    segments only (the whole range cut into chunks of at most 2048) leave the same bits in p, the momentum buffer and the mirror,
-    as tests/test_model_gpu.py::test_fused_adam_in_tiles_equals_the_flat_kernel requires of Adam."""
-    cl, ptr, stream = _lib()
-    N = TILE_N
-    seg_tab = torch.tensor(TILE_SEGS, dtype=torch.int64).to(DEV)
-    all_segs = torch.tensor([(lo, min(lo + 2048, N)) for lo in range(0, N, 2048)], dtype=torch.int64).to(DEV)
-    for clip, wd, step, (name, mu, damp, nesterov) in SGD_GRID:
-        first = step == 1
-        p0, g0, b0, sumsq = _sgd_state(N, step, clip, 300 + step)
-        out = {}
-        for form in ("flat", "tiles", "segments"):
-            p, g, buf = _dev(p0, g0, b0)
-            p16 = torch.full((N,), 4.0, device=DEV, dtype=torch.bfloat16)
-            ss = torch.tensor([sumsq], device=DEV) if sumsq is not None else None
-            b = buf if mu != 0 else None
-            if form == "flat":
-                rc = _call_flat(cl, ptr, stream, p, g, b, p16, N, ss, wd, mu, damp, nesterov, first)
-            elif form == "tiles":
-                wts = [torch.empty((c, r), device=DEV, dtype=torch.bfloat16) for _, r, c in TILE_MATS]
-                tab, tiles = _job_table(TILE_MATS, p16, wts)
-                rc = _call_tiles(cl, ptr, stream, p, g, b, p16, tab, len(TILE_MATS), tiles, seg_tab, ss, wd, mu, damp, nesterov, first)
-            else:
-                rc = _call_tiles(cl, ptr, stream, p, g, b, p16, None, 0, 0, all_segs, ss, wd, mu, damp, nesterov, first)
-            torch.cuda.synchronize()
-            assert rc == 0, cl.ce_last_error()
-            out[form] = (p.clone(), buf.clone(), p16.clone())
-        for form in ("tiles", "segments"):
-            for i, what in enumerate(("masters", "momentum_buffer", "bf16 mirror")):
-                a, b = out[form][i], out["flat"][i]
-                assert torch.equal(a, b), (clip, wd, step, name, form, what, int((a != b).sum()))
