@@ -46,11 +46,31 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
     if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1]) + (red[2] + red[3]));
 }
 
+// out += sum g^2 over [table[2b], table[2b+1]) for chunk b (multiples of 4, at most 65536 long): sumsq_kernel's rounding chain per
+// chunk, and no load outside the table (the gradient slices of frozen parameters are never read)
+__global__ __launch_bounds__(256) void sumsq_segments_kernel(const float* __restrict__ g, const long* __restrict__ table,
+                                                             float* __restrict__ out) {
+    __shared__ float red[4];
+    const long lo = table[2 * blockIdx.x], hi = table[2 * blockIdx.x + 1];
+    float s = 0.f;
+    for (long i = lo + threadIdx.x * 4; i < hi; i += 1024) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+        s += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1]) + (red[2] + red[3]));
+}
+
 // One element of clip + Adam.  Every kernel of this file updates through this function, with the contraction of a * b + c into
 // fused multiply-adds spelled out, so that the flat kernel, the tile kernel and the segment kernel give the same bits.
+// `decay` != 0 is the decoupled form (AdamW): p is first scaled by 1 - decay (decay = lr * weight_decay, one multiply-add) and the
+// caller passes wd = 0, so the gradient gets no decay term.
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float coef, float wd, float b1, float b2,
-                                          float lr_bc1, float bc2_sqrt, float eps) {
+                                          float lr_bc1, float bc2_sqrt, float eps, float decay) {
 #pragma clang fp contract(off)
+    if (decay != 0.f) p = __builtin_fmaf(p, -decay, p);
     g = g * coef;
     if (wd != 0.f) g = __builtin_fmaf(p, wd, g);
     m = __builtin_fmaf(m, b1, g * (1.0f - b1));
@@ -82,19 +102,59 @@ __device__ __forceinline__ float clip_coef(const float* __restrict__ sumsq, floa
 
 // ---- update rules ----------------------------------------------------------------------------------------------------------------
 // A rule is what the three traversals below are instantiated with: NS, the number of fp32 state streams beside p and g; Args, the
-// by-value kernel argument; a device constructor that derives the per-launch scalars (the clip coefficient among them); and
-// elem(p, g, state), one element.  `state` has max(NS, 1) slots, so that a rule without state still has something to pass on.
+// by-value kernel argument; a device constructor (args, group id) that derives the per-launch scalars (the clip coefficient among
+// them); GROUPED, whether lr / weight decay come from a table of parameter groups -- the tile and the segment traversal then hand the
+// constructor the group of their workgroup (block-uniform, looked up once), otherwise 0 -- and elem(p, g, state), one element.  `state` has max(NS, 1) slots, so that a rule without state still has something to pass on.
 struct AdamRule {
     static constexpr int NS = 2;                   // m, v
+    static constexpr bool GROUPED = false;
     struct Args {
         const float* sumsq;
         float max_norm, lr, b1, b2, eps, wd, bc1, bc2_sqrt;
     };
     float coef, wd, b1, b2, lr_bc1, bc2_sqrt, eps;
-    __device__ explicit AdamRule(const Args& a)
+    __device__ AdamRule(const Args& a, int)
         : coef(clip_coef(a.sumsq, a.max_norm)), wd(a.wd), b1(a.b1), b2(a.b2), lr_bc1(a.lr / a.bc1), bc2_sqrt(a.bc2_sqrt), eps(a.eps) {}
     __device__ __forceinline__ void elem(float& p, float g, float (&s)[2]) const {
-        adam_elem(p, g, s[0], s[1], coef, wd, b1, b2, lr_bc1, bc2_sqrt, eps);
+        adam_elem(p, g, s[0], s[1], coef, wd, b1, b2, lr_bc1, bc2_sqrt, eps, 0.f);
+    }
+};
+
+// The parameter groups of a grouped launch, by value in the kernel argument; `segment_group` (device, nullable) names the group of
+// every segment, a tile job names its own in ce_transpose_job.pad_.
+constexpr int kMaxGroups = 8;
+struct group_table {
+    const int* segment_group;
+    int ngroups;
+    ce_optim_group g[kMaxGroups];
+};
+__device__ __forceinline__ ce_optim_group pick_group(const group_table& t, int id) {
+    id = id < 0 || id >= t.ngroups ? t.ngroups - 1 : id;      // block-uniform; never outside the table
+    return t.g[id];
+}
+
+struct AdamGroupRule {
+    static constexpr int NS = 2;
+    static constexpr bool GROUPED = true;
+    struct Args {
+        const float* sumsq;
+        float max_norm, b1, b2, eps, bc1, bc2_sqrt;
+        group_table groups;
+    };
+    float coef, wd, b1, b2, lr_bc1, bc2_sqrt, eps, decay;
+    __device__ AdamGroupRule(const Args& a, int group)
+        : coef(clip_coef(a.sumsq, a.max_norm)), b1(a.b1), b2(a.b2), bc2_sqrt(a.bc2_sqrt), eps(a.eps) {
+        set_group(a, group);
+    }
+    __device__ __forceinline__ void set_group(const Args& a, int group) {
+#pragma clang fp contract(off)
+        const ce_optim_group gr = pick_group(a.groups, group);
+        lr_bc1 = gr.lr / a.bc1;
+        wd = gr.decoupled ? 0.f : gr.weight_decay;
+        decay = gr.decoupled ? gr.lr * gr.weight_decay : 0.f;
+    }
+    __device__ __forceinline__ void elem(float& p, float g, float (&s)[2]) const {
+        adam_elem(p, g, s[0], s[1], coef, wd, b1, b2, lr_bc1, bc2_sqrt, eps, decay);
     }
 };
 
@@ -108,12 +168,41 @@ struct sgd_args {
 template <bool MOM>
 struct SgdRule {
     static constexpr int NS = MOM ? 1 : 0;         // the momentum buffer
+    static constexpr bool GROUPED = false;
     using Args = sgd_args;
     float coef, wd, mu, one_minus_damp, lr;
     bool first, nesterov;
-    __device__ explicit SgdRule(const Args& a)
+    __device__ SgdRule(const Args& a, int)
         : coef(clip_coef(a.sumsq, a.max_norm)), wd(a.wd), mu(MOM ? a.mu : 0.f), one_minus_damp(a.one_minus_damp), lr(a.lr),
           first(a.first != 0), nesterov(a.nesterov != 0) {}
+    __device__ __forceinline__ void elem(float& p, float g, float (&s)[1]) const {
+        sgd_elem(p, g, s[0], coef, wd, mu, one_minus_damp, lr, first, nesterov);
+    }
+};
+
+struct sgd_group_args {
+    const float* sumsq;
+    float max_norm, mu, one_minus_damp;
+    int first, nesterov;
+    group_table groups;
+};
+template <bool MOM>
+struct SgdGroupRule {
+    static constexpr int NS = MOM ? 1 : 0;
+    static constexpr bool GROUPED = true;
+    using Args = sgd_group_args;
+    float coef, wd, mu, one_minus_damp, lr;
+    bool first, nesterov;
+    __device__ SgdGroupRule(const Args& a, int group)
+        : coef(clip_coef(a.sumsq, a.max_norm)), mu(MOM ? a.mu : 0.f), one_minus_damp(a.one_minus_damp), first(a.first != 0),
+          nesterov(a.nesterov != 0) {
+        set_group(a, group);
+    }
+    __device__ __forceinline__ void set_group(const Args& a, int group) {
+        const ce_optim_group gr = pick_group(a.groups, group);
+        lr = gr.lr;
+        wd = gr.weight_decay;
+    }
     __device__ __forceinline__ void elem(float& p, float g, float (&s)[1]) const {
         sgd_elem(p, g, s[0], coef, wd, mu, one_minus_damp, lr, first, nesterov);
     }
@@ -164,7 +253,7 @@ template <class Rule>
 __global__ __launch_bounds__(256) void optim_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
                                                          float* __restrict__ s1, bf16_t* __restrict__ p16, long n,
                                                          typename Rule::Args a) {
-    const Rule rule(a);
+    const Rule rule(a, 0);
     float* const st[2] = {s0, s1};
     const long stride = gridDim.x * 2048L;
     for (long i0 = blockIdx.x * 2048L + threadIdx.x * 4; i0 < n; i0 += stride) {
@@ -297,9 +386,10 @@ __global__ __launch_bounds__(256) void optim_tiles_kernel(float* __restrict__ p,
                                                           float* __restrict__ s1, bf16_t* __restrict__ p16,
                                                           const ce_transpose_job* __restrict__ jobs, int njobs, typename Rule::Args a) {
     __shared__ bf16_t tile[64][66];
-    const Rule rule(a);
+    Rule rule(a, 0);
     float* const st[2] = {s0, s1};
     const tile_at t = find_tile(jobs, njobs);
+    if constexpr (Rule::GROUPED) rule.set_group(a, t.job.pad_);
     const long off = reinterpret_cast<const bf16_t*>(t.job.src) - p16;
     // 64 rows x 16 four-element chunks; all loads of a thread (Adam: sixteen) in flight before the first use
     f32x4 pv[4] = {}, gv[4] = {}, sv[4][kSlots<Rule>] = {};
@@ -338,7 +428,9 @@ template <class Rule>
 __global__ __launch_bounds__(256) void optim_segments_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
                                                              float* __restrict__ s1, bf16_t* __restrict__ p16,
                                                              const long* __restrict__ table, typename Rule::Args a) {
-    const Rule rule(a);
+    int group = 0;
+    if constexpr (Rule::GROUPED) group = a.groups.segment_group ? a.groups.segment_group[blockIdx.x] : 0;
+    const Rule rule(a, group);
     float* const st[2] = {s0, s1};
     const long lo = table[2 * blockIdx.x], hi = table[2 * blockIdx.x + 1];
     f32x4 pv[2] = {}, gv[2] = {}, sv[2][kSlots<Rule>] = {};
@@ -375,6 +467,18 @@ float adam_bc2_sqrt(float beta2, int step) { return (float)sqrt(1.0 - pow((doubl
 
 AdamRule::Args adam_args(const float* sumsq, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step) {
     return {sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, adam_bc1(beta1, step), adam_bc2_sqrt(beta2, step)};
+}
+
+// the by-value group table of a grouped launch; 0 or -EINVAL with a message
+int fill_groups(const char* who, group_table& t, const ce_optim_group* groups, int ngroups, const int* segment_group, bool decoupled_ok) {
+    CE_CHECK_ARG(groups && ngroups >= 1 && ngroups <= kMaxGroups, "%s: need 1..%d groups (got %d, table %s)", who, kMaxGroups, ngroups,
+                 groups ? "given" : "NULL");
+    t.segment_group = segment_group;
+    t.ngroups = ngroups;
+    for (int i = 0; i < kMaxGroups; ++i) t.g[i] = groups[i < ngroups ? i : ngroups - 1];
+    for (int i = 0; i < ngroups; ++i)
+        CE_CHECK_ARG(decoupled_ok || !groups[i].decoupled, "%s: group %d is decoupled; decoupled weight decay is Adam's (AdamW)", who, i);
+    return 0;
 }
 
 // ---- launchers: one per form, for every rule (arguments are checked by the callers) ------------------------------------------------
@@ -472,6 +576,43 @@ extern "C" int ce_sgd_step_tiles(float* p, const float* g, float* buf, void* p_b
         launch_tiles<SgdRule<true>>(p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
     else
         launch_tiles<SgdRule<false>>(p, g, nullptr, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_sumsq_segments(const float* g, const long* table_device, int nchunks, float* out, void* stream) {
+    CE_CHECK_ARG(g && table_device && out && nchunks > 0, "ce_sumsq_segments: empty");
+    hipLaunchKernelGGL(sumsq_segments_kernel, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, g, table_device, out);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_adam_step_groups(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
+                                   int njobs, int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
+                                   const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float beta1,
+                                   float beta2, float eps, int step, void* stream) {
+    CE_CHECK_ARG(p && g && m && v && p_bf16 && step >= 1, "ce_adam_step_groups: null buffer or step < 1");
+    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "ce_adam_step_groups: nothing to update");
+    AdamGroupRule::Args a = {sumsq, max_norm, beta1, beta2, eps, adam_bc1(beta1, step), adam_bc2_sqrt(beta2, step), {}};
+    if (int rc = fill_groups("ce_adam_step_groups", a.groups, groups, ngroups, segment_group, true)) return rc;
+    launch_tiles<AdamGroupRule>(p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_sgd_step_groups(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                                  int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
+                                  const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float momentum,
+                                  float dampening, int nesterov, int first_step, void* stream) {
+    if (int rc = sgd_check("ce_sgd_step_groups", buf, momentum, dampening, nesterov)) return rc;
+    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "ce_sgd_step_groups: nothing to update");
+    CE_CHECK_ARG(p && g && p_bf16, "ce_sgd_step_groups: null buffer");
+    sgd_group_args a = {sumsq, max_norm, momentum, 1.0f - dampening, first_step != 0, nesterov != 0, {}};
+    if (int rc = fill_groups("ce_sgd_step_groups", a.groups, groups, ngroups, segment_group, false)) return rc;
+    if (momentum > 0.f)
+        launch_tiles<SgdGroupRule<true>>(p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
+    else
+        launch_tiles<SgdGroupRule<false>>(p, g, nullptr, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
     CE_LAUNCH_CHECK();
     return 0;
 }

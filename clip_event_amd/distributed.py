@@ -288,6 +288,9 @@ class GradSync:
         if sharded and is_dist() and world_size() > 1:
             if getattr(model, "_ranges", None) is None and hasattr(model, "_ready"):
                 model._ready()                   # the plan is cut from the flat layout
+            if any(not p.requires_grad for p in getattr(model, "parameters", lambda: [])()):
+                raise NotImplementedError("the sharded optimiser step (CE_SHARDED_ADAM / sharded=True) does not take frozen "
+                                          "parameters: every shard is updated whole")
             self.plan = ShardPlan(model, self.pieces, world_size())
         model.grad_sync = self            # callable: (model, tower, upto_layer=None); also queried for layer_cuts
         # With a process group live, RCCL's channel kernels will sit on some CUs while the backward runs: hand the persistent
@@ -340,6 +343,12 @@ class GradSync:
         if not active() or self.pieces < 2 or tower in self.done or not self._is_last_pass(tower):
             return []
         return piece_cuts(layers, self.pieces)
+
+    def _locked(self, name: str) -> bool:
+        """A tower without a trainable parameter (model.trainable_plan): no backward writes its range, and nobody reads it --
+        it is neither waited for nor exchanged."""
+        plan_of = getattr(self.model, "trainable_plan", None)
+        return plan_of is not None and plan_of().locked[name]
 
     def _reduce_range(self, a: int, b: int, async_op: bool):
         if b <= a:
@@ -422,7 +431,7 @@ class GradSync:
             return
         cuda = self.model._flat_grad.is_cuda
         for name in self.TOWERS:
-            if name not in self.done:
+            if name not in self.done and not self._locked(name):
                 if cuda:
                     self._join_fences(name)
                 a, b = self.model._ranges[name]

@@ -224,22 +224,30 @@ def micro_batched_backward(model, criterion, image, text, labels_per_image, labe
         hi = min(lo + mb, B)
         chunks.append((lo, hi, image[lo:hi], attach_lengths(text[lo * K:hi * K], lens[lo * K:hi * K])))
     gs = grad_sync if grad_sync is not None else getattr(model, "grad_sync", None)
-    if gs is not None and hasattr(gs, "expect_passes"):
-        gs.expect_passes({"visual": len(chunks), "text": len(chunks)})
+    # a locked tower (model.trainable_plan: nothing in it trains) is encoded once, in pass 1, and has no backward
+    locked = model.trainable_plan().locked
+    live = [t for t in ("visual", "text") if not locked[t]]
+    if gs is not None and hasattr(gs, "expect_passes") and live:
+        gs.expect_passes({t: len(chunks) for t in live})
     # every chunk, the shorter last one included, runs in buffers leased for a full chunk (the pool is keyed by byte count)
     model._lease_batch = {"vision": mb, "text": mb * K}
     try:
         with torch.no_grad():
             feats = [model.encode_both(img_c, txt_c) for _, _, img_c, txt_c in chunks]
-        fi = torch.cat([f[0] for f in feats], dim=0).requires_grad_()
-        ft = torch.cat([f[1] for f in feats], dim=0).requires_grad_()
+        fi = torch.cat([f[0] for f in feats], dim=0).requires_grad_(not locked["visual"])
+        ft = torch.cat([f[1] for f in feats], dim=0).requires_grad_(not locked["text"])
         del feats
         loss_dict = _contrastive_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch)
         _sum_losses(loss_dict, check_finite).backward()        # fi.grad, ft.grad, logit_scale.grad; no tower node, no exchange
-        for lo, hi, img_c, txt_c in chunks:
-            fi_c, ft_c = model.encode_both(img_c, txt_c)
-            torch.autograd.backward([fi_c, ft_c], [fi.grad[lo:hi], ft.grad[lo * K:hi * K]])
-            del fi_c, ft_c
+        for lo, hi, img_c, txt_c in (chunks if live else []):
+            if len(live) == 2:
+                outs, grads = model.encode_both(img_c, txt_c), [fi.grad[lo:hi], ft.grad[lo * K:hi * K]]
+            elif live[0] == "visual":
+                outs, grads = [model.encode_image(img_c)], [fi.grad[lo:hi]]
+            else:
+                outs, grads = [model.encode_text(txt_c)], [ft.grad[lo * K:hi * K]]
+            torch.autograd.backward(list(outs), grads)
+            del outs
     finally:
         model._lease_batch = None
     return loss_dict

@@ -67,11 +67,27 @@ def _tower_backward(model, desc, tower: str, batch: int, rows: int, cu, x0, leas
     """Tower backward, cut into layer ranges when a data-parallel gradient exchange is attached: after every
     range the gradients of the blocks done so far are handed to ``model.grad_sync`` (they form a contiguous
     prefix of the tower's range in the flat gradient buffer, model._prepare), so their all-reduce overlaps the
-    remaining blocks."""
+    remaining blocks.
+
+    The ranges end at the tower's ``stop_layer`` (model.trainable_plan: the lowest block that owns a trainable parameter), which is
+    returned: with a stop above 0 no kernel runs for the blocks below it, ``dx`` is not the gradient of the tower's input, and the
+    caller has nothing left to do on the input side."""
     cl, s = lib(), stream()
     layers = desc.layers
+    stop = model.trainable_plan().stop_layer[tower]
     cuts = model.grad_sync.layer_cuts(tower, layers) if (model.grad_sync is not None and
                                                            hasattr(model.grad_sync, "layer_cuts")) else []
+    cuts = [c for c in cuts if c > stop]        # hand-overs below the stop: nothing is computed there
+    # Block l's ln_1 backward also sums the c_proj bias gradient of block l - 1 (tower.cpp: fused into that kernel).  Below the stop
+    # that tensor is frozen: the descriptor gets NULL there, as block 0 has for "no block below", and the kernel skips the sum.
+    cut = getattr(desc, "_cut", 0)
+    if cut != stop:
+        prefix = "visual.transformer." if tower == "visual" else "transformer."
+        if 0 < cut < layers:
+            desc.blocks[cut - 1].g_b_proj = model._gview(f"{prefix}resblocks.{cut - 1}.mlp.c_proj.bias").data_ptr()
+        if 0 < stop < layers:
+            desc.blocks[stop - 1].g_b_proj = None
+        desc._cut = stop
     model.wait_transposes()       # the blocks' W^T copies may still be in flight on the auxiliary stream (model.refresh_operands)
     # the step's first backward pass of this tower writes the block weight gradients instead of accumulating them
     # (model.zero_grad_first_touch); the flag is consumed here, so later passes of the same step accumulate
@@ -80,13 +96,14 @@ def _tower_backward(model, desc, tower: str, batch: int, rows: int, cu, x0, leas
     if desc.wgrad_overwrite:
         pending.discard(tower)
     hi = layers - 1
-    for lo in list(cuts) + [0]:
+    for lo in (list(cuts) + [stop] if stop < layers else []):
         check(cl.ce_tower_backward_range(ctypes.byref(desc), c_int(batch), c_int(rows), ptr(cu), ptr(x0), ptr(lease.buf),
                                          ptr(dx), ptr(sel), ptr(dx_sel), c_int(hi), c_int(lo), s),
               f"ce_tower_backward_range({tower})")
-        if lo > 0:
+        if lo > stop:
             model.grad_sync(model, tower, upto_layer=lo)
         hi = lo - 1
+    return stop
 
 
 class TextPacking:
@@ -344,11 +361,17 @@ class EncodeImageFn(torch.autograd.Function):
                 dx = _empty((M, D), sdt, dev)
                 check(cl.ce_cast_scaled(ptr(dxn), c_int(L.T_F32), ptr(dx), c_int(ST), ptr(gs), c_int(0), c_long(M * D), s),
                       "ce_cast_scaled")
-            _tower_backward(model, model._vdesc, "visual", B, M, None, x0, lease, dx, None, None)
+            stop = _tower_backward(model, model._vdesc, "visual", B, M, None, x0, lease, dx, None, None)
         else:
             dx = _empty((M, D), sdt, dev)
-            _tower_backward(model, model._vdesc, "visual", B, M, None, x0, lease, dx, rows, dxn)
+            stop = _tower_backward(model, model._vdesc, "visual", B, M, None, x0, lease, dx, rows, dxn)
         lease.release()
+        if stop > 0:      # everything below block `stop` is frozen, the input side included: ln_pre, the embedding sums and the
+            #               conv1 weight gradient have no reader
+            if model.grad_sync is not None:
+                model.grad_sync(model, "visual")
+            _publish_to_main(ctx)
+            return None, None, None, None, None
         # ln_pre: x0 = LN(xpre); its dy is the gradient stream
         dxpre = _empty((M, D), torch.float32, dev)
         check(cl.ce_layernorm_bwd_t(ptr(dx), c_int(ST), c_long(D), ptr(xpre), c_int(L.T_F32), c_long(D), None, ptr(mean_pre),
@@ -461,8 +484,13 @@ class EncodeTextFn(torch.autograd.Function):
                                     None, c_int(n), c_int(D), s), "ce_layernorm_bwd(ln_final)")
         gs = _grad_scale(model, model._tdesc, dxn)
         dx = _empty((M, D), sdt, dev)
-        _tower_backward(model, model._tdesc, "text", n, M, pk.cu, x0, lease, dx, rows, dxn)
+        stop = _tower_backward(model, model._tdesc, "text", n, M, pk.cu, x0, lease, dx, rows, dxn)
         lease.release()
+        if stop > 0:      # as in EncodeImageFn.backward: no stream cast, no positional sum, no token-embedding scatter
+            if model.grad_sync is not None:
+                model.grad_sync(model, "text")
+            _publish_to_main(ctx)
+            return None, None, None, None
         if sdt != torch.float32:      # the embedding gradients below take the fp32 gradient in true units
             dx32 = _empty((M, D), torch.float32, dev)
             check(cl.ce_cast_scaled(ptr(dx), c_int(ST), ptr(dx32), c_int(L.T_F32), ptr(gs), c_int(1), c_long(M * D), s),

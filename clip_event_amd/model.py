@@ -181,6 +181,87 @@ class Stream16Saturation(FloatingPointError):
 _GEMM_SUFFIXES = ("attn.in_proj_weight", "attn.out_proj.weight", "mlp.c_fc.weight", "mlp.c_proj.weight")
 
 
+# ---- partial fine-tuning: what is trainable, as tables over the flat layout ---------------------------------------------------
+TOWERS = ("visual", "text")
+_INPUT_SIDE = {"visual": ("visual.ln_pre.", "visual.conv1.", "visual.positional_embedding", "visual.class_embedding"),
+               "text": ("token_embedding.", "positional_embedding")}
+SEGMENT, CHUNK = 2048, 1 << 16       # longest range of one workgroup: the optimiser's segment kernel, the table-driven gradient norm
+
+
+def tower_of(name: str) -> str:
+    """'visual', 'text' or 'head' (``logit_scale``): the range of the flat layout a parameter lives in."""
+    if name.startswith("visual."):
+        return "visual"
+    return "text" if name.startswith(("transformer.", "token_embedding.", "positional_embedding", "ln_final.", "text_projection")) else "head"
+
+
+def block_of(name: str):
+    """Index of the residual block a parameter belongs to, or None."""
+    parts = name.split(".")
+    return int(parts[parts.index("resblocks") + 1]) if "resblocks" in parts else None
+
+
+def trainable_tables(offsets, shapes, flags, group_of=None, tile_names=()):
+    """What a partially trainable model updates and runs, from names alone -- pure host arithmetic (no tensors, no GPU).
+
+    ``offsets`` / ``shapes`` / ``flags``: flat offset, shape and ``requires_grad`` of every parameter name; ``group_of``: the
+    parameter group of a name (missing: 0); ``tile_names``: the matrices that the optimiser updates in 64 x 64 tiles (in the order
+    of the model's transpose-job table), everything else goes through segments.  Returns a dict:
+
+      ``locked[tower]``      every parameter of the tower is frozen: it runs forward-only, without a stash;
+      ``stop_layer[tower]``  the lowest block that owns a trainable parameter -- the backward ends there -- 0 when an input-side
+                             parameter is trainable, and the number of blocks when only the output side (or nothing) is;
+      ``tiles``              [(name, group)] of the trainable ``tile_names``;
+      ``segments`` / ``segment_group``   [lo, hi) element ranges of at most 2048 elements covering every other trainable tensor,
+                             and the group of each;
+      ``chunks``             [lo, hi) ranges of at most 65536 elements covering every trainable tensor (the gradient norm).
+
+    A range never crosses a tensor: the padding between tensors (offsets are multiples of 64) belongs to no range, except that the
+    end of a tensor is rounded up to a multiple of 4 (the kernels move 16 bytes) -- up to three elements of its OWN padding, which
+    hold zeros in every flat buffer and stay zero under every update rule.  A frozen tensor is in no table."""
+    group_of = group_of or {}
+    names = sorted(offsets, key=lambda n: offsets[n])
+    numel = {n: int(np.prod(shapes[n], dtype=np.int64)) if len(shapes[n]) else 1 for n in names}
+    layers = {t: 1 + max([block_of(n) for n in names if tower_of(n) == t and block_of(n) is not None], default=-1) for t in TOWERS}
+    locked, stop = {}, {}
+    for t in TOWERS:
+        live = [n for n in names if tower_of(n) == t and flags[n]]
+        locked[t] = not live
+        if any(n.startswith(_INPUT_SIDE[t]) for n in live):
+            stop[t] = 0
+        else:
+            stop[t] = min([block_of(n) for n in live if block_of(n) is not None], default=layers[t])
+    tile_set = set(tile_names)
+    tiles = [(n, int(group_of.get(n, 0))) for n in tile_names if flags[n]]
+    segments, segment_group, chunks = [], [], []
+    for n in names:
+        if not flags[n]:
+            continue
+        lo, hi = offsets[n], offsets[n] + (numel[n] + 3) // 4 * 4
+        for c in range(lo, hi, CHUNK):
+            chunks.append((c, min(c + CHUNK, hi)))
+        if n not in tile_set:
+            for c in range(lo, hi, SEGMENT):
+                segments.append((c, min(c + SEGMENT, hi)))
+                segment_group.append(int(group_of.get(n, 0)))
+    return {"locked": locked, "stop_layer": stop, "tiles": tiles, "segments": segments, "segment_group": segment_group,
+            "chunks": chunks}
+
+
+class TrainablePlan:
+    """``CLIP.trainable_plan()``: ``trainable_tables`` of the model's current ``requires_grad`` flags, and -- once the model has
+    its flat buffers -- the same tables in device memory, in the forms the kernels take: ``tjobs`` (transpose-job table, group in
+    ``pad_``; ``(tensor, njobs, tiles)``), ``segments`` ([n, 2] int64), ``segment_group`` ([n] int32), ``chunks`` ([n, 2] int64).
+    ``plain``: nothing is frozen."""
+
+    def __init__(self, flags, tables):
+        self.flags = flags
+        self.plain = all(flags)
+        self.locked, self.stop_layer = tables["locked"], tables["stop_layer"]
+        self.host = tables
+        self.tjobs = self.segments = self.segment_group = self.chunks = None
+
+
 class CLIP(nn.Module):
     """``CLIP`` of model_clip.py:266-552 (ViT vision tower)."""
 
@@ -239,7 +320,7 @@ class CLIP(nn.Module):
     _RUNTIME = ("_flat", "_flat_grad", "_flat16", "_offsets", "_ranges", "_layer_end", "_pmap", "_pool", "_trigger",
                 "_versions", "_w16", "_w16t", "_kp", "_kp_real", "_conv_pad", "_conv_gpad", "_cast_list", "_tjobs",
                 "_tjobs_bwd", "_adam_tiles_ok", "_wt_fresh", "_wt_event", "_aux_stream", "_mirror_fresh", "_mirror_versions", "_vdesc", "_tdesc", "_vblocks", "_tblocks",
-                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch", "_lease_batch")
+                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch", "_lease_batch", "_plist", "_plans")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -383,10 +464,11 @@ class CLIP(nn.Module):
         ``p.grad`` tensor (autograd accumulated into a parameter before our backward ran, e.g.
         ``logit_scale``) is copied into its slice."""
         base = self._flat_grad.data_ptr()
-        todo = [(n, p) for n, p in self._pmap.items() if p.grad is None or p.grad.data_ptr() != base + self._offsets[n] * 4]
+        live = [(n, p) for n, p in self._pmap.items() if p.requires_grad]      # a frozen parameter keeps .grad None (torch's contract)
+        todo = [(n, p) for n, p in live if p.grad is None or p.grad.data_ptr() != base + self._offsets[n] * 4]
         if not todo:
             return
-        if all(p.grad is None for _, p in todo) and len(todo) == len(self._pmap):
+        if all(p.grad is None for _, p in todo) and len(todo) == len(live) == len(self._pmap):
             self._flat_grad.zero_()
             for n, p in todo:
                 p.grad = self._gview(n)
@@ -468,9 +550,10 @@ class CLIP(nn.Module):
         pending = getattr(self, "_first_touch", None)
         if not pending:
             return
-        for n in self._pmap:
-            if self._is_block_weight(n) and (("visual" in pending and n.startswith("visual.")) or
-                                             ("text" in pending and not n.startswith("visual."))):
+        for n, p in self._pmap.items():
+            # (a frozen weight's gradient is in no table of the optimiser: nothing consumes it, nothing to settle)
+            if p.requires_grad and self._is_block_weight(n) and (("visual" in pending and n.startswith("visual.")) or
+                                                                 ("text" in pending and not n.startswith("visual."))):
                 self._gview(n).zero_()
         self._first_touch = set()
 
@@ -483,9 +566,78 @@ class CLIP(nn.Module):
             super().zero_grad(set_to_none=set_to_none)
 
     def _attach_grads_fast(self):
+        base = self._flat_grad.data_ptr()
         for n, p in self._pmap.items():
-            if p.grad is None or p.grad.data_ptr() != self._flat_grad.data_ptr() + self._offsets[n] * 4:
+            if not p.requires_grad:
+                if p.grad is not None and p.grad.data_ptr() == base + self._offsets[n] * 4:
+                    p.grad = None         # frozen since it was attached: its slice is still written, and nothing consumes it
+            elif p.grad is None or p.grad.data_ptr() != base + self._offsets[n] * 4:
                 p.grad = self._gview(n)
+
+    # ---- partial fine-tuning ---------------------------------------------------------------------------------------
+    def _flags(self):
+        """``requires_grad`` of every parameter, in ``named_parameters()`` order."""
+        ps = self.__dict__.get("_plist")
+        if ps is None:
+            ps = self.__dict__["_plist"] = [p for _, p in self.named_parameters()]
+        return tuple(p.requires_grad for p in ps)
+
+    def trainable_plan(self, group_of=None, tiles: bool = True) -> TrainablePlan:
+        """What the current ``requires_grad`` flags leave to train (``TrainablePlan``): which tower is locked, where each tower's
+        backward may stop, and the optimiser's tables.  ``group_of`` (name -> parameter group, from the optimiser) and ``tiles``
+        (block weights in 64 x 64 tiles rather than in segments) shape the tables only.  Cached; rebuilt when a flag, the groups
+        or the flat buffers change."""
+        flags = self._flags()
+        flat = self._flat if self._flat is not None and self._flat_ok() else None
+        key = (flags, tuple(sorted(group_of.items())) if group_of else None, bool(tiles), None if flat is None else flat.data_ptr())
+        plans = self.__dict__.setdefault("_plans", {})
+        plan = plans.get(key)
+        if plan is not None:
+            return plan
+        named = list(self.named_parameters())
+        fl = {n: f for (n, _), f in zip(named, flags)}
+        if flat is None:           # no flat layout yet (a model on the host): towers only, the tables come with the layout
+            offsets, off = {}, 0
+            for n, p in named:
+                offsets[n] = off
+                off += (p.numel() + 63) // 64 * 64
+            tile_names = []
+        else:
+            offsets = self._offsets
+            tile_names = [n for n in self._pmap if n.endswith(_GEMM_SUFFIXES)] if tiles else []
+        tables = trainable_tables(offsets, {n: tuple(p.shape) for n, p in named}, fl, group_of, tile_names)
+        if flat is None:
+            tables = {"locked": tables["locked"], "stop_layer": tables["stop_layer"]}
+        plan = TrainablePlan(flags, tables)
+        if flat is not None:
+            dev = flat.device
+            plan.tjobs = self._job_table([n for n, _ in tables["tiles"]], [g for _, g in tables["tiles"]])
+            plan.segments = torch.tensor(tables["segments"], dtype=torch.int64).reshape(-1, 2).to(dev)
+            plan.segment_group = torch.tensor(tables["segment_group"], dtype=torch.int32).to(dev)
+            plan.chunks = torch.tensor(tables["chunks"], dtype=torch.int64).reshape(-1, 2).to(dev)
+        if len(plans) >= 8:
+            plans.clear()
+        plans[key] = plan
+        return plan
+
+    def _lock_tower(self, tower: str, unlocked_layers: int):
+        layers = (self.visual.transformer if tower == "visual" else self.transformer).layers
+        n_open = max(0, min(int(unlocked_layers), layers))
+        out_side = ("visual.ln_post.", "visual.proj") if tower == "visual" else ("ln_final.", "text_projection")
+        for n, p in self.named_parameters():
+            if tower_of(n) != tower:
+                continue
+            b = block_of(n)
+            p.requires_grad_(n_open > 0 and ((b is not None and b >= layers - n_open) or n.startswith(out_side)))
+
+    def lock_image_tower(self, unlocked_layers: int = 0):
+        """Freeze the image tower except its top ``unlocked_layers`` blocks and, with any block open, ``ln_post`` + ``proj``
+        (open_clip's spelling; only ``requires_grad`` flags are set).  Fully locked, the tower runs forward-only (LiT)."""
+        self._lock_tower("visual", unlocked_layers)
+
+    def lock_text_tower(self, unlocked_layers: int = 0):
+        """The same for the text tower; the output side is ``ln_final`` + ``text_projection``."""
+        self._lock_tower("text", unlocked_layers)
 
     # ---- fp16 residual / gradient stream: saturation telemetry ------------------------------------------------
     def stream16_saturation(self, reset: bool = False):
@@ -557,16 +709,7 @@ class CLIP(nn.Module):
             self._w16t[n] = torch.empty(p.shape[1], p.shape[0], dtype=torch.bfloat16, device=dev)  # [E, width]
         self._cast_list = gemm_names + ["visual.conv1.weight", "visual.proj", "text_projection"]
         # one-launch transposition table for every W^T copy
-        from ._lib import TransposeJob
-        def table(names):
-            jobs = (TransposeJob * len(names))()
-            tiles = 0
-            for i, n in enumerate(names):
-                src, dst = self._w16[n], self._w16t[n]
-                jobs[i].src, jobs[i].dst = src.data_ptr(), dst.data_ptr()
-                jobs[i].rows, jobs[i].cols, jobs[i].tile_start = src.shape[0], src.shape[1], tiles
-                tiles += ((src.shape[0] + 63) // 64) * ((src.shape[1] + 63) // 64)
-            return torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev), len(names), tiles
+        table = self._job_table
 
         # two tables: the feature projections' W^T are FORWARD operands; the blocks' W^T are read by the backward only
         # (input-gradient GEMMs), so their rebuild can run beside the next forward (refresh_operands)
@@ -613,6 +756,22 @@ class CLIP(nn.Module):
         lib().ce_tower_workspace_bytes.restype = ctypes.c_size_t
         self._w8 = None
         self._fp8_fresh = False
+
+    def _job_table(self, names, groups=None):
+        """``(device table, njobs, tiles)``: one ``ce_transpose_job`` per name (bf16 operand copy -> its W^T copy); ``groups``
+        (optional, one per name) goes into ``pad_``, where the grouped optimiser step reads the job's parameter group."""
+        from ._lib import TransposeJob
+        jobs = (TransposeJob * len(names))()
+        tiles = 0
+        for i, n in enumerate(names):
+            src, dst = self._w16[n], self._w16t[n]
+            jobs[i].src, jobs[i].dst = src.data_ptr(), dst.data_ptr()
+            jobs[i].rows, jobs[i].cols, jobs[i].tile_start = src.shape[0], src.shape[1], tiles
+            jobs[i].pad_ = 0 if groups is None else int(groups[i])
+            tiles += ((src.shape[0] + 63) // 64) * ((src.shape[1] + 63) // 64)
+        if not len(names):
+            return None, 0, 0
+        return torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(self._flat.device), len(names), tiles
 
     def _build_fp8_tables(self):
         """e4m3 copies of the blocks' GEMM weights, one fp32 scale per row: straight [out,in] (scale per output
@@ -736,7 +895,7 @@ class CLIP(nn.Module):
         self.refresh_operands()
 
     # ---- encoders -------------------------------------------------------------------------
-    def _note_pass(self, tower: str):
+    def _note_pass(self, tower: str, locked: bool = False):
         """Bookkeeping before a tower forward: refuse torch's DistributedDataParallel (its reducer waits for
         per-parameter autograd hooks that the HIP backward never fires -- an "unchanged" train.py would die on the
         second iteration inside the reducer with an unrelated message) and tell the gradient exchange that one more
@@ -748,14 +907,18 @@ class CLIP(nn.Module):
                 "are written by the HIP backward as side effects, so DDP's autograd hooks never fire.  Wrap the model "
                 "with clip_event_amd.distributed.DistributedDataParallel(model, device_ids=[gpu]) instead (same call "
                 "site, train.py:222-225; see INTEGRATION.md).")
-        if self.grad_sync is not None and torch.is_grad_enabled() and hasattr(self.grad_sync, "note_forward"):
+        if self.grad_sync is not None and torch.is_grad_enabled() and not locked and hasattr(self.grad_sync, "note_forward"):
             self.grad_sync.note_forward(tower)
 
     def encode_image(self, image, use_grid: bool = False):
         """model_clip.py:390-391 -> VisualTransformer.forward (:232-263)."""
         self._ready()
-        self._note_pass("visual")
+        locked = self.trainable_plan().locked["visual"]
+        self._note_pass("visual", locked)
         from .functional import EncodeImageFn
+        if locked:       # nothing in the tower trains: forward-only even with grad mode on -- no stash, no autograd node
+            with torch.no_grad():
+                return EncodeImageFn.apply(image, self._trigger, self, bool(use_grid), True)
         # decided HERE: inside autograd.Function.forward grad mode is always off.  Without grad the tower keeps no stash.
         return EncodeImageFn.apply(image, self._trigger, self, bool(use_grid), not torch.is_grad_enabled())
 
@@ -763,10 +926,14 @@ class CLIP(nn.Module):
         """model_clip.py:398-417.  ``lengths`` (optional, host integers: tokens up to and including each caption's EOT) spares
         the text tower its one device read-back per new token tensor; ``functional.attach_lengths`` tags a tensor instead."""
         self._ready()
-        self._note_pass("text")
+        locked = self.trainable_plan().locked["text"]
+        self._note_pass("text", locked)
         from .functional import EncodeTextFn, attach_lengths
         if lengths is not None:
             attach_lengths(text, lengths)
+        if locked:       # as encode_image
+            with torch.no_grad():
+                return EncodeTextFn.apply(text, self._trigger, self, True)
         return EncodeTextFn.apply(text, self._trigger, self, not torch.is_grad_enabled())
 
     def encode_both(self, image, text, use_grid: bool = False):

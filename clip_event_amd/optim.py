@@ -7,6 +7,7 @@ from __future__ import annotations
 import math
 import os
 from bisect import bisect_right
+import ctypes
 from ctypes import c_float, c_int, c_long
 from typing import List, Sequence
 
@@ -14,29 +15,156 @@ import torch
 
 from ._lib import check, lib, ptr, stream
 
+MAX_GROUPS = 8
+
+
+class OptimGroup(ctypes.Structure):
+    """``ce_optim_group`` of include/clip_event_hip.h."""
+    _fields_ = [("lr", c_float), ("weight_decay", c_float), ("decoupled", c_int), ("pad_", c_int)]
+
 
 class _FusedFlatOptimizer(torch.optim.Optimizer):
     """What the fused optimisers share: one param group over the model's flat buffers, the gradient zero-fill, the device
     scalar of the gradient norm, the whole of ``step()`` and the frames of ``state_dict()`` / ``load_state_dict()``.
 
-    A subclass names its two entry points (``_flat_op(p, g, *state, p16, n, *args, stream)`` on a range of the flat buffers,
-    ``_tiles_op(p, g, *state, p16, jobs, njobs, tiles, segments, nsegments, *args, stream)``) and its torch counterpart
-    (``_stock``), and provides ``_state()`` (allocate the flat state buffers and ``sumsq``), ``_step_args(sumsq)`` (the state
-    buffers the kernels take and the rule's scalar arguments) and ``_after_step(sharded)`` (what to note once the step is
-    launched)."""
+    A model that can describe its trainable ranges (``trainable_plan``, model.CLIP) may have frozen parameters and parameter
+    ``groups`` (a list of dicts: ``"params"`` = parameter names or Parameters, plus ``lr`` / ``weight_decay`` / -- Adam --
+    ``decoupled``; at most 8; what is named nowhere forms the first group with the constructor's values).  ``step()`` then takes
+    the grouped path: the gradient norm over the plan's chunk table, the update over its tile and segment tables with each
+    group's scalars; a frozen range is in no table.  With nothing frozen, one group and no decoupled decay it is the plain path,
+    launch for launch what it was before groups existed.  Every group is an entry of ``param_groups`` that holds the group's
+    TRAINABLE parameters; a parameter frozen or unfrozen between steps leaves or joins its group at the next ``step()`` (an
+    unfrozen one starts with zero moments, under the one shared step count).
 
-    def __init__(self, model, max_norm, defaults):
+    A subclass names its entry points (``_flat_op(p, g, *state, p16, n, *args, stream)`` on a range of the flat buffers,
+    ``_tiles_op(p, g, *state, p16, jobs, njobs, tiles, segments, nsegments, *args, stream)``, ``_groups_op``: the same with
+    ``segment_group`` behind ``nsegments`` and ``groups, ngroups`` in place of lr / weight decay) and its torch counterpart
+    (``_stock``), and provides ``_state()`` (allocate the flat state buffers and ``sumsq``), ``_step_args(sumsq)`` /
+    ``_group_args(sumsq)`` (the state buffers the kernels take and the rule's scalar arguments, without lr / weight decay in the
+    grouped form) and ``_after_step(sharded)`` (what to note once the step is launched)."""
+
+    _GROUP_KEYS = ("lr", "weight_decay")       # what a group may set for itself; everything else is shared
+
+    def __init__(self, model, max_norm, defaults, groups=None):
         name = type(self).__name__
-        frozen = [n for n, p in model.named_parameters() if not p.requires_grad]
-        if frozen:
-            raise NotImplementedError(f"{name} updates the whole flat parameter buffer; frozen parameters "
-                                      f"({frozen[:3]}...) need {self._stock} over the trainable ones instead")
+        named = list(model.named_parameters())
+        frozen = [n for n, p in named if not p.requires_grad]
+        if (frozen or groups) and not hasattr(model, "trainable_plan"):
+            what = f"frozen parameters ({frozen[:3]}...)" if frozen else "parameter groups"
+            raise NotImplementedError(f"{name} updates the whole flat parameter buffer; {what} need a model that describes its "
+                                      f"trainable ranges (trainable_plan), or {self._stock} over the trainable ones instead")
+        if (frozen or groups) and getattr(getattr(model, "grad_sync", None), "plan", None) is not None:
+            raise NotImplementedError(f"{name}: the sharded optimiser step (CE_SHARDED_ADAM) does not take frozen parameters or "
+                                      "parameter groups")
         self.model = model
         self.max_norm = max_norm
         self.step_count = 0                # steps taken by THIS object (Adam's bias correction; the telemetry cadence)
         self.sat_poll_every = int(os.environ.get("CE_SAT_POLL_EVERY", "16"))     # 0 = never
         self.sumsq = None
-        super().__init__([p for p in model.parameters() if p.requires_grad], defaults)
+        # group specs: (own hyper-parameters, names); names None = whatever no group lists, with the constructor's values
+        by_id, known = {id(p): n for n, p in named}, {n for n, _ in named}
+        if len(groups or ()) > MAX_GROUPS:
+            raise ValueError(f"{name}: at most {MAX_GROUPS} parameter groups (got {len(groups)})")
+        specs, owner = [], {}
+        for gi, g in enumerate(groups or ()):
+            if not isinstance(g, dict) or "params" not in g:
+                raise ValueError(f"{name}: group {gi} must be a dict with a 'params' list")
+            extra = sorted(set(g) - {"params"} - set(self._GROUP_KEYS))
+            if extra:
+                raise ValueError(f"{name}: group {gi} sets {extra}; a group may set {sorted(self._GROUP_KEYS)} only "
+                                 "(everything else is shared by all groups)")
+            for q in g["params"]:
+                n = q if isinstance(q, str) else by_id.get(id(q))
+                if n not in known:
+                    raise ValueError(f"{name}: group {gi} names {q if isinstance(q, str) else 'a tensor'!r}, which is no parameter of the model")
+                if n in owner:
+                    raise ValueError(f"{name}: parameter {n} is in groups {owner[n]} and {gi}")
+                if n in frozen:
+                    raise ValueError(f"{name}: group {gi} names the frozen parameter {n}; unfreeze it first")
+                owner[n] = gi
+            specs.append((self._group_hyper(g), {n for n, at in owner.items() if at == gi}))
+        if not specs or any(p.requires_grad and n not in owner for n, p in named):
+            specs.insert(0, ({}, None))
+        if len(specs) > MAX_GROUPS:
+            raise ValueError(f"{name}: at most {MAX_GROUPS} parameter groups (got {len(specs)} with the unnamed parameters' group)")
+        self._specs = specs
+        self._flags_seen = tuple(p.requires_grad for _, p in named)
+        if groups or frozen:
+            params = [{"params": [p for n, p in named if p.requires_grad and (n in names if names is not None else n not in owner)],
+                       **hyper} for hyper, names in specs]
+        else:
+            params = [p for _, p in named]
+        super().__init__(params, defaults)
+
+    def _group_hyper(self, g):
+        """The param-group entries a user group sets for itself."""
+        return {k: g[k] for k in ("lr", "weight_decay") if k in g}
+
+    # ---- groups and frozen parameters ----
+    def _follow_flags(self):
+        """Make ``param_groups`` hold the trainable parameters of every group again after a ``requires_grad`` flag changed
+        (cheap when none did).  A parameter that became trainable and is named in no group joins the unnamed parameters' group,
+        which is appended behind the others if there was none; its state starts from zero."""
+        m = self.model
+        if not hasattr(m, "_flags"):
+            return
+        flags = m._flags()
+        if flags == self._flags_seen:
+            return
+        named = list(m.named_parameters())
+        owner = {n: gi for gi, (_, names) in enumerate(self._specs) for n in names or ()}
+        woken = [n for (n, p), was in zip(named, self._flags_seen) if p.requires_grad and not was]
+        if all(names is not None for _, names in self._specs) and any(p.requires_grad and n not in owner for n, p in named):
+            if len(self._specs) >= MAX_GROUPS:
+                raise ValueError(f"{type(self).__name__}: a parameter unfrozen outside every group needs the unnamed parameters' "
+                                 f"group, and there are {MAX_GROUPS} groups already")
+            self._specs.append(({}, None))
+            self.add_param_group({"params": [p for n, p in named if p.requires_grad and n not in owner]})
+        for g, (_, names) in zip(self.param_groups, self._specs):
+            g["params"] = [p for n, p in named if p.requires_grad and (n in names if names is not None else n not in owner)]
+        self._flags_seen = flags
+        if woken and self.step_count > 0 and getattr(m, "_flat", None) is not None:
+            for buf in self.state_buffers():
+                for n in woken:
+                    o = m._offsets[n]
+                    buf[o:o + (m._pmap[n].numel() + 63) // 64 * 64].zero_()
+
+    def _group_of(self):
+        """name -> index of its group, for every trainable parameter."""
+        owner = {n: gi for gi, (_, names) in enumerate(self._specs) for n in names or ()}
+        default = next((gi for gi, (_, names) in enumerate(self._specs) if names is None), None)
+        return {n: owner.get(n, default) for n, p in self.model.named_parameters() if p.requires_grad}
+
+    def _plain(self) -> bool:
+        """Nothing frozen (as of the last ``_follow_flags``), one group, no decoupled decay: the launches of the step before groups
+        existed."""
+        return len(self.param_groups) == 1 and not self.param_groups[0].get("decoupled_weight_decay") and all(self._flags_seen)
+
+    def _grouped_step(self, sumsq, s):
+        m = self.model
+        if getattr(getattr(m, "grad_sync", None), "plan", None) is not None:
+            raise NotImplementedError(f"{type(self).__name__}: the sharded optimiser step (CE_SHARDED_ADAM) does not take frozen "
+                                      "parameters or parameter groups")
+        group_of = self._group_of()
+        if not group_of:
+            raise RuntimeError(f"{type(self).__name__}.step: every parameter is frozen")
+        tiles = bool(getattr(m, "_adam_tiles_ok", False)) and os.environ.get("CE_ADAM_TILES", "1") != "0"
+        plan = m.trainable_plan(group_of, tiles=tiles)
+        garr = (OptimGroup * len(self.param_groups))()
+        for i, g in enumerate(self.param_groups):
+            garr[i].lr, garr[i].weight_decay, garr[i].decoupled = float(g["lr"]), float(g["weight_decay"]), int(bool(g.get("decoupled_weight_decay")))
+        if sumsq is not None:
+            sumsq.zero_()
+            check(lib().ce_sumsq_segments(ptr(m._flat_grad), ptr(plan.chunks), c_int(plan.chunks.shape[0]), ptr(sumsq), s),
+                  "ce_sumsq_segments")
+        state, args = self._group_args(sumsq)
+        tj, tn_, tt = plan.tjobs
+        check(getattr(lib(), self._groups_op)(ptr(m._flat), ptr(m._flat_grad), *(ptr(b) for b in state), ptr(m._flat16), ptr(tj),
+                                              c_int(tn_), c_int(tt), ptr(plan.segments), c_int(plan.segments.shape[0]),
+                                              ptr(plan.segment_group), ptr(sumsq), c_float(self.max_norm or 0.0), garr,
+                                              c_int(len(garr)), *args, s), self._groups_op)
+        # a frozen range was not touched: its mirror and W^T copy were current before the step and its master did not move
+        m.mark_operands_stale(mirror_fresh=True, wt_fresh=tiles)
 
     # kept as attributes of the first (only) group so that schedulers and user code see one source of truth
     @property
@@ -65,11 +193,13 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         """clip + update (engine.py:87-95): sum of squares of the whole gradient buffer, then the update with the clip coefficient
-        applied on the fly -- by default in tiles that also leave the blocks' W^T operand copies behind (``_tiles_op``)."""
+        applied on the fly -- by default in tiles that also leave the blocks' W^T operand copies behind (``_tiles_op``).  With
+        frozen parameters, several groups or decoupled decay: the same over the tables of ``model.trainable_plan`` (``_grouped_step``)."""
         if closure is not None:
             raise RuntimeError(f"{type(self).__name__}.step takes no closure")
         self._state()
         m = self.model
+        self._follow_flags()            # a parameter frozen or unfrozen since the last step
         m._settle_first_touch()         # a tower that saw no backward since zero_grad_first_touch
         m.wait_transposes()             # the update rewrites the bf16 mirror an asynchronous W^T rebuild may still be reading
         n = m._flat.numel()
@@ -79,6 +209,12 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         plan = getattr(getattr(m, "grad_sync", None), "plan", None)
         sharded = plan is not None and D.active()
         sumsq = self.sumsq if self.max_norm is not None else None
+        if not self._plain():
+            self._grouped_step(sumsq, s)
+            self._after_step(False)
+            if self.sat_poll_every and self.step_count % self.sat_poll_every == 0 and hasattr(m, "poll_stream16_saturation"):
+                m.poll_stream16_saturation()
+            return
         state, args = self._step_args(sumsq)
 
         def sum_squares(lo, hi):
@@ -116,20 +252,30 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         if self.sat_poll_every and self.step_count % self.sat_poll_every == 0 and hasattr(m, "poll_stream16_saturation"):
             m.poll_stream16_saturation()
 
+    def _params(self):
+        """Every parameter of every group, in group order: torch's state indices run consecutively over them."""
+        self._follow_flags()
+        return [p for g in self.param_groups for p in g["params"]]
+
     def _offset_of(self):
-        """Flat offset of every parameter of the group, in group order."""
+        """Flat offset of every parameter of the groups, in group order."""
         names = {id(p): n for n, p in self.model.named_parameters()}
-        return [self.model._offsets[names[id(p)]] for p in self.param_groups[0]["params"]]
+        return [self.model._offsets[names[id(p)]] for p in self._params()]
 
     def _pieces(self, buf):
-        """The piece of the flat buffer ``buf`` that belongs to each parameter of the group, in group order, in its shape."""
-        return [buf[o:o + p.numel()].view(p.shape) for p, o in zip(self.param_groups[0]["params"], self._offset_of())]
+        """The piece of the flat buffer ``buf`` that belongs to each parameter of the groups, in group order, in its shape."""
+        return [buf[o:o + p.numel()].view(p.shape) for p, o in zip(self._params(), self._offset_of())]
 
     # ---- torch-format state (checkpoint interop): the frames; a subclass fills in the per-parameter state ----
     def _state_dict_of(self, state):
-        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
-        group["params"] = list(range(len(self.param_groups[0]["params"])))
-        return {"state": state, "param_groups": [group]}
+        self._params()
+        groups, at = [], 0
+        for g in self.param_groups:
+            group = {k: v for k, v in g.items() if k != "params"}
+            group["params"] = list(range(at, at + len(g["params"])))
+            at += len(g["params"])
+            groups.append(group)
+        return {"state": state, "param_groups": groups}
 
     def _refuse_sharded_state(self, what):
         if getattr(self, "_moments_stale", False):
@@ -137,16 +283,31 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
                                "clip_event_amd.distributed.consolidate(model, optimizer) on EVERY rank before state_dict()")
 
     def _matching_group(self, sd):
-        """The one param group of ``sd``, after checking that it is ours."""
-        params, groups = self.param_groups[0]["params"], sd["param_groups"]
-        if len(groups) != 1 or len(groups[0]["params"]) != len(params):
-            raise ValueError("optimizer state does not match: expected one group of %d parameters" % len(params))
-        return groups[0]
+        """The param groups of ``sd`` (the one group itself when there is one), after checking that they are ours."""
+        self._params()
+        groups = sd["param_groups"]
+        if len(self.param_groups) == 1:
+            params = self.param_groups[0]["params"]
+            if len(groups) != 1 or len(groups[0]["params"]) != len(params):
+                raise ValueError("optimizer state does not match: expected one group of %d parameters" % len(params))
+            return groups[0]
+        if len(groups) != len(self.param_groups) or any(len(a["params"]) != len(b["params"]) for a, b in zip(groups, self.param_groups)):
+            raise ValueError("optimizer state does not match: expected %d groups of %s parameters"
+                             % (len(self.param_groups), [len(g["params"]) for g in self.param_groups]))
+        def norm(v):
+            return tuple(v) if isinstance(v, (list, tuple)) else v
+
+        for k in groups[0]:
+            if k not in ("params", "lr", "weight_decay", "decoupled_weight_decay", "initial_lr") and \
+                    any(norm(g.get(k)) != norm(groups[0][k]) for g in groups):
+                raise ValueError(f"optimizer state sets {k!r} per group; the fused step shares it")
+        return groups
 
     def _adopt_group(self, group):
-        for k, v in group.items():
-            if k != "params":
-                self.param_groups[0][k] = tuple(v) if k == "betas" else v
+        for mine, theirs in zip(self.param_groups, group if isinstance(group, list) else [group]):
+            for k, v in theirs.items():
+                if k != "params":
+                    mine[k] = tuple(v) if k == "betas" else v
 
 
 class FusedAdam(_FusedFlatOptimizer):
@@ -160,12 +321,24 @@ class FusedAdam(_FusedFlatOptimizer):
     ``exp_avg_sq``): the ``'optimizer'`` entry of a reference checkpoint (engine.py:202-218) loads here and vice
     versa.  The moments themselves live in two flat buffers next to the flat parameters."""
 
-    _flat_op, _tiles_op, _stock = "ce_adam_step", "ce_adam_step_tiles", "torch.optim.Adam"
+    _flat_op, _tiles_op, _groups_op, _stock = "ce_adam_step", "ce_adam_step_tiles", "ce_adam_step_groups", "torch.optim.Adam"
+    _GROUP_KEYS = ("lr", "weight_decay", "decoupled")
 
     def __init__(self, model, lr: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 max_norm=1.0):
+                 max_norm=1.0, decoupled: bool = False, groups=None):
         self.m = self.v = None
-        super().__init__(model, max_norm, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+        if decoupled or any(isinstance(g, dict) and "decoupled" in g for g in groups or ()):
+            # AdamW (``torch.optim.AdamW``): p *= 1 - lr * weight_decay, no decay term in the gradient.  The group key is torch's,
+            # so that a state_dict loaded into torch.optim.AdamW keeps the decoupled form.
+            defaults["decoupled_weight_decay"] = bool(decoupled)
+        super().__init__(model, max_norm, defaults, groups)
+
+    def _group_hyper(self, g):
+        hyper = super()._group_hyper(g)
+        if "decoupled" in g:
+            hyper["decoupled_weight_decay"] = bool(g["decoupled"])
+        return hyper
 
     @property
     def betas(self):
@@ -191,6 +364,9 @@ class FusedAdam(_FusedFlatOptimizer):
     def _step_args(self, sumsq):
         return (self.m, self.v), (ptr(sumsq), c_float(self.max_norm or 0.0), c_float(float(self.lr)), c_float(self.betas[0]),
                                   c_float(self.betas[1]), c_float(self.eps), c_float(self.weight_decay), c_int(self.step_count))
+
+    def _group_args(self, sumsq):
+        return (self.m, self.v), (c_float(self.betas[0]), c_float(self.betas[1]), c_float(self.eps), c_int(self.step_count))
 
     def _after_step(self, sharded):
         if sharded:
@@ -234,10 +410,10 @@ class FusedSGD(_FusedFlatOptimizer):
     as in torch, "first step" means "no buffer yet", not a counter (the arithmetic never reads ``step_count``): the first step
     copies the decayed gradient into it whatever the dampening is."""
 
-    _flat_op, _tiles_op, _stock = "ce_sgd_step", "ce_sgd_step_tiles", "torch.optim.SGD"
+    _flat_op, _tiles_op, _groups_op, _stock = "ce_sgd_step", "ce_sgd_step_tiles", "ce_sgd_step_groups", "torch.optim.SGD"
 
     def __init__(self, model, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
-                 nesterov: bool = False, max_norm=1.0):
+                 nesterov: bool = False, max_norm=1.0, groups=None):
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
         if momentum < 0.0:
@@ -249,7 +425,8 @@ class FusedSGD(_FusedFlatOptimizer):
         self.buf = None
         self._has_buf = False              # a momentum buffer exists: the next step is not the first
         super().__init__(model, max_norm, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                                               nesterov=nesterov, maximize=False, foreach=None, differentiable=False, fused=None))
+                                               nesterov=nesterov, maximize=False, foreach=None, differentiable=False, fused=None),
+                         groups)
 
     @property
     def momentum(self):
@@ -278,6 +455,14 @@ class FusedSGD(_FusedFlatOptimizer):
         return (self.buf if mu != 0 else None,), (ptr(sumsq), c_float(self.max_norm or 0.0), c_float(lr), c_float(mu), c_float(damp),
                                                   c_float(wd), c_int(int(bool(group["nesterov"]))), c_int(int(not self._has_buf)))
 
+    def _group_args(self, sumsq):
+        group = self.param_groups[0]
+        if any(g.get("maximize") for g in self.param_groups):
+            raise NotImplementedError("FusedSGD: maximize is not supported")
+        mu, damp = float(group["momentum"]), float(group["dampening"])
+        return (self.buf if mu != 0 else None,), (c_float(mu), c_float(damp), c_int(int(bool(group["nesterov"]))),
+                                                  c_int(int(not self._has_buf)))
+
     def _after_step(self, sharded):
         if sharded:
             self._moments_stale = self.momentum != 0       # the momentum stays sharded
@@ -293,8 +478,8 @@ class FusedSGD(_FusedFlatOptimizer):
 
     def load_state_dict(self, sd):
         self._moments_stale = False          # (every rank loads the same tensors)
-        params = self.param_groups[0]["params"]
         group = self._matching_group(sd)
+        params = self._params()
         bufs = {int(k): st["momentum_buffer"] for k, st in sd["state"].items() if st.get("momentum_buffer") is not None}
         if bufs and len(bufs) != len(params):
             raise ValueError("only %d of %d parameters carry a momentum_buffer; the fused kernel keeps one buffer and one "
@@ -354,12 +539,24 @@ class WarmupCosineLR(torch.optim.lr_scheduler._LRScheduler):
         return [b * w * c for b in self.base_lrs]
 
 
+def no_decay_groups(model, weight_decay: float):
+    """The usual fine-tuning split as ``groups`` for ``FusedAdam`` / ``FusedSGD``: gains, biases, every other tensor of one
+    dimension or none and ``logit_scale`` get weight decay 0, the matrices (and embeddings) ``weight_decay``.  Trainable
+    parameters only, by name."""
+    decay, no_decay = [], []
+    for n, p in model.named_parameters():
+        if p.requires_grad:
+            (no_decay if p.ndim < 2 or n.endswith(".bias") or n == "logit_scale" else decay).append(n)
+    return [g for g in ({"params": decay, "weight_decay": float(weight_decay)}, {"params": no_decay, "weight_decay": 0.0}) if g["params"]]
+
+
 def build_optimizer(cfg: dict, model, fused: bool = True):
     """engine.py:129-151 (``cfg['optimizer']`` in {'sgd','adam'}); with ``fused`` both return the fused step, which also
-    performs engine.py:89's clip_grad_norm_(.,1).  A model with frozen parameters gets the stock SGD over the trainable ones
-    (the fused step updates the whole flat buffer)."""
+    performs engine.py:89's clip_grad_norm_(.,1).  Frozen parameters: a model that describes its trainable ranges
+    (``trainable_plan``: model.CLIP) keeps the fused step, which then updates those ranges only; any other model gets the stock
+    SGD over the trainable ones (the fused step would update the whole flat buffer)."""
     if cfg["optimizer"] == "sgd":
-        if fused and all(p.requires_grad for p in model.parameters()):
+        if fused and (hasattr(model, "trainable_plan") or all(p.requires_grad for p in model.parameters())):
             return FusedSGD(model, lr=cfg["lr"], momentum=cfg["momentum"], weight_decay=cfg["weight_decay"], max_norm=1.0)
         return torch.optim.SGD([p for p in model.parameters() if p.requires_grad], lr=cfg["lr"],
                                momentum=cfg["momentum"], weight_decay=cfg["weight_decay"])

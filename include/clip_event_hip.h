@@ -333,6 +333,31 @@ int ce_sgd_step(float* p, const float* g, float* buf, void* p_bf16, long n, cons
 int ce_sgd_step_tiles(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
                       int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
                       float momentum, float dampening, float weight_decay, int nesterov, int first_step, void* stream);
+/* ---- partial fine-tuning: a gradient norm and an update over TABLES of what is trainable, with parameter groups ----
+ * out += sum of g^2 over the [lo, hi) element ranges of `table_device` (2 x nchunks longs in DEVICE memory; multiples of 4, at
+ * most 65536 long: one workgroup each, ce_sumsq's rounding chain per chunk).  Nothing outside the table is read: the gradient
+ * slices of frozen parameters may hold anything. */
+int ce_sumsq_segments(const float* g, const long* table_device, int nchunks, float* out, void* stream);
+/* one parameter group: its learning rate and weight decay; decoupled != 0 (Adam only) = AdamW: p *= 1 - lr * weight_decay before the
+ * update and no decay term in the gradient */
+typedef struct ce_optim_group {
+    float lr, weight_decay;
+    int decoupled, pad_;
+} ce_optim_group;
+/* ce_adam_step_tiles / ce_sgd_step_tiles with per-group lr / weight_decay: `groups` is a HOST array of 1 <= ngroups <= 8 entries,
+ * passed into the kernels by value.  A tile job names its group in ce_transpose_job.pad_, segment i in segment_group[i] (DEVICE
+ * memory; NULL: every segment is of group 0); an id outside [0, ngroups) is taken as ngroups - 1.  What is in no table (a frozen
+ * range) is neither read nor written: masters, state, bf16 mirror and W^T copy stay as they are.  One group that is not decoupled
+ * gives ce_*_step_tiles' bits.  -EINVAL for ngroups outside 1..8, groups == NULL, empty tables, a decoupled group with SGD, and
+ * whatever the ungrouped entry points refuse. */
+int ce_adam_step_groups(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                        int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
+                        float max_norm, const ce_optim_group* groups, int ngroups, float beta1, float beta2, float eps, int step,
+                        void* stream);
+int ce_sgd_step_groups(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                       int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
+                       float max_norm, const ce_optim_group* groups, int ngroups, float momentum, float dampening, int nesterov,
+                       int first_step, void* stream);
 
 /* ---- transformer tower runner (tower.cpp): the 12x ResidualAttentionBlock loop of
  * Transformer.forward (model_clip.py:171-211) and its backward, all launches issued from C++ ---- */

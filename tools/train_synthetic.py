@@ -6,7 +6,11 @@ the reference's other optimiser) -> warm-up cosine schedule -> checkpoint in
 the reference's layout -> resume from it.  A smoke run of every host-side component together, not a benchmark.
 
 ``--micro-batch N`` runs every step in chunks of N images (engine.train_step(micro_batch=N): the step for batches whose
-activation stash does not fit)."""
+activation stash does not fit).
+
+Partial fine-tuning: ``--lock-image-tower`` / ``--lock-text-tower`` freeze a tower (``--unlocked-layers N``: except its top N blocks
+and its output side), ``--no-decay-groups`` puts gains, biases and ``logit_scale`` into a parameter group without weight decay,
+``--adamw`` decouples the decay (both with ``--optimizer adam`` and a weight decay of 0.1; the fused step stays in use)."""
 import argparse
 import os
 import sys
@@ -19,7 +23,7 @@ import torch
 from clip_event_amd import checkpoint, clip, distributed as D, synthetic as S
 from clip_event_amd.engine import train_step
 from clip_event_amd.losses import CriterionContrastive
-from clip_event_amd.optim import build_lr_scheduler, build_optimizer
+from clip_event_amd.optim import FusedAdam, FusedSGD, build_lr_scheduler, build_optimizer, no_decay_groups
 from clip_event_amd.preprocess import preprocess
 
 CAPTIONS = list(S.ASCII_CAPTIONS)
@@ -40,7 +44,14 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--micro-batch", type=int, default=None, metavar="N", help="images per chunk of a step (default: unchunked)")
     ap.add_argument("--optimizer", choices=("adam", "sgd"), default="adam", help="cfg['optimizer'] of engine.py:129-151")
+    ap.add_argument("--lock-image-tower", action="store_true", help="freeze the image tower (CLIP.lock_image_tower)")
+    ap.add_argument("--lock-text-tower", action="store_true", help="freeze the text tower (CLIP.lock_text_tower)")
+    ap.add_argument("--unlocked-layers", type=int, default=0, metavar="N", help="blocks a locked tower keeps trainable, from the top")
+    ap.add_argument("--no-decay-groups", action="store_true", help="optim.no_decay_groups: no weight decay on gains, biases, logit_scale")
+    ap.add_argument("--adamw", action="store_true", help="decoupled weight decay (FusedAdam(decoupled=True))")
     args = ap.parse_args()
+    if args.adamw and args.optimizer != "adam":
+        ap.error("--adamw goes with --optimizer adam")
     mb = args.micro_batch
     dev = torch.device("cuda", 0)
     # (SGD's clipped step is lr x a unit-norm gradient: it needs a far larger lr than Adam's per-element lr to move the loss)
@@ -51,7 +62,25 @@ def main():
     model = S.synthetic_model("vit_b32", seed=0).to(dev)
     model.set_hyps(constrastive_overbatch=True, alignment=False, multiattention=False)
     criterion = CriterionContrastive("ce")
-    optimizer = build_optimizer(cfg, model)                                     # engine.py:129-151
+    if args.no_decay_groups or args.adamw:
+        cfg["weight_decay"] = 0.1
+
+    def lock(m):
+        if args.lock_image_tower:
+            m.lock_image_tower(args.unlocked_layers)
+        if args.lock_text_tower:
+            m.lock_text_tower(args.unlocked_layers)
+
+    def make_optimizer(m):
+        if not (args.no_decay_groups or args.adamw):
+            return build_optimizer(cfg, m)                                      # engine.py:129-151; frozen parameters: still the fused step
+        groups = no_decay_groups(m, cfg["weight_decay"]) if args.no_decay_groups else None
+        if args.optimizer == "adam":
+            return FusedAdam(m, lr=cfg["lr"], weight_decay=cfg["weight_decay"], max_norm=1.0, decoupled=args.adamw, groups=groups)
+        return FusedSGD(m, lr=cfg["lr"], momentum=cfg["momentum"], weight_decay=cfg["weight_decay"], max_norm=1.0, groups=groups)
+
+    lock(model)
+    optimizer = make_optimizer(model)
     scheduler = build_lr_scheduler(cfg, optimizer, 0)                           # engine.py:154-176
     data = batch(rng, B, K, dev)                                                # one fixed batch: the loss must fall
     losses = []
@@ -60,11 +89,13 @@ def main():
         scheduler.step()
         losses.append(float(sum(v.detach() for v in ld.values())))
     print("loss:", " ".join(f"{v:.3f}" for v in losses[::3]), "lr", optimizer.param_groups[0]["lr"])
-    assert losses[-1] < 0.5 * losses[0]
+    # (a locked tower cannot follow the fixed batch as fast: the loss must still fall)
+    assert losses[-1] < (0.5 if not (args.lock_image_tower or args.lock_text_tower) else 1.0) * losses[0]
     with tempfile.TemporaryDirectory() as d:
         path = checkpoint.save_model_on_master(model, d, cfg["task"], 20, 0.0, optimizer)      # engine.py:202-218
         model2, opt_state, begin_epoch, _ = checkpoint.load_checkpoint(path, device=dev)       # train.py:101-124
-        optimizer2 = build_optimizer(cfg, model2)
+        lock(model2)
+        optimizer2 = make_optimizer(model2)
         optimizer2.load_state_dict(opt_state)
         scheduler2 = build_lr_scheduler(cfg, optimizer2, begin_epoch)
     assert begin_epoch == 20 and abs(optimizer2.param_groups[0]["lr"] - optimizer.param_groups[0]["lr"]) < 1e-12
