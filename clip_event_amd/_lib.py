@@ -62,6 +62,51 @@ def gemm_nt_plan(M: int, N: int, K: int, epilogue: int, fp8: bool = False, *, ld
     return plan
 
 
+TN_MAX_GROUP = 36                       # CE_TN_MAX_GROUP
+TN_FORMS = ("v1", "v2", "v3", "v3")     # ce_tn_plan.form -> the policy's name for it
+_TN_KERNELS = ("gemm_tn_kernel", "gemm_tn2_kernel", "gemm_tn3_kernel<{rows},{stages}>", "gemm_tn3lw_kernel<{rows},{stages}>")
+
+
+class TNKnobs(ctypes.Structure):
+    """``ce_tn_knobs`` of include/clip_event_hip.h: the weight-gradient GEMM's environment switches as values."""
+    _fields_ = [(name, ctypes.c_int) for name in ("variant", "force_splits", "depth", "rows", "loader_waves")]
+
+    def __init__(self, variant=3, force_splits=0, depth=3, rows=48, loader_waves=1):
+        super().__init__(variant, force_splits, depth, rows, loader_waves)
+
+
+class TNPlan(ctypes.Structure):
+    """``ce_tn_plan`` of include/clip_event_hip.h; ``form`` indexes ``TN_FORMS``."""
+    _fields_ = ([(name, ctypes.c_int) for name in ("form", "rows", "stages", "block", "lds_bytes", "workgroups", "splits",
+                                                    "m_per_split", "depth", "kernel_overwrites", "zero_fill_first", "tiles",
+                                                    "prof_class")] +
+                [(name, ctypes.c_int * TN_MAX_GROUP) for name in ("tiles_n", "tiles_k", "tile_end")])
+
+    @property
+    def kernel(self) -> str:
+        return _TN_KERNELS[self.form].format(rows=self.rows, stages=self.stages)
+
+
+def gemm_tn_plan(shapes, M: int, splits: int = 0, overwrite: bool = False, knobs: TNKnobs = None) -> TNPlan:
+    """The launch ``ce_gemm_tn_grouped_ex`` would make of the problems ``shapes`` = [(Nn, Kk), ...] under ``knobs`` (None:
+    the process's, from the environment) -- ``ce_gemm_tn_plan``: host arithmetic, no GPU."""
+    n = len(shapes)
+    Nn, Kk = (ctypes.c_int * n)(*[s[0] for s in shapes]), (ctypes.c_int * n)(*[s[1] for s in shapes])
+    plan = TNPlan()
+    check(lib().ce_gemm_tn_plan(n, Nn, Kk, M, splits, int(overwrite), ctypes.byref(knobs) if knobs is not None else None,
+                                ctypes.byref(plan)), "ce_gemm_tn_plan")
+    return plan
+
+
+def tower_wgrad_cuts(n_blocks: int, width: int, M: int, extra_tiles: int = 0, force_group: int = 0):
+    """Blocks per grouped weight-gradient launch of ``ce_tower_backward``, top-down (``ce_tower_wgrad_cuts``; no GPU)."""
+    sizes = (ctypes.c_int * max(n_blocks, 1))()
+    groups = lib().ce_tower_wgrad_cuts(n_blocks, width, M, ctypes.c_long(extra_tiles), force_group, sizes)
+    if groups < 0:
+        check(groups, "ce_tower_wgrad_cuts")
+    return list(sizes[:groups])
+
+
 def lib() -> ctypes.CDLL:
     """Load the shared library once; fail loudly when it has not been built."""
     global _lib

@@ -29,6 +29,7 @@
 
 #include "common.hpp"
 #include "nt_plan.hpp"
+#include "tn_plan.hpp"
 #include "../../include/clip_event_hip.h"
 
 #ifndef CE_DIAG_TN3
@@ -1982,13 +1983,13 @@ unsigned int* next_tile_queue(hipStream_t s) {
 }
 
 // One instantiation: raise its dynamic LDS limit once, then launch (forward runs on the caller's thread, backward on autograd's).
-template <auto Kernel>
-void launch_kernel(const NTPlan& p, const NTArgs& a, hipStream_t stream) {
+template <auto Kernel, class Args>
+void launch_kernel(int workgroups, int block, int lds_bytes, const Args& a, hipStream_t stream) {
     static std::once_flag attr;
     std::call_once(attr, [&] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds_bytes);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     });
-    hipLaunchKernelGGL(Kernel, dim3(p.workgroups), dim3(p.block), p.lds_bytes, stream, a);
+    hipLaunchKernelGGL(Kernel, dim3(workgroups), dim3(block), lds_bytes, stream, a);
 }
 
 // (kernel, tm, ts) -> instantiation: the one place that names the NT kernels for launch.  The e4m3 operand form (F8) exists for
@@ -1998,7 +1999,7 @@ void launch_kernel(const NTPlan& p, const NTArgs& a, hipStream_t stream) {
 template <int EPI, int F8>
 bool dispatch(const NTPlan& p, const NTArgs& a, hipStream_t s) {
 #define CE_NT_CASE_IF(COND, KERNEL, TM, TS, ...) \
-    case key(KERNEL, TM, TS): if constexpr (COND) { launch_kernel<__VA_ARGS__>(p, a, s); return true; } break
+    case key(KERNEL, TM, TS): if constexpr (COND) { launch_kernel<__VA_ARGS__>(p.workgroups, p.block, p.lds_bytes, a, s); return true; } break
 #define CE_NT_CASE(KERNEL, TM, ...) CE_NT_CASE_IF(true, KERNEL, TM, 0, __VA_ARGS__)
     constexpr auto key = [](int kernel, int tm, int ts) { return 128 * kernel + 8 * tm + ts; };
     constexpr bool two = nt_two_heights(EPI);
@@ -2185,44 +2186,20 @@ extern "C" int ce_gemm_tn_grouped(int count, const void* const* P, const long* l
     return ce_gemm_tn_grouped_ex(count, P, ldp, Q, ldq, M, Nn, Kk, out, ldo, splits, 0, stream);
 }
 
+// TN launch: tn_plan (tn_plan.cpp) decides, the switch below launches what it decided
+static_assert(TN_PLAN_BM == TN_BM && TN_PLAN_LDS_V1 == TN_LDS_BYTES && TN_PLAN_LDS_128 == T2_LDS_BYTES &&
+              tn_plan_lds_256(48, 3) == 3 * 48 * 1024 && tn_plan_lds_256(32, 4) == 4 * 32 * 1024 && TN_PLAN_BLOCK[TN_V1] == 256 &&
+              TN_PLAN_BLOCK[TN_V2] == 256 && TN_PLAN_BLOCK[TN_V3] == 1024 && TN_PLAN_BLOCK[TN_V3LW] == 768,
+              "tn_plan.hpp is out of step with the kernels");
+
 extern "C" int ce_gemm_tn_grouped_ex(int count, const void* const* P, const long* ldp, const void* const* Q,
                                      const long* ldq, int M, const int* Nn, const int* Kk, float* const* out,
                                      const long* ldo, int splits, int overwrite, void* stream) {
     CE_CHECK_ARG(count >= 1 && count <= CE_TN_MAX_GROUP && M > 0, "ce_gemm_tn_grouped: 1..%d problems, M > 0", CE_TN_MAX_GROUP);
-    // overwrite: out = product.  Unsplit 256x256 tiles store their accumulators; every other form (split tiles, the 128x128
-    // kernels) zero-fills the outputs first and accumulates as usual.
-    auto zero_outputs = [&]() -> int {
-        for (int i = 0; i < count; ++i)
-            if (hipMemset2DAsync(out[i], (size_t)ldo[i] * 4, 0, (size_t)Kk[i] * 4, (size_t)Nn[i], (hipStream_t)stream) != hipSuccess) {
-                ce_set_error("ce_gemm_tn_grouped: zero-fill of output %d failed", i);
-                return -5;
-            }
-        return 0;
-    };
-    static std::once_flag attr_set;
-    static int variant = 3;   // CE_GEMM_TN: 1 = register-staged v1 kernel (one launch per problem), 2 = 128x128 v2,
-                              // 3 (default) = 256x256 ring kernel v3 where the shapes allow, v2 elsewhere
-    std::call_once(attr_set, [] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            TN_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            T2_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn3_kernel<32, 4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            4 * 32 * 1024);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn3_kernel<48, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            3 * 48 * 1024);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn3lw_kernel<48, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            3 * 48 * 1024);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn3lw_kernel<32, 4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            4 * 32 * 1024);
-        const char* e = getenv("CE_GEMM_TN");
-        if (e) variant = atoi(e);
-    });
     hipStream_t s = (hipStream_t)stream;
     TNGroup g;
     g.count = count;
     g.M = M;
-    int tiles = 0;
     double flops = 0.0, bytes = 0.0;
     long ldmax = 0;
     for (int i = 0; i < count; ++i) {
@@ -2233,98 +2210,62 @@ extern "C" int ce_gemm_tn_grouped_ex(int count, const void* const* P, const long
         TNArgs& a = g.prob[i];
         a.P = (const bf16_t*)P[i]; a.ldp = ldp[i]; a.Q = (const bf16_t*)Q[i]; a.ldq = ldq[i];
         a.out = out[i]; a.ldo = ldo[i]; a.M = M; a.Nn = Nn[i]; a.Kk = Kk[i];
-        a.tiles_n = ce_div_up(Nn[i], TN_BN); a.tiles_k = ce_div_up(Kk[i], TN_BK);
-        tiles += a.tiles_n * a.tiles_k;
-        g.tile_end[i] = tiles;
         flops += 2.0 * M * Nn[i] * Kk[i];
         bytes += 2.0 * ((double)M * Nn[i] + (double)M * Kk[i]) + 8.0 * Nn[i] * Kk[i];
         if (ldp[i] > ldmax) ldmax = ldp[i];
         if (ldq[i] > ldmax) ldmax = ldq[i];
     }
-    for (int i = count; i < CE_TN_MAX_GROUP; ++i) g.tile_end[i] = tiles;
-    const int m_tiles = ce_div_up(M, TN_BM);
     CE_CHECK_ARG((long)M * ldmax * 2 < (1L << 32), "ce_gemm_tn: operand exceeds 4 GiB");
-    if (variant == 1) {
-        if (overwrite && zero_outputs() != 0) return -5;
-        if (splits <= 0) splits = 512 / tiles;
-        if (splits > m_tiles) splits = m_tiles;
-        if (splits < 1) splits = 1;
-        g.m_per_split = ce_div_up(m_tiles, splits) * TN_BM;
-        g.splits = ce_div_up(M, g.m_per_split);
-        for (int i = 0; i < count; ++i) {
-            TNArgs a = g.prob[i];
-            a.splits = g.splits; a.m_per_split = g.m_per_split;
-            CeProfScope prof(CE_PROF_GEMM_TN2, 2.0 * M * a.Nn * a.Kk, 0.0, s);
-            hipLaunchKernelGGL(gemm_tn_kernel, dim3(a.tiles_n * a.tiles_k * a.splits), dim3(256), TN_LDS_BYTES, s, a);
-        }
-        CE_LAUNCH_CHECK();
-        return 0;
+
+    const TNPlan p = tn_plan(M, count, Nn, Kk, splits, overwrite != 0, tn_process_knobs());
+    g.splits = p.splits; g.m_per_split = p.m_per_split; g.depth = p.depth; g.overwrite = p.kernel_overwrites;
+    for (int i = 0; i < CE_TN_MAX_GROUP; ++i) g.tile_end[i] = p.tile_end[i];
+    for (int i = 0; i < count; ++i) {
+        TNArgs& a = g.prob[i];
+        a.tiles_n = p.tiles_n[i]; a.tiles_k = p.tiles_k[i]; a.splits = p.splits; a.m_per_split = p.m_per_split;
     }
-    // v3 (256x256 tiles, one workgroup per CU) when every problem is a multiple of 256 both ways and the contraction is
-    // long enough to amortise the 64 KB prologue
-    bool can3 = variant == 3 && M >= 2048;
-    for (int i = 0; i < count; ++i) can3 = can3 && Nn[i] % 256 == 0 && Kk[i] % 256 == 0;
-    if (can3) {
-        int tiles3 = 0;
-        for (int i = 0; i < count; ++i) {
-            TNArgs& a = g.prob[i];
-            a.tiles_n = Nn[i] / 256; a.tiles_k = Kk[i] / 256;
-            tiles3 += a.tiles_n * a.tiles_k;
-            g.tile_end[i] = tiles3;
-        }
-        for (int i = count; i < CE_TN_MAX_GROUP; ++i) g.tile_end[i] = tiles3;
-        static int force_splits = getenv("CE_TN3_SPLITS") ? atoi(getenv("CE_TN3_SPLITS")) : 0;
-        // M split by a cost model fitted to tools/bench_tn_group.py (us): a workgroup spends 1.7 per 64-row contraction
-        // tile + 3 of prologue; rounds of 256 workgroups; only the LAST round's epilogue is exposed -- 0.20 per tile with
-        // float atomics (256 KB at 1.3 TB/s chip-wide), 0.105 as a plain read-modify-write when nothing is split
-        auto cost = [&](int sp) {
-            const long wgs = (long)tiles3 * sp;
-            const long rounds = (wgs + 255) / 256;
-            const long tail = wgs - (rounds - 1) * 256;
-            return rounds * (ce_div_up(m_tiles, sp) * 1.7 + 3.0) + tail * (sp == 1 ? 0.105 : 0.20);
-        };
-        int sp = 1;
-        if (splits > 0) sp = splits;
-        else if (force_splits > 0) sp = force_splits;
-        else {
-            double best = cost(1);
-            for (int c = 2; c <= 16 && c <= m_tiles && (long)tiles3 * c <= 256; ++c)     // split only within one resident round:
-                if (cost(c) < best) { best = cost(c); sp = c; }                         // every split tile costs atomic bandwidth
-        }
-        if (sp > m_tiles) sp = m_tiles;
-        if (sp < 1) sp = 1;
-        g.m_per_split = ce_div_up(m_tiles, sp) * TN_BM;
-        g.splits = ce_div_up(M, g.m_per_split);
-        g.overwrite = (overwrite && g.splits == 1) ? 1 : 0;
-        if (overwrite && !g.overwrite && zero_outputs() != 0) return -5;
-        static int depth = getenv("CE_TN3_DEPTH") ? atoi(getenv("CE_TN3_DEPTH")) : 3;
-        g.depth = depth < 1 ? 1 : (depth > 3 ? 3 : depth);
-        CeProfScope prof(CE_PROF_GEMM_TN, flops, bytes, s);
-        // 48-row stages x 3 slots (default; in the step 993 TF/s) or 32-row stages x 4 slots (CE_TN3_ROWS=32: 935): one
-        // stage less in flight costs nothing (prefetch depth 2 = depth 3 above), a third fewer barriers per FLOP pays
-        static int rows48 = getenv("CE_TN3_ROWS") ? atoi(getenv("CE_TN3_ROWS")) != 32 : 1;
-        static int lw = getenv("CE_TN3_LW") ? atoi(getenv("CE_TN3_LW")) : 1;   // loader-wave form: 1127 -> 1188 TF/s in the step
-        if (lw && rows48)
-            hipLaunchKernelGGL((gemm_tn3lw_kernel<48, 3>), dim3((unsigned)(tiles3 * g.splits)), dim3(768), 3 * 48 * 1024, s, g);
-        else if (lw)
-            hipLaunchKernelGGL((gemm_tn3lw_kernel<32, 4>), dim3((unsigned)(tiles3 * g.splits)), dim3(768), 4 * 32 * 1024, s, g);
-        else if (rows48)
-            hipLaunchKernelGGL((gemm_tn3_kernel<48, 3>), dim3((unsigned)(tiles3 * g.splits)), dim3(1024), 3 * 48 * 1024, s, g);
-        else
-            hipLaunchKernelGGL((gemm_tn3_kernel<32, 4>), dim3((unsigned)(tiles3 * g.splits)), dim3(1024), 4 * 32 * 1024, s, g);
-        CE_LAUNCH_CHECK();
-        return 0;
+    if (p.zero_fill_first)
+        for (int i = 0; i < count; ++i)
+            if (hipMemset2DAsync(out[i], (size_t)ldo[i] * 4, 0, (size_t)Kk[i] * 4, (size_t)Nn[i], s) != hipSuccess) {
+                ce_set_error("ce_gemm_tn_grouped: zero-fill of output %d failed", i);
+                return -5;
+            }
+
+    // (form, rows) -> instantiation: the one place that names the TN kernels for launch, in the order in which the code
+    // object holds them.  One profiler scope per launch: v1 takes one problem per launch.
+    constexpr auto key = [](int form, int rows) { return 64 * form + rows; };
+#define CE_TN_CASE(FORM, ROWS, ...)                                                      \
+    case key(FORM, ROWS): {                                                              \
+        CeProfScope prof(p.prof_class, flops, bytes, s);                                 \
+        launch_kernel<__VA_ARGS__>(p.workgroups, p.block, p.lds_bytes, g, s);            \
+    } break
+    switch (key(p.form, p.rows)) {
+        case key(TN_V1, 64):
+            for (int i = 0; i < count; ++i) {
+                const TNArgs& a = g.prob[i];
+                CeProfScope prof(p.prof_class, 2.0 * M * a.Nn * a.Kk, 0.0, s);
+                launch_kernel<gemm_tn_kernel>(a.tiles_n * a.tiles_k * a.splits, p.block, p.lds_bytes, a, s);
+            }
+            break;
+        CE_TN_CASE(TN_V2, 64, gemm_tn2_kernel);
+        CE_TN_CASE(TN_V3, 32, gemm_tn3_kernel<32, 4>);
+        CE_TN_CASE(TN_V3, 48, gemm_tn3_kernel<48, 3>);
+        CE_TN_CASE(TN_V3LW, 48, gemm_tn3lw_kernel<48, 3>);
+        CE_TN_CASE(TN_V3LW, 32, gemm_tn3lw_kernel<32, 4>);
+        default: CE_CHECK_ARG(false, "ce_gemm_tn_grouped: no kernel of form %d with %d-row stages", (int)p.form, p.rows);
     }
-    // v2: one resident round (at most 2 workgroups per CU = 512 slots), never a ragged second round of SPLIT tiles
-    if (overwrite && zero_outputs() != 0) return -5;
-    if (splits <= 0) splits = 512 / tiles;
-    if (splits > m_tiles) splits = m_tiles;
-    if (splits < 1) splits = 1;
-    g.m_per_split = ce_div_up(m_tiles, splits) * TN_BM;
-    g.splits = ce_div_up(M, g.m_per_split);
-    CeProfScope prof(CE_PROF_GEMM_TN2, flops, bytes, s);
-    hipLaunchKernelGGL(gemm_tn2_kernel, dim3((unsigned)(tiles * g.splits)), dim3(256), T2_LDS_BYTES, s, g);
+#undef CE_TN_CASE
     CE_LAUNCH_CHECK();
+    return 0;
+}
+
+// what the launcher above would do with this group under `knobs` (NULL: the process's); launches nothing
+extern "C" int ce_gemm_tn_plan(int count, const int* Nn, const int* Kk, int M, int splits, int overwrite, const ce_tn_knobs* knobs,
+                               ce_tn_plan* out) {
+    CE_CHECK_ARG(out && Nn && Kk && count >= 1 && count <= CE_TN_MAX_GROUP && M > 0,
+                 "ce_gemm_tn_plan: 1..%d problems, M > 0 and a result struct", CE_TN_MAX_GROUP);
+    for (int i = 0; i < count; ++i) CE_CHECK_ARG(Nn[i] > 0 && Kk[i] > 0, "ce_gemm_tn_plan: empty problem %d", i);
+    *out = tn_plan(M, count, Nn, Kk, splits, overwrite != 0, knobs ? TNKnobs(*knobs) : tn_process_knobs());
     return 0;
 }
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "tn_plan.hpp"
 #include "../../include/clip_event_hip.h"
 
 static thread_local char g_err[512] = "";
@@ -30,6 +31,12 @@ extern "C" int ce_stream16_set_counters(unsigned int* device_counters) {
     return 0;
 }
 unsigned int* ce_sat_counters() { return g_sat_counters; }
+
+// ---- the process's weight-gradient GEMM switches: the environment, read once (the TN launcher and the profiler's names) ----
+const TNKnobs& tn_process_knobs() {
+    static const TNKnobs knobs = tn_knobs_from_env();
+    return knobs;
+}
 
 // ---- profiler: HIP events recorded on the launch stream around every launch of a class ----
 namespace {
@@ -76,8 +83,7 @@ extern "C" void ce_profile_enable(int on) {
 extern "C" const char* ce_profile_class_name(int cls) {
     if (cls < 0 || cls >= CE_PROF_NCLASS) return "?";
     if (cls == CE_PROF_GEMM_TN) {      // the rocprofv3 row of whichever 256x256 form the launcher uses (csrc/gemm.hip)
-        static const bool lw = getenv("CE_TN3_LW") ? atoi(getenv("CE_TN3_LW")) != 0 : true;
-        return lw ? "gemm_tn3lw_kernel" : "gemm_tn3_kernel";
+        return tn_process_knobs().loader_waves ? "gemm_tn3lw_kernel" : "gemm_tn3_kernel";
     }
     if (cls >= CE_PROF_GEMM_TN && cls < CE_PROF_GEMM_NT_QGELU) return kRest[cls - CE_PROF_GEMM_TN];
     const int epi = cls >= CE_PROF_GEMM_NT_QGELU ? CE_EPI_BIAS_QGELU_BF16 : cls / CE_PROF_NT_FAMILIES;

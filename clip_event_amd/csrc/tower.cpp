@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "tn_plan.hpp"
 #include "../../include/clip_event_hip.h"
 
 namespace {
@@ -23,7 +24,7 @@ namespace {
 // grouped launch (ce_gemm_tn_grouped): several rounds of unsplit tiles, so each round's atomic epilogue (memory-side
 // float atomics run at 1.3 TB/s chip-wide: a 10-20 % tail of a one-round launch) overlaps the next round's contraction.  The gradient operands (bf16
 // dY buffers) of the queued blocks stay alive in a ring of WG_SETS buffer sets.
-constexpr int WG_MAX_BLOCKS = 8;            // blocks per grouped launch (x 4 problems <= CE_TN_MAX_GROUP)
+constexpr int WG_MAX_BLOCKS = TN_GROUP_MAX_BLOCKS;   // blocks per grouped launch (x 4 problems <= CE_TN_MAX_GROUP)
 constexpr int WG_SETS = WG_MAX_BLOCKS + 1;  // a block writes its own set and the next block's dxb
 // LayerNorm-backward partial sums: a ring of LNP_RING buffer sets (two per block); ce_layernorm_fold runs whenever the ring is
 // full and at the end of a backward call, so a tower workspace carries 8 sets, not one per layer (ViT-L: 24) -- they only live
@@ -328,35 +329,19 @@ extern "C" int ce_tower_backward_range(const ce_tower_desc* d, int batch, int ro
         }
         return rc;
     };
-    // Where to cut the block sequence into grouped launches.  A launch of T unsplit 256x256 tiles takes ceil(T / 256)
-    // rounds of the 256 CUs and every round costs a full tile time, so the cuts are chosen (small dynamic programme over
-    // the blocks of this call) to minimise the total number of rounds: ViT-B/32 image tower, 108 tiles per block, 11
-    // blocks below the pruned one: 7 blocks (756 tiles, 2.95 rounds) + 4 blocks and the pruned block's in_proj (459
-    // tiles, 1.8 rounds) = 5 rounds; fixed groups of 5 took 6.  Shapes the 256x256 kernel does not take are counted in
-    // 128x128 tiles over the 512 two-per-CU slots.  CE_WGRAD_GROUP = n forces groups of n blocks.
+    // Where to cut the block sequence into grouped launches: tn_group_cuts (tn_plan.cpp) minimises the rounds the launches
+    // take.  ViT-B/32 image tower, 108 tiles per block, 11 blocks below the pruned one: 7 blocks (756 tiles, 2.95 rounds) +
+    // 4 blocks and the pruned block's in_proj (459 tiles, 1.8 rounds) = 5 rounds; fixed groups of 5 took 6.
+    // CE_WGRAD_GROUP = n forces groups of n blocks.
     static const int force_group = getenv("CE_WGRAD_GROUP") ? atoi(getenv("CE_WGRAD_GROUP")) : 0;
     bool cut_after[Layout::MAX_LAYERS] = {};
     auto plan_cuts = [&](int hi, int lo, long extra_tiles) {       // blocks hi .. lo (top-down) are about to be queued
-        const int n = hi - lo + 1;
-        if (n <= 0) return;
-        const bool big = (w % 256 == 0) && M >= 2048;
-        const long t = big ? 12L * (w / 256) * (w / 256) : 12L * ((w + 127) / 128) * ((w + 127) / 128);
-        const long slots = big ? 256 : 512;
-        long cost[Layout::MAX_LAYERS + 1];
-        int take[Layout::MAX_LAYERS + 1];
-        cost[0] = 0;
-        for (int k = 1; k <= n; ++k) {                               // k blocks, counted from the BOTTOM of the range
-            cost[k] = -1;
-            for (int g = 1; g <= WG_MAX_BLOCKS && g <= k; ++g) {     // the topmost group of those k has g blocks
-                if (force_group >= 1 && g != force_group && g != k) continue;
-                const long tiles = g * t + (k == n ? extra_tiles : 0);   // the group that starts the range inherits the queue
-                const long c = cost[k - g] + (tiles + slots - 1) / slots * 1000 + 1;   // rounds first, then fewer launches
-                if (cost[k] < 0 || c < cost[k]) { cost[k] = c; take[k] = g; }
-            }
-        }
+        static_assert(Layout::MAX_LAYERS <= TN_CUT_MAX_BLOCKS, "tn_group_cuts takes fewer blocks than a tower has");
+        int sizes[Layout::MAX_LAYERS];
+        const int groups = tn_group_cuts(hi - lo + 1, w, M, extra_tiles, force_group, sizes);
         int l = hi;
-        for (int k = n; k > 0; k -= take[k]) {
-            l -= take[k];
+        for (int i = 0; i < groups; ++i) {
+            l -= sizes[i];
             cut_after[l + 1] = true;                                  // flush once block l+1 has been queued
         }
     };
@@ -429,8 +414,7 @@ extern "C" int ce_tower_backward_range(const ce_tower_desc* d, int batch, int ro
         if (d->stream16) TRY(ce_cast_scaled(dx, ST, L.dxb[top % WG_SETS], CE_T_BF16, GS, 1, (long)M * w, stream));
         else TRY(ce_cast_bf16(reinterpret_cast<const float*>(dx), L.dxb[top % WG_SETS], (long)M * w, stream));
     }
-    plan_cuts(top, layer_lo, pend.count > 0 ? ((w % 256 == 0 && M >= 2048) ? 3L * (w / 256) * (w / 256)
-                                                                              : 3L * ((w + 127) / 128) * ((w + 127) / 128)) : 0);
+    plan_cuts(top, layer_lo, pend.count > 0 ? 3 * tn_problem_tiles(M, w, w) : 0);      // the pruned block's in_proj
     for (int l = top; l >= layer_lo; --l) {
         const ce_block_params& p = d->blocks[l];
         BlockStash& s = L.blk[l];
@@ -475,3 +459,9 @@ extern "C" int ce_tower_backward_range(const ce_tower_desc* d, int batch, int ro
     return 0;
 }
 
+// the cuts ce_tower_backward makes (tn_group_cuts); launches nothing
+extern "C" int ce_tower_wgrad_cuts(int n_blocks, int width, int M, long extra_tiles, int force_group, int* sizes_out) {
+    CE_CHECK_ARG(sizes_out && n_blocks >= 1 && n_blocks <= TN_CUT_MAX_BLOCKS && width > 0 && M > 0 && extra_tiles >= 0,
+                 "ce_tower_wgrad_cuts: 1..%d blocks, width, M > 0, extra_tiles >= 0 and a result array", TN_CUT_MAX_BLOCKS);
+    return tn_group_cuts(n_blocks, width, M, extra_tiles, force_group, sizes_out);
+}

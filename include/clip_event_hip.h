@@ -562,6 +562,24 @@ typedef struct { int kernel, tm, ts, tall_panels, tiles_m, tiles_n, tile_chunk,
 int ce_gemm_nt_plan(int M, int N, int K, int epilogue, int fp8,
                     long lda, long ldb, long ldo, long ldo2, long ldaux, long ldr,
                     ce_nt_plan* out);
+/* The same for the weight-gradient (TN) launcher: what ce_gemm_tn_grouped_ex(count, ..., M, Nn, Kk, ..., splits, overwrite)
+ * launches.  knobs: the environment's weight-gradient switches (csrc/tn_plan.cpp names them) as values -- variant [3],
+ * force_splits [0], depth [3, clamped to 1..3], rows [48 unless exactly 32], loader_waves [1]; NULL: the process's, read from
+ * the environment once.  form: 0 gemm_tn_kernel (v1: one launch per problem, `workgroups` in all),
+ * 1 gemm_tn2_kernel (v2, 128x128 tiles), 2 gemm_tn3_kernel<rows,stages>, 3 gemm_tn3lw_kernel<rows,stages> (v3, 256x256 tiles);
+ * workgroups = tiles * splits, every split m_per_split rows (a multiple of 64); kernel_overwrites: unsplit 256x256 tiles store
+ * `out`; zero_fill_first: the launcher zeroes `out` before the launch (overwrite on any other form); tiles_n, tiles_k, tile_end
+ * (cumulative, padded with `tiles`): the tiling per problem. */
+typedef struct { int variant, force_splits, depth, rows, loader_waves; } ce_tn_knobs;
+typedef struct { int form, rows, stages, block, lds_bytes, workgroups, splits, m_per_split, depth,
+                 kernel_overwrites, zero_fill_first, tiles, prof_class;
+                 int tiles_n[CE_TN_MAX_GROUP], tiles_k[CE_TN_MAX_GROUP], tile_end[CE_TN_MAX_GROUP]; } ce_tn_plan;
+int ce_gemm_tn_plan(int count, const int* Nn, const int* Kk, int M, int splits, int overwrite,
+                    const ce_tn_knobs* knobs, ce_tn_plan* out);
+/* How ce_tower_backward groups the weight gradients of n_blocks (1..64) residual blocks of `width`, M rows, into grouped TN
+ * launches: group sizes top-down into sizes_out[n_blocks], returns their number.  extra_tiles: tiles already queued (they go
+ * out with the first group); force_group: CE_WGRAD_GROUP (0: planned). */
+int ce_tower_wgrad_cuts(int n_blocks, int width, int M, long extra_tiles, int force_group, int* sizes_out);
 /* tuning hook (tools/ only): 0 auto, 4/5/6/8 = tile height (x32 rows) of the 256-column kernel, 105 = 160x128 tile */
 void ce_gemm_nt_fp8_tune(int variant);
 

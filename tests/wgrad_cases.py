@@ -152,37 +152,25 @@ def launched():
     return {c: int(buf[4 * c]) for c in (PROF_TN3, PROF_TN2) if buf[4 * c] > 0}
 
 
-def _env_int(name, default):
-    """The integer the launcher reads from `name` (C atoi: 0 for text that is not a number)."""
-    v = os.environ.get(name)
-    if v is None:
-        return default
-    try:
-        return int(v)
-    except ValueError:
-        return 0
-
-
-def family(counts):
-    """(form, kernel name) of what ran, from the profiler classes and the environment the launcher read."""
+def ran_form(counts, plan):
+    """The form that ran, from the profiler classes alone; v1 and v2 share a class, there the plan tells which."""
+    from clip_event_amd._lib import TN_FORMS
     if counts.get(PROF_TN3):
-        lw = _env_int("CE_TN3_LW", 1) != 0
-        rows = 32 if _env_int("CE_TN3_ROWS", 48) == 32 else 48
-        return "v3", f"gemm_tn3{'lw' if lw else ''}_kernel<{rows},{3 if rows == 48 else 4}>"
+        return "v3"
     if counts.get(PROF_TN2):
-        if _env_int("CE_GEMM_TN", 3) == 1:
-            return "v1", "gemm_tn_kernel"
-        return "v2", "gemm_tn2_kernel"
-    return "none", "none"
+        return "v1" if TN_FORMS[plan.form] == "v1" else "v2"
+    return "none"
 
 
 def expected_form(policy):
-    return {1: "v1", 2: "v2"}.get(_env_int("CE_GEMM_TN", 3), policy)
+    """The case table's policy, or the form CE_GEMM_TN forces.  Only the plain spellings "1" and "2" count here (the library
+    parses with atoi, so "01" would force v1 there and fail the case here, not pass it)."""
+    return {"1": "v1", "2": "v2"}.get(os.environ.get("CE_GEMM_TN", "").strip(), policy)
 
 
 def run_case(case, seed=0, dev="cuda:0", log=print):
     """Every (M, splits, overwrite) of a case: one launch each, checked against fp64.  Returns one record per launch."""
-    from clip_event_amd._lib import lib
+    from clip_event_amd._lib import TN_FORMS, gemm_tn_plan, lib
     recs = []
     lib().ce_profile_enable(1)
     launched()
@@ -197,16 +185,18 @@ def run_case(case, seed=0, dev="cuda:0", log=print):
                     outs = [p.fresh_out(overwrite) for p in probs]
                     rc = grouped_call(probs, outs, M, splits, overwrite)
                     torch.cuda.synchronize()
-                    form, kernel = family(launched())
+                    plan = gemm_tn_plan([(p.Nn, p.Kk) for p in probs], M, splits, overwrite)      # under the process's knobs
+                    form, kernel = ran_form(launched(), plan), plan.kernel
                     rec = dict(case=case.name, M=M, splits=splits, overwrite=overwrite, problems=len(probs), rc=rc, form=form,
-                               kernel=kernel, expect=expected_form(case.policy))
+                               kernel=kernel, workgroups=plan.workgroups, expect=expected_form(case.policy))
                     over, worst, rel, guards = 0, 0.0, 0.0, True
                     if rc == 0:
                         for p, o in zip(probs, outs):
                             (ov, wo, re_), g = p.check(o, overwrite)
                             over, worst, rel, guards = over + ov, max(worst, wo), max(rel, re_), guards and g
                     rec.update(over=over, worst=worst, rel=rel, guards=guards,
-                               ok=rc == 0 and over == 0 and rel < TN_REL_L2 and guards and form == rec["expect"])
+                               ok=(rc == 0 and over == 0 and rel < TN_REL_L2 and guards and
+                                   form == rec["expect"] == TN_FORMS[plan.form]))
                     log(f"[tn {case.name} M={M} splits={splits} overwrite={overwrite}] {kernel} ({form}, want {rec['expect']}): "
                         f"{over} elements over 2^-12 |P|^T|Q|, worst ratio {worst:.2e}, rel_l2 {rel:.2e}, "
                         f"guards {'untouched' if guards else 'WRITTEN'}" + ("" if rc == 0 else f", rc {rc}"))
