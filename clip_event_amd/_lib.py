@@ -8,9 +8,12 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 from ctypes import c_char_p, c_void_p
 
 import torch
+
+from .build import HEADER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libclip_event_hip.so")
@@ -51,14 +54,13 @@ def gemm_nt_plan(M: int, N: int, K: int, epilogue: int, fp8: bool = False, *, ld
     """The launch ``ce_gemm_nt`` (``fp8``: the loader-wave path of ``ce_gemm_nt_fp8``) would make under the process's current
     knobs (``ce_gemm_nt_plan``: host arithmetic, no GPU).  Leading dimensions default to those of contiguous operands; an
     operand the epilogue does not have has 0."""
-    c_long = ctypes.c_long
     has_out2 = epilogue in (EPI_BIAS_GELU, EPI_GELUGRAD_BF16)
     has_resid = epilogue in (EPI_BIAS_RESID_F32, EPI_BIAS_RESID_F16)
     lds = [K if lda is None else lda, K if ldb is None else ldb, N if ldo is None else ldo,
            (N if has_out2 else 0) if ldo2 is None else ldo2, (N if epilogue == EPI_GELUGRAD_BF16 else 0) if ldaux is None else ldaux,
            (N if has_resid else 0) if ldr is None else ldr]
     plan = NTPlan()
-    check(lib().ce_gemm_nt_plan(M, N, K, epilogue, int(fp8), *[c_long(v) for v in lds], ctypes.byref(plan)), "ce_gemm_nt_plan")
+    check(lib().ce_gemm_nt_plan(M, N, K, epilogue, int(fp8), *lds, ctypes.byref(plan)), "ce_gemm_nt_plan")
     return plan
 
 
@@ -101,22 +103,56 @@ def gemm_tn_plan(shapes, M: int, splits: int = 0, overwrite: bool = False, knobs
 def tower_wgrad_cuts(n_blocks: int, width: int, M: int, extra_tiles: int = 0, force_group: int = 0):
     """Blocks per grouped weight-gradient launch of ``ce_tower_backward``, top-down (``ce_tower_wgrad_cuts``; no GPU)."""
     sizes = (ctypes.c_int * max(n_blocks, 1))()
-    groups = lib().ce_tower_wgrad_cuts(n_blocks, width, M, ctypes.c_long(extra_tiles), force_group, sizes)
+    groups = lib().ce_tower_wgrad_cuts(n_blocks, width, M, extra_tiles, force_group, sizes)
     if groups < 0:
         check(groups, "ce_tower_wgrad_cuts")
     return list(sizes[:groups])
 
 
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t}
+_DECL = re.compile(r"((?:\w+\s+)*\w+\s*\*?)\s*\b(ce_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+
+
+def signatures(header_text: str) -> dict:
+    """{name: (restype, [argtypes])} of every function ``header_text`` (include/clip_event_hip.h) declares.  Scalars map to
+    the ctypes scalar of the same name, every pointer to ``c_void_p``, a ``void`` return to None and a ``const char*`` return
+    to ``c_char_p``; any other type raises and names the declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header_text, flags=re.S)
+    text = "\n".join(line for line in text.split("\n") if not line.lstrip().startswith("#"))
+    out = {}
+    for ret, name, params in _DECL.findall(text):
+        ret = " ".join(ret.replace("*", " * ").split())
+        if ret not in _SCALARS and ret not in ("void", "const char *"):
+            raise TypeError(f"{name}: return type '{ret}' has no ctypes mapping")
+        restype = c_char_p if "*" in ret else _SCALARS.get(ret)
+        argtypes = []
+        for param in ([] if params.strip() in ("", "void") else params.split(",")):
+            ctype = " ".join(w for w in param.split()[:-1] if w != "const")         # the last word is the parameter's name
+            if "*" not in param and ctype not in _SCALARS:
+                raise TypeError(f"{name}: parameter '{' '.join(param.split())}' has no ctypes mapping")
+            argtypes.append(c_void_p if "*" in param else _SCALARS[ctype])
+        out[name] = (restype, argtypes)
+    return out
+
+
 def lib() -> ctypes.CDLL:
-    """Load the shared library once; fail loudly when it has not been built."""
+    """Load the shared library once and give every function the header declares its ``restype`` / ``argtypes``: a wrong
+    width or a wrong argument count then raises in Python, before the call.  Fails loudly when the library has not been
+    built or the header is not where ``build.HEADER`` says."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise HipExtensionMissing(
                 f"{LIB_PATH} not found: build it with `python -m clip_event_amd.build` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.ce_last_error.restype = c_char_p
+        with open(HEADER) as f:
+            declared = signatures(f.read())
+        cdll = ctypes.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in declared.items():
+            fn = getattr(cdll, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _lib = cdll
     return _lib
 
 

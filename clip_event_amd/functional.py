@@ -12,12 +12,12 @@ from __future__ import annotations
 import ctypes
 import os
 import weakref
-from ctypes import c_float, c_int, c_long, c_void_p
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from . import ops
 from ._lib import check, lib, ptr, stream
 
 
@@ -31,9 +31,8 @@ def _tower_workspace(model, desc, batch: int, tag: str, infer: bool = False):
     that a shorter last chunk runs in the full chunk's buffer (the pool is keyed by byte count and never frees)."""
     from .model import _Lease
     fn = lib().ce_tower_infer_workspace_bytes if infer else lib().ce_tower_workspace_bytes
-    fn.restype = ctypes.c_size_t
     hint = getattr(model, "_lease_batch", None)
-    nbytes = fn(ctypes.byref(desc), c_int(max(batch, hint.get(tag, 0)) if hint else batch))
+    nbytes = fn(ctypes.byref(desc), max(batch, hint.get(tag, 0)) if hint else batch)
     if nbytes == 0:
         raise RuntimeError(fn.__name__ + ": " + lib().ce_last_error().decode())
     if infer:
@@ -47,7 +46,7 @@ def _tower_forward_infer(model, desc, tag: str, batch: int, rows: int, cu, x0, x
     the pool as soon as the launches are enqueued (the next lease of this tag is taken on the same stream, as the
     training leases are)."""
     lease = _tower_workspace(model, desc, batch, tag, infer=True)
-    check(lib().ce_tower_forward_infer(ctypes.byref(desc), c_int(batch), c_int(rows), ptr(cu), ptr(x0), ptr(lease.buf),
+    check(lib().ce_tower_forward_infer(ctypes.byref(desc), batch, rows, ptr(cu), ptr(x0), ptr(lease.buf),
                                        ptr(x_out), ptr(sel), stream()), f"ce_tower_forward_infer({tag})")
     lease.release()
 
@@ -97,9 +96,8 @@ def _tower_backward(model, desc, tower: str, batch: int, rows: int, cu, x0, leas
         pending.discard(tower)
     hi = layers - 1
     for lo in (list(cuts) + [stop] if stop < layers else []):
-        check(cl.ce_tower_backward_range(ctypes.byref(desc), c_int(batch), c_int(rows), ptr(cu), ptr(x0), ptr(lease.buf),
-                                         ptr(dx), ptr(sel), ptr(dx_sel), c_int(hi), c_int(lo), s),
-              f"ce_tower_backward_range({tower})")
+        check(cl.ce_tower_backward_range(ctypes.byref(desc), batch, rows, ptr(cu), ptr(x0), ptr(lease.buf), ptr(dx), ptr(sel),
+                                         ptr(dx_sel), hi, lo, s), f"ce_tower_backward_range({tower})")
         if lo > stop:
             model.grad_sync(model, tower, upto_layer=lo)
         hi = lo - 1
@@ -189,7 +187,7 @@ def text_packing(model, text, lengths=None) -> TextPacking:
         eot = None
     else:
         eot = _empty((n,), torch.int32, dev)
-        check(cl.ce_eot_rows(ptr(text), ptr(eot), c_long(n), c_int(T), s), "ce_eot_rows")
+        check(cl.ce_eot_rows(ptr(text), ptr(eot), n, T, s), "ce_eot_rows")
         flat = None
     if not model.pack_text:
         if eot is None:
@@ -238,16 +236,47 @@ def _grad_scale(model, desc, top_grad):
     if not getattr(model, "stream16", False):
         desc.grad_scale = None
         return None
-    buf = _empty((1 + 256,), torch.float32, top_grad.device)            # [0] the scale, [1:] CE_GRAD_SCALE_SCRATCH partial maxima
-    check(lib().ce_grad_scale(ptr(top_grad), c_long(top_grad.numel()), c_float(model.grad_target), c_void_p(buf.data_ptr() + 4),
-                              ptr(buf), stream()), "ce_grad_scale")
-    desc.grad_scale = buf.data_ptr()
-    return buf
+    gs = ops.grad_scale(top_grad, model.grad_target)
+    desc.grad_scale = gs.data_ptr()
+    return gs
 
 
 def _check_stream(ctx, model):
     if ctx.stream16 != bool(getattr(model, "stream16", False)):
         raise RuntimeError("model.stream16 changed between this pass's forward and its backward")
+
+
+def _tower_top_forward(model, xN, ln: str, proj: str):
+    """What follows a tower's blocks -- final LayerNorm, then projection (``visual.ln_post`` / ``visual.proj``,
+    model_clip.py:256-261; ``ln_final`` / ``text_projection``, :413-415) -- on the consumed rows ``xN`` [n, D]:
+    (features fp32 [n, E], LayerNorm output bf16 [n, D], mean, rstd)."""
+    P = model._pmap
+    h, mean, rstd = ops.layernorm_fwd_t(xN, P[ln + ".weight"], P[ln + ".bias"])
+    return ops.gemm_nt(h, model._w16t[proj], L.EPI_F32), h, mean, rstd       # W^T copy [E, D]: features = h @ proj
+
+
+def _tower_top_backward(model, desc, dfeat, xN, h, mean, rstd, ln: str, proj: str):
+    """Backward of ``_tower_top_forward`` for the feature gradient ``dfeat`` (fp32 [n, E], contiguous): adds the gradients
+    of the projection and of the LayerNorm's parameters, and returns (the fp32 gradient at the tower output [n, D], the
+    gradient scale of this pass -- ``_grad_scale``, chosen from that tensor)."""
+    P, G = model._pmap, model._gview
+    dfb = torch.empty_like(dfeat, dtype=torch.bfloat16)
+    check(lib().ce_cast_bf16(ptr(dfeat), ptr(dfb), dfeat.numel(), stream()), "ce_cast_bf16")
+    dh = ops.gemm_nt(dfb, model._w16[proj], L.EPI_BF16)       # features = h @ proj  ->  dh = dF proj^T
+    ops.gemm_tn(h, dfb, G(proj))                              # dproj += h^T dF
+    dxn = ops.layernorm_bwd_t(dh, xN, mean, rstd, P[ln + ".weight"], G(ln + ".weight"), G(ln + ".bias"),
+                              torch.empty_like(xN, dtype=torch.float32))
+    return dxn, _grad_scale(model, desc, dxn)
+
+
+def _tower_backward_done(ctx, tower: str, n_inputs: int):
+    """Close of a tower node's backward: hand the tower's remaining gradients to the data-parallel exchange, make the step's
+    stream wait for this one, and return the (absent) input gradients."""
+    model = ctx.model
+    if model.grad_sync is not None:
+        model.grad_sync(model, tower)
+    _publish_to_main(ctx)
+    return (None,) * n_inputs
 
 
 class EncodeImageFn(torch.autograd.Function):
@@ -269,21 +298,13 @@ class EncodeImageFn(torch.autograd.Function):
         M = B * T
         P = model._pmap
         patches = _empty((B * g * g, model._kp), torch.bfloat16, dev)
-        check(cl.ce_im2col(ptr(image), ptr(patches), c_int(B), c_int(R), c_int(ps), c_int(model._kp), s), "ce_im2col")
-        patch_out = _empty((B * g * g, D), torch.float32, dev)
-        wconv = model._w16["visual.conv1.weight"]
-        check(cl.ce_gemm_nt(ptr(patches), c_long(model._kp), ptr(wconv), c_long(model._kp), c_int(B * g * g), c_int(D),
-                            c_int(model._kp), c_int(L.EPI_F32), None, None, c_long(0), ptr(patch_out), c_long(D), None,
-                            c_long(0), None, c_long(0), s), "ce_gemm_nt(conv1)")
+        check(cl.ce_im2col(ptr(image), ptr(patches), B, R, ps, model._kp, s), "ce_im2col")
+        patch_out = ops.gemm_nt(patches, model._w16["visual.conv1.weight"], L.EPI_F32)
         xpre = _empty((M, D), torch.float32, dev)
         check(cl.ce_vision_assemble(ptr(patch_out), ptr(P["visual.class_embedding"]), ptr(P["visual.positional_embedding"]),
-                                    ptr(xpre), c_int(B), c_int(T), c_int(D), s), "ce_vision_assemble")
-        sdt, ST = _stream_type(model)                         # residual stream: fp32, or fp16 (model.stream16)
-        x0 = _empty((M, D), sdt, dev)
-        mean_pre, rstd_pre = _empty((M,), torch.float32, dev), _empty((M,), torch.float32, dev)
-        check(cl.ce_layernorm_fwd_t(ptr(xpre), c_int(L.T_F32), c_long(D), None, ptr(P["visual.ln_pre.weight"]),
-                                    ptr(P["visual.ln_pre.bias"]), ptr(x0), c_int(ST), c_long(D), ptr(mean_pre), ptr(rstd_pre),
-                                    c_int(M), c_int(D), c_float(1e-5), s), "ce_layernorm_fwd(ln_pre)")
+                                    ptr(xpre), B, T, D, s), "ce_vision_assemble")
+        sdt, _ = _stream_type(model)                          # residual stream: fp32, or fp16 (model.stream16)
+        x0, mean_pre, rstd_pre = ops.layernorm_fwd_t(xpre, P["visual.ln_pre.weight"], P["visual.ln_pre.bias"], sdt)
         if use_grid:
             rows, n = None, M
         else:                      # only the CLS row of each image is consumed (model_clip.py:256): pruned last block
@@ -297,19 +318,9 @@ class EncodeImageFn(torch.autograd.Function):
             _tower_forward_infer(model, model._vdesc, "vision", B, M, None, x0, xN, rows)
         else:
             lease = _tower_workspace(model, model._vdesc, B, "vision")
-            check(cl.ce_tower_forward(ctypes.byref(model._vdesc), c_int(B), c_int(M), None, ptr(x0), ptr(lease.buf), ptr(xN),
-                                      ptr(rows), s),
+            check(cl.ce_tower_forward(ctypes.byref(model._vdesc), B, M, None, ptr(x0), ptr(lease.buf), ptr(xN), ptr(rows), s),
                   "ce_tower_forward(vision)")
-        hpost = _empty((n, D), torch.bfloat16, dev)
-        mean_post, rstd_post = _empty((n,), torch.float32, dev), _empty((n,), torch.float32, dev)
-        check(cl.ce_layernorm_fwd_t(ptr(xN), c_int(ST), c_long(D), None, ptr(P["visual.ln_post.weight"]),
-                                    ptr(P["visual.ln_post.bias"]), ptr(hpost), c_int(L.T_BF16), c_long(D), ptr(mean_post),
-                                    ptr(rstd_post), c_int(n), c_int(D), c_float(1e-5), s), "ce_layernorm_fwd(ln_post)")
-        feat = _empty((n, E), torch.float32, dev)
-        wp = model._w16t["visual.proj"]                       # [E, D]: features = hpost @ proj
-        check(cl.ce_gemm_nt(ptr(hpost), c_long(D), ptr(wp), c_long(D), c_int(n), c_int(E), c_int(D), c_int(L.EPI_F32),
-                            None, None, c_long(0), ptr(feat), c_long(E), None, c_long(0), None, c_long(0), s),
-              "ce_gemm_nt(visual.proj)")
+        feat, hpost, mean_post, rstd_post = _tower_top_forward(model, xN, "visual.ln_post", "visual.proj")
         if infer:
             return feat.view(B, T, E) if use_grid else feat
         ctx.model, ctx.lease, ctx.use_grid, ctx.B = model, lease, use_grid, B
@@ -330,78 +341,42 @@ class EncodeImageFn(torch.autograd.Function):
         B, g, D, E = ctx.B, v.patch_num, model.vision_width, model.embed_dim
         T = g * g + 1
         M = B * T
-        n = M if ctx.use_grid else B
         model._attach_grads()
         P, G = model._pmap, model._gview
-        dfeat = _f32(dfeat).reshape(n, E)
-        dfb = _empty((n, E), torch.bfloat16, dev)
-        check(cl.ce_cast_bf16(ptr(dfeat), ptr(dfb), c_long(n * E), s), "ce_cast_bf16")
-        # features = hpost @ proj  ->  dhpost = dF proj^T ; dproj += hpost^T dF
-        dh = _empty((n, D), torch.bfloat16, dev)
-        check(cl.ce_gemm_nt(ptr(dfb), c_long(E), ptr(model._w16["visual.proj"]), c_long(E), c_int(n), c_int(D), c_int(E),
-                            c_int(L.EPI_BF16), None, None, c_long(0), ptr(dh), c_long(D), None, c_long(0), None,
-                            c_long(0), s), "ce_gemm_nt(dproj)")
-        check(cl.ce_gemm_tn(ptr(hpost), c_long(D), ptr(dfb), c_long(E), c_int(n), c_int(D), c_int(E),
-                            ptr(G("visual.proj")), c_long(E), c_int(0), s), "ce_gemm_tn(visual.proj)")
         _check_stream(ctx, model)
-        sdt, ST = _stream_type(model)
         # gradient w.r.t. the tower output (fp32): [B,D] in pruned mode (the tower's dx_sel) or [M,D] in grid mode, where it
         # IS the gradient stream on entry -- an fp16 stream holds gradient * scale, the scale chosen from this tensor
-        grid_mode = rows is None
-        dxn = _empty((n, D), torch.float32, dev)
-        check(cl.ce_layernorm_bwd_t(ptr(dh), c_int(L.T_BF16), c_long(D), ptr(xN), c_int(ST), c_long(D), None, ptr(mean_post),
-                                    ptr(rstd_post), ptr(P["visual.ln_post.weight"]), None, c_int(L.T_F32), ptr(dxn),
-                                    c_int(L.T_F32), c_long(D), None, c_long(0), ptr(G("visual.ln_post.weight")),
-                                    ptr(G("visual.ln_post.bias")), None, None, c_int(n), c_int(D), s), "ce_layernorm_bwd(ln_post)")
-        gs = _grad_scale(model, model._vdesc, dxn)
-        if grid_mode:
-            if gs is None:
-                dx = dxn
-            else:
-                dx = _empty((M, D), sdt, dev)
-                check(cl.ce_cast_scaled(ptr(dxn), c_int(L.T_F32), ptr(dx), c_int(ST), ptr(gs), c_int(0), c_long(M * D), s),
-                      "ce_cast_scaled")
+        dxn, gs = _tower_top_backward(model, model._vdesc, _f32(dfeat).reshape(-1, E), xN, hpost, mean_post, rstd_post,
+                                      "visual.ln_post", "visual.proj")
+        if rows is None:           # grid mode
+            dx = dxn if gs is None else ops.cast_scaled(dxn, xN.dtype, gs)
             stop = _tower_backward(model, model._vdesc, "visual", B, M, None, x0, lease, dx, None, None)
         else:
-            dx = _empty((M, D), sdt, dev)
+            dx = _empty((M, D), xN.dtype, dev)
             stop = _tower_backward(model, model._vdesc, "visual", B, M, None, x0, lease, dx, rows, dxn)
         lease.release()
         if stop > 0:      # everything below block `stop` is frozen, the input side included: ln_pre, the embedding sums and the
             #               conv1 weight gradient have no reader
-            if model.grad_sync is not None:
-                model.grad_sync(model, "visual")
-            _publish_to_main(ctx)
-            return None, None, None, None, None
+            return _tower_backward_done(ctx, "visual", 5)
         # ln_pre: x0 = LN(xpre); its dy is the gradient stream
-        dxpre = _empty((M, D), torch.float32, dev)
-        check(cl.ce_layernorm_bwd_t(ptr(dx), c_int(ST), c_long(D), ptr(xpre), c_int(L.T_F32), c_long(D), None, ptr(mean_pre),
-                                    ptr(rstd_pre), ptr(P["visual.ln_pre.weight"]), None, c_int(L.T_F32), ptr(dxpre),
-                                    c_int(L.T_F32), c_long(D), None, c_long(0), ptr(G("visual.ln_pre.weight")),
-                                    ptr(G("visual.ln_pre.bias")), None, ptr(gs), c_int(M), c_int(D), s),
-              "ce_layernorm_bwd(ln_pre)")
+        dxpre = ops.layernorm_bwd_t(dx, xpre, mean_pre, rstd_pre, P["visual.ln_pre.weight"], G("visual.ln_pre.weight"),
+                                    G("visual.ln_pre.bias"), _empty((M, D), torch.float32, dev), gscale=gs)
         # positional / class embedding gradients: sums over the batch axis
-        check(cl.ce_batch_reduce(ptr(dxpre), ptr(G("visual.positional_embedding")), c_int(B), c_long(T * D),
-                                 c_long(T * D), c_int(1), s), "ce_batch_reduce(pos)")
-        check(cl.ce_batch_reduce(ptr(dxpre), ptr(G("visual.class_embedding")), c_int(B), c_long(T * D), c_long(D),
-                                 c_int(1), s), "ce_batch_reduce(cls)")
+        check(cl.ce_batch_reduce(ptr(dxpre), ptr(G("visual.positional_embedding")), B, T * D, T * D, 1, s),
+              "ce_batch_reduce(pos)")
+        check(cl.ce_batch_reduce(ptr(dxpre), ptr(G("visual.class_embedding")), B, T * D, D, 1, s), "ce_batch_reduce(cls)")
         # conv1 weight gradient: dW[width, 3*p*p] += dpatch^T patches   (no input gradient is ever needed)
         dpatch = _empty((B * g * g, D), torch.bfloat16, dev)
-        check(cl.ce_vision_assemble_bwd(ptr(dxpre), ptr(dpatch), c_int(B), c_int(T), c_int(D), s), "ce_vision_assemble_bwd")
-        if model._conv_pad is None:
-            check(cl.ce_gemm_tn(ptr(dpatch), c_long(D), ptr(patches), c_long(model._kp), c_int(B * g * g), c_int(D),
-                                c_int(model._kp), ptr(G("visual.conv1.weight")), c_long(model._kp), c_int(0), s),
-                  "ce_gemm_tn(conv1)")
+        check(cl.ce_vision_assemble_bwd(ptr(dxpre), ptr(dpatch), B, T, D, s), "ce_vision_assemble_bwd")
+        if model._conv_pad is None:        # the gradient view has the weight's 4-D shape: its rows are model._kp apart
+            ops.gemm_tn(dpatch, patches, G("visual.conv1.weight"), ldo=model._kp)
         else:       # padded patch columns (model._build_device_tables): gradient through a padded scratch
             gp = model._conv_gpad
             gp.zero_()
-            check(cl.ce_gemm_tn(ptr(dpatch), c_long(D), ptr(patches), c_long(model._kp), c_int(B * g * g), c_int(D),
-                                c_int(model._kp), ptr(gp), c_long(model._kp), c_int(0), s), "ce_gemm_tn(conv1, padded)")
-            check(cl.ce_add_cols(ptr(gp), c_long(model._kp), ptr(G("visual.conv1.weight")), c_long(model._kp_real), c_int(D),
-                                 c_int(model._kp_real), s), "ce_add_cols(conv1)")
-        if model.grad_sync is not None:
-            model.grad_sync(model, "visual")
-        _publish_to_main(ctx)
-        return None, None, None, None, None
+            ops.gemm_tn(dpatch, patches, gp)
+            check(cl.ce_add_cols(ptr(gp), model._kp, ptr(G("visual.conv1.weight")), model._kp_real, D, model._kp_real, s),
+                  "ce_add_cols(conv1)")
+        return _tower_backward_done(ctx, "visual", 5)
 
 
 class EncodeTextFn(torch.autograd.Function):
@@ -419,33 +394,23 @@ class EncodeTextFn(torch.autograd.Function):
         n, T = text.shape
         if T != model.context_length:
             raise RuntimeError(f"expected {model.context_length} tokens per row, got {T}")
-        D, E = model.transformer.width, model.embed_dim
+        D = model.transformer.width
         P = model._pmap
         pk = text_packing(model, text)
         M = pk.rows                                        # activation rows: live tokens only when packed
         sdt, ST = _stream_type(model)                      # residual stream: fp32, or fp16 (model.stream16)
         x0 = _empty((M, D), sdt, dev)
         check(cl.ce_token_embed_t(ptr(text), ptr(pk.src), ptr(P["token_embedding.weight"]), ptr(P["positional_embedding"]),
-                                  ptr(x0), c_int(ST), c_long(M), c_int(T), c_int(D), c_int(model.vocab_size), s),
-              "ce_token_embed")
+                                  ptr(x0), ST, M, T, D, model.vocab_size, s), "ce_token_embed")
         rows = pk.sel                                      # EOT row of each caption (argmax token id, model_clip.py:415)
         xN = _empty((n, D), sdt, dev)                      # pruned last block: only the EOT rows are produced
         if infer:                  # grad mode was off at the call (CLIP.encode_text): no stash, nothing kept for a backward
             _tower_forward_infer(model, model._tdesc, "text", n, M, pk.cu, x0, xN, rows)
         else:
             lease = _tower_workspace(model, model._tdesc, n, "text")
-            check(cl.ce_tower_forward(ctypes.byref(model._tdesc), c_int(n), c_int(M), ptr(pk.cu), ptr(x0), ptr(lease.buf),
-                                      ptr(xN), ptr(rows), s), "ce_tower_forward(text)")
-        hfin = _empty((n, D), torch.bfloat16, dev)
-        mean_f, rstd_f = _empty((n,), torch.float32, dev), _empty((n,), torch.float32, dev)
-        check(cl.ce_layernorm_fwd_t(ptr(xN), c_int(ST), c_long(D), None, ptr(P["ln_final.weight"]), ptr(P["ln_final.bias"]),
-                                    ptr(hfin), c_int(L.T_BF16), c_long(D), ptr(mean_f), ptr(rstd_f), c_int(n), c_int(D),
-                                    c_float(1e-5), s), "ce_layernorm_fwd(ln_final)")
-        feat = _empty((n, E), torch.float32, dev)
-        wp = model._w16t["text_projection"]                   # [E, D]
-        check(cl.ce_gemm_nt(ptr(hfin), c_long(D), ptr(wp), c_long(D), c_int(n), c_int(E), c_int(D), c_int(L.EPI_F32),
-                            None, None, c_long(0), ptr(feat), c_long(E), None, c_long(0), None, c_long(0), s),
-              "ce_gemm_nt(text_projection)")
+            check(cl.ce_tower_forward(ctypes.byref(model._tdesc), n, M, ptr(pk.cu), ptr(x0), ptr(lease.buf), ptr(xN), ptr(rows),
+                                      s), "ce_tower_forward(text)")
+        feat, hfin, mean_f, rstd_f = _tower_top_forward(model, xN, "ln_final", "text_projection")
         if infer:
             return feat
         ctx.model, ctx.lease, ctx.n = model, lease, n
@@ -462,58 +427,65 @@ class EncodeTextFn(torch.autograd.Function):
         cl, s = lib(), stream()
         text, x0, xN, pk, hfin, mean_f, rstd_f = ctx.saved
         dev = model._flat.device
-        T, D, E = model.context_length, model.transformer.width, model.embed_dim
+        T, D = model.context_length, model.transformer.width
         M, rows = pk.rows, pk.sel
         model._attach_grads()
-        P, G = model._pmap, model._gview
-        dfeat = _f32(dfeat)
-        dfb = _empty((n, E), torch.bfloat16, dev)
-        check(cl.ce_cast_bf16(ptr(dfeat), ptr(dfb), c_long(n * E), s), "ce_cast_bf16")
-        dh = _empty((n, D), torch.bfloat16, dev)
-        check(cl.ce_gemm_nt(ptr(dfb), c_long(E), ptr(model._w16["text_projection"]), c_long(E), c_int(n), c_int(D),
-                            c_int(E), c_int(L.EPI_BF16), None, None, c_long(0), ptr(dh), c_long(D), None, c_long(0), None,
-                            c_long(0), s), "ce_gemm_nt(dtext_projection)")
-        check(cl.ce_gemm_tn(ptr(hfin), c_long(D), ptr(dfb), c_long(E), c_int(n), c_int(D), c_int(E),
-                            ptr(G("text_projection")), c_long(E), c_int(0), s), "ce_gemm_tn(text_projection)")
+        G = model._gview
         _check_stream(ctx, model)
-        sdt, ST = _stream_type(model)
-        dxn = _empty((n, D), torch.float32, dev)           # [n, D] gradient at the EOT rows (dx_sel of the pruned tower: fp32)
-        check(cl.ce_layernorm_bwd_t(ptr(dh), c_int(L.T_BF16), c_long(D), ptr(xN), c_int(ST), c_long(D), None, ptr(mean_f),
-                                    ptr(rstd_f), ptr(P["ln_final.weight"]), None, c_int(L.T_F32), ptr(dxn), c_int(L.T_F32),
-                                    c_long(D), None, c_long(0), ptr(G("ln_final.weight")), ptr(G("ln_final.bias")), None,
-                                    None, c_int(n), c_int(D), s), "ce_layernorm_bwd(ln_final)")
-        gs = _grad_scale(model, model._tdesc, dxn)
-        dx = _empty((M, D), sdt, dev)
+        # dxn: [n, D] gradient at the EOT rows (dx_sel of the pruned tower: fp32)
+        dxn, gs = _tower_top_backward(model, model._tdesc, _f32(dfeat), xN, hfin, mean_f, rstd_f, "ln_final", "text_projection")
+        dx = _empty((M, D), xN.dtype, dev)
         stop = _tower_backward(model, model._tdesc, "text", n, M, pk.cu, x0, lease, dx, rows, dxn)
         lease.release()
         if stop > 0:      # as in EncodeImageFn.backward: no stream cast, no positional sum, no token-embedding scatter
-            if model.grad_sync is not None:
-                model.grad_sync(model, "text")
-            _publish_to_main(ctx)
-            return None, None, None, None
-        if sdt != torch.float32:      # the embedding gradients below take the fp32 gradient in true units
-            dx32 = _empty((M, D), torch.float32, dev)
-            check(cl.ce_cast_scaled(ptr(dx), c_int(ST), ptr(dx32), c_int(L.T_F32), ptr(gs), c_int(1), c_long(M * D), s),
-                  "ce_cast_scaled")
-            dx = dx32
+            return _tower_backward_done(ctx, "text", 4)
+        if gs is not None:            # the embedding gradients below take the fp32 gradient in true units
+            dx = ops.cast_scaled(dx, torch.float32, gs, divide=True)
         if pk.cu is None:
-            check(cl.ce_batch_reduce(ptr(dx), ptr(G("positional_embedding")), c_int(n), c_long(T * D), c_long(T * D),
-                                     c_int(1), s), "ce_batch_reduce(text pos)")
+            check(cl.ce_batch_reduce(ptr(dx), ptr(G("positional_embedding")), n, T * D, T * D, 1, s), "ce_batch_reduce(text pos)")
         else:
-            check(cl.ce_pos_embed_bwd_packed(ptr(dx), ptr(pk.cu), ptr(G("positional_embedding")), c_int(n), c_int(T),
-                                             c_int(D), s), "ce_pos_embed_bwd_packed")
-        check(cl.ce_token_embed_bwd(ptr(text), ptr(pk.src), ptr(dx), ptr(G("token_embedding.weight")), c_long(M), c_int(D),
-                                    c_int(model.vocab_size), s), "ce_token_embed_bwd")
-        if model.grad_sync is not None:
-            model.grad_sync(model, "text")
-        _publish_to_main(ctx)
-        return None, None, None, None
+            check(cl.ce_pos_embed_bwd_packed(ptr(dx), ptr(pk.cu), ptr(G("positional_embedding")), n, T, D, s),
+                  "ce_pos_embed_bwd_packed")
+        check(cl.ce_token_embed_bwd(ptr(text), ptr(pk.src), ptr(dx), ptr(G("token_embedding.weight")), M, D, model.vocab_size, s),
+              "ce_token_embed_bwd")
+        return _tower_backward_done(ctx, "text", 4)
 
 
 def _sgemm(A, sam, sak, Bm, sbk, sbn, C, M, N, K, alpha_ptr=None, alpha=1.0, alpha_exp=0, beta=0.0):
-    check(lib().ce_sgemm(ptr(A), c_long(sam), c_long(sak), ptr(Bm), c_long(sbk), c_long(sbn), ptr(C), c_long(C.stride(0)),
-                         c_int(M), c_int(N), c_int(K), ptr(alpha_ptr), c_float(alpha), c_int(alpha_exp), c_float(beta),
-                         stream()), "ce_sgemm")
+    check(lib().ce_sgemm(ptr(A), sam, sak, ptr(Bm), sbk, sbn, ptr(C), C.stride(0), M, N, K, ptr(alpha_ptr), alpha, alpha_exp,
+                         beta, stream()), "ce_sgemm")
+
+
+def _l2norm(f):
+    """(f / |f| row by row, 1 / |f|) of a contiguous fp32 matrix (``ce_l2norm_fwd``)."""
+    n, E = f.shape
+    y, inv = torch.empty_like(f), _empty((n,), torch.float32, f.device)
+    check(lib().ce_l2norm_fwd(ptr(f), E, ptr(y), E, ptr(inv), n, E, stream()), "ce_l2norm_fwd")
+    return y, inv
+
+
+def _l2norm_bwd(dy, y, inv):
+    """Gradient w.r.t. f of ``y, inv = _l2norm(f)`` for the gradient ``dy`` w.r.t. y (``ce_l2norm_bwd``)."""
+    n, E = y.shape
+    df = torch.empty_like(y)
+    check(lib().ce_l2norm_bwd(ptr(dy), E, ptr(y), E, ptr(inv), ptr(df), E, n, E, 0, stream()), "ce_l2norm_bwd")
+    return df
+
+
+def _index64(t, dev):
+    """Labels / ``index_pos`` rows as the kernels read them: contiguous int64 on ``dev`` (None stays None)."""
+    return None if t is None else t.to(device=dev, dtype=torch.int64).contiguous()
+
+
+def _infonce_workspace(nq: int, dev):
+    return _empty((lib().ce_infonce_workspace_bytes(nq),), torch.uint8, dev)
+
+
+def _small_head_workspace(nI: int, nT: int, nsel: int, E: int, dev):
+    """(workspace of ``ce_head_small_fwd``, index of its four result scalars)."""
+    cl = lib()
+    return (_empty((cl.ce_head_small_workspace_floats(nI, nT, nsel, E),), torch.float32, dev),
+            cl.ce_head_small_scalars_offset(nI, nT, nsel, E))
 
 
 class LogitsFn(torch.autograd.Function):
@@ -529,10 +501,8 @@ class LogitsFn(torch.autograd.Function):
         fi, ft = _f32(fi), _f32(ft)
         B, E = fi.shape
         N = ft.shape[0]
-        In, Tn = torch.empty_like(fi), torch.empty_like(ft)
-        inv_i, inv_t = _empty((B,), torch.float32, dev), _empty((N,), torch.float32, dev)
-        check(cl.ce_l2norm_fwd(ptr(fi), c_long(E), ptr(In), c_long(E), ptr(inv_i), c_int(B), c_int(E), s), "ce_l2norm_fwd")
-        check(cl.ce_l2norm_fwd(ptr(ft), c_long(E), ptr(Tn), c_long(E), ptr(inv_t), c_int(N), c_int(E), s), "ce_l2norm_fwd")
+        In, inv_i = _l2norm(fi)
+        Tn, inv_t = _l2norm(ft)
         ls = logit_scale.detach().reshape(1)
         lpt = None
         # both matrices over the batch from the same features: logits_per_text IS logits_per_image^T (the same products summed in
@@ -553,8 +523,7 @@ class LogitsFn(torch.autograd.Function):
                 raise RuntimeError("per-instance logits need the same number of descriptions per image")
             K = N // B
             lpi = _empty((B, K), torch.float32, dev)
-            check(cl.ce_instance_logits(ptr(In), ptr(Tn), ptr(ls), ptr(lpi), c_int(B), c_int(K), c_int(E), s),
-                  "ce_instance_logits")
+            check(cl.ce_instance_logits(ptr(In), ptr(Tn), ptr(ls), ptr(lpi), B, K, E, s), "ce_instance_logits")
         # the logits are this node's OUTPUTS: keeping the tensors themselves on ctx would close a cycle through their
         # grad_fn (= ctx) that Python's collector cannot see, and every step's whole graph (both towers' activation
         # stashes) would stay alive; detached aliases share the storage without the back edge
@@ -578,30 +547,24 @@ class LogitsFn(torch.autograd.Function):
             G = torch.add(_f32(dlpi), _f32(dlpt).t())
             _sgemm(G, N, 1, Tn, E, 1, dIn, B, E, N, alpha_ptr=ls, alpha_exp=1)
             _sgemm(G, 1, N, In, E, 1, dTn, N, E, B, alpha_ptr=ls, alpha_exp=1)
-            check(cl.ce_dot(ptr(G), ptr(lpi), c_long(G.numel()), ptr(dls), s), "ce_dot")
+            check(cl.ce_dot(ptr(G), ptr(lpi), G.numel(), ptr(dls), s), "ce_dot")
             dlpi = dlpt = None
         if dlpt is not None:
             dlpt = _f32(dlpt)
             # lpt = s T I^T : dT += s dlpt I ; dI += s dlpt^T T
             _sgemm(dlpt, B, 1, In, E, 1, dTn, N, E, B, alpha_ptr=ls, alpha_exp=1, beta=1.0)
             _sgemm(dlpt, 1, B, Tn, E, 1, dIn, B, E, N, alpha_ptr=ls, alpha_exp=1, beta=1.0)
-            check(cl.ce_dot(ptr(dlpt), ptr(lpt), c_long(N * B), ptr(dls), s), "ce_dot")
+            check(cl.ce_dot(ptr(dlpt), ptr(lpt), N * B, ptr(dls), s), "ce_dot")
         if dlpi is not None:
             dlpi = _f32(dlpi)
             if ctx.overbatch:
                 _sgemm(dlpi, N, 1, Tn, E, 1, dIn, B, E, N, alpha_ptr=ls, alpha_exp=1, beta=1.0)
                 _sgemm(dlpi, 1, N, In, E, 1, dTn, N, E, B, alpha_ptr=ls, alpha_exp=1, beta=1.0)
             else:
-                K = N // B
-                check(cl.ce_instance_logits_bwd(ptr(dlpi), ptr(In), ptr(Tn), ptr(ls), ptr(dIn), ptr(dTn), c_int(B),
-                                                c_int(K), c_int(E), s), "ce_instance_logits_bwd")
-            check(cl.ce_dot(ptr(dlpi), ptr(lpi), c_long(dlpi.numel()), ptr(dls), s), "ce_dot")
-        dfi, dft = torch.empty_like(In), torch.empty_like(Tn)
-        check(cl.ce_l2norm_bwd(ptr(dIn), c_long(E), ptr(In), c_long(E), ptr(inv_i), ptr(dfi), c_long(E), c_int(B), c_int(E),
-                               c_int(0), s), "ce_l2norm_bwd")
-        check(cl.ce_l2norm_bwd(ptr(dTn), c_long(E), ptr(Tn), c_long(E), ptr(inv_t), ptr(dft), c_long(E), c_int(N), c_int(E),
-                               c_int(0), s), "ce_l2norm_bwd")
-        return dfi, dft, dls.reshape(()), None, None
+                check(cl.ce_instance_logits_bwd(ptr(dlpi), ptr(In), ptr(Tn), ptr(ls), ptr(dIn), ptr(dTn), B, N // B, E, s),
+                      "ce_instance_logits_bwd")
+            check(cl.ce_dot(ptr(dlpi), ptr(lpi), dlpi.numel(), ptr(dls), s), "ce_dot")
+        return _l2norm_bwd(dIn, In, inv_i), _l2norm_bwd(dTn, Tn, inv_t), dls.reshape(()), None, None
 
 
 def logits_from_features(image_features, text_features, logit_scale, overbatch: bool = True, want: str = "both"):
@@ -617,44 +580,33 @@ class InfoNCEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, logit_scale, labels, sel):
-        cl, s = lib(), stream()
         dev = q.device
         q, k = _f32(q), _f32(k)
         E = q.shape[1]
-        qn, kn = torch.empty_like(q), torch.empty_like(k)
-        inv_q, inv_k = _empty((q.shape[0],), torch.float32, dev), _empty((k.shape[0],), torch.float32, dev)
-        check(cl.ce_l2norm_fwd(ptr(q), c_long(E), ptr(qn), c_long(E), ptr(inv_q), c_int(q.shape[0]), c_int(E), s), "ce_l2norm_fwd")
-        check(cl.ce_l2norm_fwd(ptr(k), c_long(E), ptr(kn), c_long(E), ptr(inv_k), c_int(k.shape[0]), c_int(E), s), "ce_l2norm_fwd")
-        labels = labels.to(device=dev, dtype=torch.int64).contiguous()
-        sel = sel.to(device=dev, dtype=torch.int64).contiguous() if sel is not None else None
+        qn, inv_q = _l2norm(q)
+        kn, inv_k = _l2norm(k)
+        labels, sel = _index64(labels, dev), _index64(sel, dev)
         nq = q.shape[0] if sel is None else sel.shape[0]
         ls = logit_scale.detach().reshape(1)
         lse = _empty((nq,), torch.float32, dev)
         loss = torch.zeros((), dtype=torch.float32, device=dev)
-        cl.ce_infonce_workspace_bytes.restype = ctypes.c_size_t
-        ws = _empty((int(cl.ce_infonce_workspace_bytes(c_int(nq))),), torch.uint8, dev)
-        check(cl.ce_infonce_fwd(ptr(qn), c_long(E), ptr(sel), c_int(nq), ptr(kn), c_long(E), c_int(k.shape[0]), c_int(E),
-                                ptr(ls), ptr(labels), ptr(lse), ptr(loss), ptr(ws), s), "ce_infonce_fwd")
+        ws = _infonce_workspace(nq, dev)
+        check(lib().ce_infonce_fwd(ptr(qn), E, ptr(sel), nq, ptr(kn), E, k.shape[0], E, ptr(ls), ptr(labels), ptr(lse), ptr(loss),
+                                   ptr(ws), stream()), "ce_infonce_fwd")
         ctx.saved = (qn, kn, inv_q, inv_k, ls, labels, sel, lse)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        cl, s = lib(), stream()
         qn, kn, inv_q, inv_k, ls, labels, sel, lse = ctx.saved
         E = qn.shape[1]
         nq = qn.shape[0] if sel is None else sel.shape[0]
         g = g.contiguous().float().reshape(1)
         dqn, dkn = torch.zeros_like(qn), torch.zeros_like(kn)
         dls = torch.zeros(1, dtype=torch.float32, device=qn.device)
-        check(cl.ce_infonce_bwd(ptr(qn), c_long(E), ptr(sel), c_int(nq), ptr(kn), c_long(E), c_int(kn.shape[0]), c_int(E),
-                                ptr(ls), ptr(labels), ptr(lse), ptr(g), ptr(dqn), ptr(dkn), ptr(dls), s), "ce_infonce_bwd")
-        dq, dk = torch.empty_like(qn), torch.empty_like(kn)
-        check(cl.ce_l2norm_bwd(ptr(dqn), c_long(E), ptr(qn), c_long(E), ptr(inv_q), ptr(dq), c_long(E), c_int(qn.shape[0]),
-                               c_int(E), c_int(0), s), "ce_l2norm_bwd")
-        check(cl.ce_l2norm_bwd(ptr(dkn), c_long(E), ptr(kn), c_long(E), ptr(inv_k), ptr(dk), c_long(E), c_int(kn.shape[0]),
-                               c_int(E), c_int(0), s), "ce_l2norm_bwd")
-        return dq, dk, dls.reshape(()), None, None
+        check(lib().ce_infonce_bwd(ptr(qn), E, ptr(sel), nq, ptr(kn), E, kn.shape[0], E, ptr(ls), ptr(labels), ptr(lse), ptr(g),
+                                   ptr(dqn), ptr(dkn), ptr(dls), stream()), "ce_infonce_bwd")
+        return _l2norm_bwd(dqn, qn, inv_q), _l2norm_bwd(dkn, kn, inv_k), dls.reshape(()), None, None
 
 
 def fused_head_ok(embed_dim: int) -> bool:
@@ -674,24 +626,19 @@ class InfoNCEPairFn(torch.autograd.Function):
         dev = fi.device
         fi, ft = _f32(fi), _f32(ft)
         E = fi.shape[1]
-        In, Tn = torch.empty_like(fi), torch.empty_like(ft)
-        inv_i, inv_t = _empty((fi.shape[0],), torch.float32, dev), _empty((ft.shape[0],), torch.float32, dev)
-        check(cl.ce_l2norm_fwd(ptr(fi), c_long(E), ptr(In), c_long(E), ptr(inv_i), c_int(fi.shape[0]), c_int(E), s), "ce_l2norm_fwd")
-        check(cl.ce_l2norm_fwd(ptr(ft), c_long(E), ptr(Tn), c_long(E), ptr(inv_t), c_int(ft.shape[0]), c_int(E), s), "ce_l2norm_fwd")
-        labels_i = labels_i.to(device=dev, dtype=torch.int64).contiguous()
-        labels_t = labels_t.to(device=dev, dtype=torch.int64).contiguous()
-        sel = sel.to(device=dev, dtype=torch.int64).contiguous() if sel is not None else None
+        In, inv_i = _l2norm(fi)
+        Tn, inv_t = _l2norm(ft)
+        labels_i, labels_t, sel = _index64(labels_i, dev), _index64(labels_t, dev), _index64(sel, dev)
         nqi = fi.shape[0]
         nqt = ft.shape[0] if sel is None else sel.shape[0]
         ls = logit_scale.detach().reshape(1)
         lse_i, lse_t = _empty((nqi,), torch.float32, dev), _empty((nqt,), torch.float32, dev)
         losses = torch.zeros(2, dtype=torch.float32, device=dev)
-        cl.ce_infonce_workspace_bytes.restype = ctypes.c_size_t
-        ws = _empty((int(cl.ce_infonce_workspace_bytes(c_int(max(nqi, nqt)))),), torch.uint8, dev)
-        check(cl.ce_infonce_fwd(ptr(In), c_long(E), None, c_int(nqi), ptr(Tn), c_long(E), c_int(ft.shape[0]), c_int(E), ptr(ls),
-                                ptr(labels_i), ptr(lse_i), ptr(losses[0:1]), ptr(ws), s), "ce_infonce_fwd(image)")
-        check(cl.ce_infonce_fwd(ptr(Tn), c_long(E), ptr(sel), c_int(nqt), ptr(In), c_long(E), c_int(fi.shape[0]), c_int(E), ptr(ls),
-                                ptr(labels_t), ptr(lse_t), ptr(losses[1:2]), ptr(ws), s), "ce_infonce_fwd(text)")
+        ws = _infonce_workspace(max(nqi, nqt), dev)
+        check(cl.ce_infonce_fwd(ptr(In), E, None, nqi, ptr(Tn), E, ft.shape[0], E, ptr(ls), ptr(labels_i), ptr(lse_i),
+                                ptr(losses[0:1]), ptr(ws), s), "ce_infonce_fwd(image)")
+        check(cl.ce_infonce_fwd(ptr(Tn), E, ptr(sel), nqt, ptr(In), E, fi.shape[0], E, ptr(ls), ptr(labels_t), ptr(lse_t),
+                                ptr(losses[1:2]), ptr(ws), s), "ce_infonce_fwd(text)")
         ctx.saved = (In, Tn, inv_i, inv_t, ls, labels_i, labels_t, sel, lse_i, lse_t)
         return losses[0], losses[1]
 
@@ -707,16 +654,11 @@ class InfoNCEPairFn(torch.autograd.Function):
         g = torch.stack([zero[0] if g_i is None else g_i.float().reshape(()), zero[1] if g_t is None else g_t.float().reshape(())])
         acc = torch.zeros(In.numel() + Tn.numel() + 4, dtype=torch.float32, device=dev)         # dIn | dTn | dlogit_scale: one fill
         dIn, dTn, dls = acc[:In.numel()].view_as(In), acc[In.numel():In.numel() + Tn.numel()].view_as(Tn), acc[In.numel() + Tn.numel():]
-        check(cl.ce_infonce_bwd(ptr(In), c_long(E), None, c_int(nqi), ptr(Tn), c_long(E), c_int(Tn.shape[0]), c_int(E), ptr(ls),
-                                ptr(labels_i), ptr(lse_i), ptr(g[0:1]), ptr(dIn), ptr(dTn), ptr(dls), s), "ce_infonce_bwd(image)")
-        check(cl.ce_infonce_bwd(ptr(Tn), c_long(E), ptr(sel), c_int(nqt), ptr(In), c_long(E), c_int(In.shape[0]), c_int(E), ptr(ls),
-                                ptr(labels_t), ptr(lse_t), ptr(g[1:2]), ptr(dTn), ptr(dIn), ptr(dls), s), "ce_infonce_bwd(text)")
-        dfi, dft = torch.empty_like(In), torch.empty_like(Tn)
-        check(cl.ce_l2norm_bwd(ptr(dIn), c_long(E), ptr(In), c_long(E), ptr(inv_i), ptr(dfi), c_long(E), c_int(In.shape[0]), c_int(E),
-                               c_int(0), s), "ce_l2norm_bwd")
-        check(cl.ce_l2norm_bwd(ptr(dTn), c_long(E), ptr(Tn), c_long(E), ptr(inv_t), ptr(dft), c_long(E), c_int(Tn.shape[0]), c_int(E),
-                               c_int(0), s), "ce_l2norm_bwd")
-        return dfi, dft, dls[0].reshape(()), None, None, None
+        check(cl.ce_infonce_bwd(ptr(In), E, None, nqi, ptr(Tn), E, Tn.shape[0], E, ptr(ls), ptr(labels_i), ptr(lse_i), ptr(g[0:1]),
+                                ptr(dIn), ptr(dTn), ptr(dls), s), "ce_infonce_bwd(image)")
+        check(cl.ce_infonce_bwd(ptr(Tn), E, ptr(sel), nqt, ptr(In), E, In.shape[0], E, ptr(ls), ptr(labels_t), ptr(lse_t), ptr(g[1:2]),
+                                ptr(dTn), ptr(dIn), ptr(dls), s), "ce_infonce_bwd(text)")
+        return _l2norm_bwd(dIn, In, inv_i), _l2norm_bwd(dTn, Tn, inv_t), dls[0].reshape(()), None, None, None
 
 
 def small_head_ok(fi, ft, index_pos) -> bool:
@@ -735,37 +677,29 @@ class SmallHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, fi, ft, logit_scale, labels_i, labels_t, sel):
-        cl, s = lib(), stream()
         dev = fi.device
         fi, ft = _f32(fi), _f32(ft)
         nI, E = fi.shape
         nT = ft.shape[0]
-        labels_i = labels_i.to(device=dev, dtype=torch.int64).contiguous()
-        labels_t = labels_t.to(device=dev, dtype=torch.int64).contiguous()
-        sel = sel.to(device=dev, dtype=torch.int64).contiguous() if sel is not None else None
+        labels_i, labels_t, sel = _index64(labels_i, dev), _index64(labels_t, dev), _index64(sel, dev)
         nsel = nT if sel is None else int(sel.shape[0])
-        cl.ce_head_small_workspace_floats.restype = ctypes.c_size_t
-        cl.ce_head_small_scalars_offset.restype = ctypes.c_size_t
-        dims = (c_int(nI), c_int(nT), c_int(nsel), c_int(E))
-        ws = _empty((int(cl.ce_head_small_workspace_floats(*dims)),), torch.float32, dev)
-        off = int(cl.ce_head_small_scalars_offset(*dims))
+        ws, off = _small_head_workspace(nI, nT, nsel, E, dev)
         ls = logit_scale.detach().reshape(1)
-        check(cl.ce_head_small_fwd(ptr(fi), ptr(ft), c_int(nI), c_int(nT), c_int(E), ptr(ls), ptr(labels_i), ptr(labels_t), ptr(sel),
-                                   c_int(nsel), ptr(ws), s), "ce_head_small_fwd")
+        check(lib().ce_head_small_fwd(ptr(fi), ptr(ft), nI, nT, E, ptr(ls), ptr(labels_i), ptr(labels_t), ptr(sel), nsel, ptr(ws),
+                                      stream()), "ce_head_small_fwd")
         ctx.saved = (ws, ls, sel, (nI, nT, nsel, E))
         return ws[off], ws[off + 1]
 
     @staticmethod
     def backward(ctx, g_i, g_t):
-        cl, s = lib(), stream()
         ws, ls, sel, (nI, nT, nsel, E) = ctx.saved
         dev = ws.device
         g_i = None if g_i is None else g_i.float()
         g_t = None if g_t is None else g_t.float()
         dfi, dft = _empty((nI, E), torch.float32, dev), _empty((nT, E), torch.float32, dev)
         dls = _empty((1,), torch.float32, dev)
-        check(cl.ce_head_small_bwd(c_int(nI), c_int(nT), c_int(nsel), c_int(E), ptr(ls), ptr(g_i), ptr(g_t), ptr(sel), ptr(ws),
-                                   ptr(dfi), ptr(dft), ptr(dls), s), "ce_head_small_bwd")
+        check(lib().ce_head_small_bwd(nI, nT, nsel, E, ptr(ls), ptr(g_i), ptr(g_t), ptr(sel), ptr(ws), ptr(dfi), ptr(dft), ptr(dls),
+                                      stream()), "ce_head_small_bwd")
         return dfi, dft, dls.reshape(()), None, None, None
 
 

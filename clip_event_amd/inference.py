@@ -7,7 +7,6 @@ probabilities (``zero_shot_topk``) and image<->text retrieval numbers (``retriev
 which sweeps the similarity tiles and never writes the [B, N] matrix."""
 from __future__ import annotations
 
-from ctypes import c_int, c_long
 from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -36,13 +35,8 @@ class TopK(NamedTuple):
 
 
 def _l2norm(x: torch.Tensor) -> torch.Tensor:
-    from ._lib import check, lib, ptr, stream
-    x = x.detach().float().contiguous()
-    n, E = x.shape
-    y = torch.empty_like(x)
-    inv = torch.empty(n, dtype=torch.float32, device=x.device)
-    check(lib().ce_l2norm_fwd(ptr(x), c_long(E), ptr(y), c_long(E), ptr(inv), c_int(n), c_int(E), stream()), "ce_l2norm_fwd")
-    return y
+    from . import functional as F
+    return F._l2norm(x.detach().float().contiguous())[0]
 
 
 @torch.no_grad()

@@ -2,8 +2,6 @@
 on the HIP kernels of head.hip / ot.hip."""
 from __future__ import annotations
 
-from ctypes import c_int, c_long
-
 import torch
 from torch import nn
 
@@ -25,8 +23,8 @@ class _CrossEntropyFn(torch.autograd.Function):
         C = logits.shape[1]
         lse = torch.empty(nrows, dtype=torch.float32, device=logits.device)
         loss = torch.zeros((), dtype=torch.float32, device=logits.device)
-        check(lib().ce_xent_fwd(ptr(logits), c_long(logits.stride(0)), ptr(labels), ptr(sel), ptr(lse), ptr(loss),
-                                c_int(nrows), c_int(C), stream()), "ce_xent_fwd")
+        check(lib().ce_xent_fwd(ptr(logits), logits.stride(0), ptr(labels), ptr(sel), ptr(lse), ptr(loss),
+                                nrows, C, stream()), "ce_xent_fwd")
         ctx.saved = (logits, labels, sel, lse)
         return loss
 
@@ -36,8 +34,8 @@ class _CrossEntropyFn(torch.autograd.Function):
         nrows = logits.shape[0] if sel is None else sel.shape[0]
         d = torch.zeros_like(logits) if sel is not None else torch.empty_like(logits)
         g = g.contiguous().float()
-        check(lib().ce_xent_bwd(ptr(logits), c_long(logits.stride(0)), ptr(labels), ptr(sel), ptr(lse), ptr(g), ptr(d),
-                                c_long(d.stride(0)), c_int(nrows), c_int(logits.shape[1]), stream()), "ce_xent_bwd")
+        check(lib().ce_xent_bwd(ptr(logits), logits.stride(0), ptr(labels), ptr(sel), ptr(lse), ptr(g), ptr(d),
+                                d.stride(0), nrows, logits.shape[1], stream()), "ce_xent_bwd")
         return d, None, None
 
 
@@ -55,7 +53,7 @@ class _ElemLossFn(torch.autograd.Function):
         if x.shape != y.shape:
             raise RuntimeError(f"target size {tuple(y.shape)} must match input size {tuple(x.shape)}")
         loss = torch.zeros((), dtype=torch.float32, device=x.device)
-        check(lib().ce_elem_loss_fwd(ptr(x), ptr(y), c_long(x.numel()), c_int(mode), ptr(loss), stream()), "ce_elem_loss_fwd")
+        check(lib().ce_elem_loss_fwd(ptr(x), ptr(y), x.numel(), mode, ptr(loss), stream()), "ce_elem_loss_fwd")
         ctx.saved, ctx.mode = (x, y), mode
         return loss
 
@@ -64,7 +62,7 @@ class _ElemLossFn(torch.autograd.Function):
         x, y = ctx.saved
         dx = torch.empty_like(x)
         g = g.contiguous().float()
-        check(lib().ce_elem_loss_bwd(ptr(x), ptr(y), c_long(x.numel()), c_int(ctx.mode), ptr(g), ptr(dx), stream()),
+        check(lib().ce_elem_loss_bwd(ptr(x), ptr(y), x.numel(), ctx.mode, ptr(g), ptr(dx), stream()),
               "ce_elem_loss_bwd")
         return dx, None, None
 

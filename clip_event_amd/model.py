@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from ctypes import c_float, c_int, c_long, c_void_p
+from ctypes import c_int, c_void_p
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -535,7 +535,7 @@ class CLIP(nn.Module):
 
     def _zero_segments(self, table):
         if table.shape[0]:
-            check(lib().ce_zero_segments(ptr(self._flat_grad), ptr(table), c_int(table.shape[0]), stream()), "ce_zero_segments")
+            check(lib().ce_zero_segments(ptr(self._flat_grad), ptr(table), table.shape[0], stream()), "ce_zero_segments")
 
     def zero_grad_first_touch(self):
         if self._flat_grad is None or os.environ.get("CE_WGRAD_FIRST_TOUCH", "1") == "0":
@@ -753,7 +753,6 @@ class CLIP(nn.Module):
 
         self._vdesc = desc("visual.transformer.", self.visual.transformer, self.visual.patch_num ** 2 + 1, False)
         self._tdesc = desc("transformer.", self.transformer, self.context_length, True)
-        lib().ce_tower_workspace_bytes.restype = ctypes.c_size_t
         self._w8 = None
         self._fp8_fresh = False
 
@@ -819,7 +818,7 @@ class CLIP(nn.Module):
             host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
             self._qjobs = host.to(self._flat.device)
             self._qjobs_n, self._qjobs_groups, self._qjobs_key = len(jobs), groups, key
-        check(cl.ce_quant_rows_fp8_multi(ptr(self._qjobs), c_int(self._qjobs_n), c_int(self._qjobs_groups), s),
+        check(cl.ce_quant_rows_fp8_multi(ptr(self._qjobs), self._qjobs_n, self._qjobs_groups, s),
               "ce_quant_rows_fp8_multi")
         self._fp8_fresh = True
 
@@ -840,9 +839,9 @@ class CLIP(nn.Module):
         if not (self._mirror_fresh and vers == self._mirror_versions):
             self.wait_transposes()        # an earlier asynchronous rebuild may still be reading the mirror
             # masters changed outside the fused optimiser: rebuild the whole bf16 mirror (one launch)
-            check(cl.ce_cast_bf16(ptr(self._flat), ptr(self._flat16), c_long(self._flat.numel()), s), "ce_cast_bf16")
+            check(cl.ce_cast_bf16(ptr(self._flat), ptr(self._flat16), self._flat.numel(), s), "ce_cast_bf16")
         tj, tn_, tt = self._tjobs
-        check(cl.ce_multi_transpose_bf16(ptr(tj), c_int(tn_), c_int(tt), s), "ce_multi_transpose_bf16")
+        check(cl.ce_multi_transpose_bf16(ptr(tj), tn_, tt, s), "ce_multi_transpose_bf16")
         tj, tn_, tt = self._tjobs_bwd
         if self._mirror_fresh and vers == self._mirror_versions and getattr(self, "_wt_fresh", False):
             pass                          # the fused Adam wrote the blocks' W^T copies with the update (ce_adam_step_tiles)
@@ -854,15 +853,15 @@ class CLIP(nn.Module):
                 self._aux_stream = torch.cuda.Stream(device=self._flat.device)
             self._aux_stream.wait_stream(cur)
             with torch.cuda.stream(self._aux_stream):
-                check(cl.ce_multi_transpose_bf16(ptr(tj), c_int(tn_), c_int(tt), stream()), "ce_multi_transpose_bf16(blocks)")
+                check(cl.ce_multi_transpose_bf16(ptr(tj), tn_, tt, stream()), "ce_multi_transpose_bf16(blocks)")
                 self._wt_event = torch.cuda.Event()
                 self._wt_event.record(self._aux_stream)
         else:
             self.wait_transposes()
-            check(cl.ce_multi_transpose_bf16(ptr(tj), c_int(tn_), c_int(tt), s), "ce_multi_transpose_bf16(blocks)")
+            check(cl.ce_multi_transpose_bf16(ptr(tj), tn_, tt, s), "ce_multi_transpose_bf16(blocks)")
         if self._conv_pad is not None:
-            check(cl.ce_cast_transpose(ptr(self._pmap["visual.conv1.weight"]), ptr(self._conv_pad), c_long(self._kp), None,
-                                       c_long(0), c_int(self.vision_width), c_int(self._kp_real), s), "ce_cast_transpose(conv1)")
+            check(cl.ce_cast_transpose(ptr(self._pmap["visual.conv1.weight"]), ptr(self._conv_pad), self._kp, None,
+                                       0, self.vision_width, self._kp_real, s), "ce_cast_transpose(conv1)")
         self._mirror_fresh = False
         self._wt_fresh = False
         self._versions = vers

@@ -4,7 +4,6 @@ the HIP library.  bf16 tensors are torch.bfloat16, residual/grad streams torch.f
 ``_t`` wrappers, model.stream16)."""
 from __future__ import annotations
 
-from ctypes import c_float, c_int, c_long, c_void_p
 from typing import Optional
 
 import torch
@@ -15,6 +14,12 @@ from ._lib import check, lib, ptr, stream
 
 def _rows(t: torch.Tensor) -> int:
     return t.shape[0]
+
+
+def _nt_tail(epilogue, bias, resid, out, out2, ldo2, aux):
+    """The arguments ``ce_gemm_nt``, ``ce_gemm_nt_fp8`` and ``ce_gemm_nt_mx8`` share, from ``epilogue`` on."""
+    return (epilogue, ptr(bias), ptr(resid), resid.stride(0) if resid is not None else 0, ptr(out), out.stride(0), ptr(out2),
+            ldo2, ptr(aux), aux.stride(0) if aux is not None else 0, stream())
 
 
 def gemm_nt(a: torch.Tensor, b: torch.Tensor, epilogue: int, *, bias=None, resid=None, out=None, out2=None,
@@ -33,20 +38,20 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, epilogue: int, *, bias=None, resid
                           dtype=torch.float16 if epilogue == L.EPI_BIAS_RESID_F16 else (torch.float32 if f32_out else torch.bfloat16))
     if epilogue == L.EPI_BIAS_GELU and out2 is None:
         out2 = torch.empty_like(out)
-    check(lib().ce_gemm_nt(ptr(a), c_long(a.stride(0)), ptr(b), c_long(b.stride(0)), c_int(M), c_int(N), c_int(K),
-                           c_int(epilogue), ptr(bias), ptr(resid), c_long(resid.stride(0) if resid is not None else 0),
-                           ptr(out), c_long(out.stride(0)), ptr(out2),
-                           c_long(0 if out2 is None else (N if out2.dim() == 1 else out2.stride(0))),   # 1-D: GELUGRAD column sums
-                           ptr(aux), c_long(aux.stride(0) if aux is not None else 0), stream()), "ce_gemm_nt")
+    ldo2 = 0 if out2 is None else (N if out2.dim() == 1 else out2.stride(0))        # 1-D: GELUGRAD column sums
+    check(lib().ce_gemm_nt(ptr(a), a.stride(0), ptr(b), b.stride(0), M, N, K,
+                           *_nt_tail(epilogue, bias, resid, out, out2, ldo2, aux)), "ce_gemm_nt")
     return (out, out2) if epilogue == L.EPI_BIAS_GELU else out
 
 
-def gemm_tn(p: torch.Tensor, q: torch.Tensor, out: torch.Tensor, splits: int = 0, M: Optional[int] = None):
-    """out[Nn,Kk] += p[M,Nn]^T @ q[M,Kk] (fp32 atomic accumulation)."""
+def gemm_tn(p: torch.Tensor, q: torch.Tensor, out: torch.Tensor, splits: int = 0, M: Optional[int] = None,
+            ldo: Optional[int] = None):
+    """out[Nn,Kk] += p[M,Nn]^T @ q[M,Kk] (fp32 atomic accumulation); ``ldo``: the row pitch of ``out`` when it is not
+    ``out.stride(0)`` (a 4-D convolution weight written as [Nn, Kk])."""
     assert p.dtype == torch.bfloat16 and q.dtype == torch.bfloat16 and out.dtype == torch.float32
     M = p.shape[0] if M is None else M
-    check(lib().ce_gemm_tn(ptr(p), c_long(p.stride(0)), ptr(q), c_long(q.stride(0)), c_int(M), c_int(p.shape[1]),
-                           c_int(q.shape[1]), ptr(out), c_long(out.stride(0)), c_int(splits), stream()), "ce_gemm_tn")
+    check(lib().ce_gemm_tn(ptr(p), p.stride(0), ptr(q), q.stride(0), M, p.shape[1], q.shape[1], ptr(out),
+                           out.stride(0) if ldo is None else ldo, splits, stream()), "ce_gemm_tn")
     return out
 
 
@@ -58,8 +63,8 @@ def layernorm_fwd(x: torch.Tensor, w, b, *, rows=None, out_f32=False, eps=1e-5, 
     y = torch.empty(M, D, device=x.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
     mean = torch.empty(M, device=x.device, dtype=torch.float32)
     rstd = torch.empty(M, device=x.device, dtype=torch.float32)
-    check(lib().ce_layernorm_fwd(ptr(x), c_long(x.stride(0)), ptr(rows), ptr(w), ptr(b), ptr(y), c_long(y.stride(0)),
-                                 c_int(1 if out_f32 else 0), ptr(mean), ptr(rstd), c_int(M), c_int(D), c_float(eps),
+    check(lib().ce_layernorm_fwd(ptr(x), x.stride(0), ptr(rows), ptr(w), ptr(b), ptr(y), y.stride(0),
+                                 1 if out_f32 else 0, ptr(mean), ptr(rstd), M, D, eps,
                                  stream()), "ce_layernorm_fwd")
     return y, mean, rstd
 
@@ -70,10 +75,10 @@ def layernorm_bwd(dy, x, mean, rstd, w, dw, db, *, rows=None, dx_in=None, dx_out
     D = dy.shape[1]
     if dx_out is None:
         dx_out = torch.zeros_like(x) if rows is not None else torch.empty_like(x)
-    check(lib().ce_layernorm_bwd(ptr(dy), c_long(dy.stride(0)), c_int(1 if dy.dtype == torch.float32 else 0), ptr(x),
-                                 c_long(x.stride(0)), ptr(rows), ptr(mean), ptr(rstd), ptr(w), ptr(dx_in), ptr(dx_out),
-                                 c_long(dx_out.stride(0)), ptr(dxb), c_long(dxb.stride(0) if dxb is not None else 0),
-                                 ptr(dw), ptr(db), ptr(dxsum), c_int(M), c_int(D), stream()), "ce_layernorm_bwd")
+    check(lib().ce_layernorm_bwd(ptr(dy), dy.stride(0), 1 if dy.dtype == torch.float32 else 0, ptr(x),
+                                 x.stride(0), ptr(rows), ptr(mean), ptr(rstd), ptr(w), ptr(dx_in), ptr(dx_out),
+                                 dx_out.stride(0), ptr(dxb), dxb.stride(0) if dxb is not None else 0,
+                                 ptr(dw), ptr(db), ptr(dxsum), M, D, stream()), "ce_layernorm_bwd")
     return dx_out
 
 
@@ -87,9 +92,9 @@ def layernorm_fwd_t(x: torch.Tensor, w, b, out_dtype=torch.bfloat16, *, rows=Non
     y = torch.empty(M, D, device=x.device, dtype=out_dtype)
     mean = torch.empty(M, device=x.device, dtype=torch.float32)
     rstd = torch.empty(M, device=x.device, dtype=torch.float32)
-    check(lib().ce_layernorm_fwd_t(ptr(x), c_int(_TYPE[x.dtype]), c_long(x.stride(0)), ptr(rows), ptr(w), ptr(b), ptr(y),
-                                   c_int(_TYPE[out_dtype]), c_long(y.stride(0)), ptr(mean), ptr(rstd), c_int(M), c_int(D),
-                                   c_float(eps), stream()), "ce_layernorm_fwd_t")
+    check(lib().ce_layernorm_fwd_t(ptr(x), _TYPE[x.dtype], x.stride(0), ptr(rows), ptr(w), ptr(b), ptr(y),
+                                   _TYPE[out_dtype], y.stride(0), ptr(mean), ptr(rstd), M, D,
+                                   eps, stream()), "ce_layernorm_fwd_t")
     return y, mean, rstd
 
 
@@ -97,12 +102,12 @@ def layernorm_bwd_t(dy, x, mean, rstd, w, dw, db, dx_out, *, gscale=None, rows=N
     """``layernorm_bwd`` with typed operands (ce_layernorm_bwd_t); fp16 gradient operands hold gradient * gscale[0]
     (``gscale``: a 1-element fp32 DEVICE tensor, see ``grad_scale``)."""
     M, D = dy.shape
-    check(lib().ce_layernorm_bwd_t(ptr(dy), c_int(_TYPE[dy.dtype]), c_long(dy.stride(0)), ptr(x), c_int(_TYPE[x.dtype]),
-                                   c_long(x.stride(0)), ptr(rows), ptr(mean), ptr(rstd), ptr(w), ptr(dx_in),
-                                   c_int(_TYPE[dx_in.dtype] if dx_in is not None else L.T_F32), ptr(dx_out),
-                                   c_int(_TYPE[dx_out.dtype]), c_long(dx_out.stride(0)), ptr(dxb),
-                                   c_long(dxb.stride(0) if dxb is not None else 0), ptr(dw), ptr(db), ptr(dxsum),
-                                   ptr(gscale), c_int(M), c_int(D), stream()), "ce_layernorm_bwd_t")
+    check(lib().ce_layernorm_bwd_t(ptr(dy), _TYPE[dy.dtype], dy.stride(0), ptr(x), _TYPE[x.dtype],
+                                   x.stride(0), ptr(rows), ptr(mean), ptr(rstd), ptr(w), ptr(dx_in),
+                                   _TYPE[dx_in.dtype] if dx_in is not None else L.T_F32, ptr(dx_out),
+                                   _TYPE[dx_out.dtype], dx_out.stride(0), ptr(dxb),
+                                   dxb.stride(0) if dxb is not None else 0, ptr(dw), ptr(db), ptr(dxsum),
+                                   ptr(gscale), M, D, stream()), "ce_layernorm_bwd_t")
     return dx_out
 
 
@@ -110,21 +115,21 @@ def grad_scale(x: torch.Tensor, target: float = 1024.0) -> torch.Tensor:
     """1-element device tensor: the power of two s with s * max|x| in (target / 2, target] (ce_grad_scale)."""
     assert x.dtype == torch.float32 and x.is_contiguous()
     buf = torch.empty(257, device=x.device, dtype=torch.float32)
-    check(lib().ce_grad_scale(ptr(x), c_long(x.numel()), c_float(target), c_void_p(buf.data_ptr() + 4), ptr(buf), stream()),
+    check(lib().ce_grad_scale(ptr(x), x.numel(), target, buf.data_ptr() + 4, ptr(buf), stream()),
           "ce_grad_scale")
     return buf[:1]
 
 
 def cast_scaled(x: torch.Tensor, dtype, scale: torch.Tensor, divide: bool = False):
     y = torch.empty_like(x, dtype=dtype)
-    check(lib().ce_cast_scaled(ptr(x), c_int(_TYPE[x.dtype]), ptr(y), c_int(_TYPE[dtype]), ptr(scale), c_int(1 if divide else 0),
-                               c_long(x.numel()), stream()), "ce_cast_scaled")
+    check(lib().ce_cast_scaled(ptr(x), _TYPE[x.dtype], ptr(y), _TYPE[dtype], ptr(scale), 1 if divide else 0,
+                               x.numel(), stream()), "ce_cast_scaled")
     return y
 
 
 def cast_t(x: torch.Tensor, dtype, mul: float = 1.0):
     y = torch.empty_like(x, dtype=dtype)
-    check(lib().ce_cast_t(ptr(x), c_int(_TYPE[x.dtype]), ptr(y), c_int(_TYPE[dtype]), c_float(mul), c_long(x.numel()), stream()),
+    check(lib().ce_cast_t(ptr(x), _TYPE[x.dtype], ptr(y), _TYPE[dtype], mul, x.numel(), stream()),
           "ce_cast_t")
     return y
 
@@ -134,30 +139,30 @@ def attention_fwd(qkv: torch.Tensor, B: int, L: int, H: int, causal: bool, cu_se
     assert qkv.dtype == torch.bfloat16
     o = torch.empty(qkv.shape[0], H * 64, device=qkv.device, dtype=torch.bfloat16)
     lse = torch.empty(B * H * L, device=qkv.device, dtype=torch.float32)
-    check(lib().ce_attention_fwd(ptr(qkv), c_long(qkv.stride(0)), ptr(o), c_long(o.stride(0)), ptr(lse),
-                                 ptr(cu_seqlens), c_int(B), c_int(L), c_int(H), c_int(1 if causal else 0), stream()),
+    check(lib().ce_attention_fwd(ptr(qkv), qkv.stride(0), ptr(o), o.stride(0), ptr(lse),
+                                 ptr(cu_seqlens), B, L, H, 1 if causal else 0, stream()),
           "ce_attention_fwd")
     return o, lse
 
 
 def attention_bwd(qkv, o, dout, lse, B: int, L: int, H: int, causal: bool, bias_grad=None, cu_seqlens=None):
     dqkv = torch.empty_like(qkv)
-    check(lib().ce_attention_bwd(ptr(qkv), c_long(qkv.stride(0)), ptr(o), c_long(o.stride(0)), ptr(dout),
-                                 c_long(dout.stride(0)), ptr(lse), ptr(dqkv), c_long(dqkv.stride(0)), ptr(bias_grad),
-                                 ptr(cu_seqlens), c_int(B), c_int(L), c_int(H), c_int(1 if causal else 0), stream()),
+    check(lib().ce_attention_bwd(ptr(qkv), qkv.stride(0), ptr(o), o.stride(0), ptr(dout),
+                                 dout.stride(0), ptr(lse), ptr(dqkv), dqkv.stride(0), ptr(bias_grad),
+                                 ptr(cu_seqlens), B, L, H, 1 if causal else 0, stream()),
           "ce_attention_bwd")
     return dqkv
 
 
 def probe_mfma(shape: int, a_frags: torch.Tensor, b_frags: torch.Tensor) -> torch.Tensor:
     out = torch.empty(64, 4 if shape == 16 else 16, device=a_frags.device, dtype=torch.float32)
-    check(lib().ce_probe_mfma(c_int(shape), ptr(a_frags), ptr(b_frags), ptr(out), stream()), "ce_probe_mfma")
+    check(lib().ce_probe_mfma(shape, ptr(a_frags), ptr(b_frags), ptr(out), stream()), "ce_probe_mfma")
     return out
 
 
 def probe_tr16(image: torch.Tensor, byte_off: torch.Tensor) -> torch.Tensor:
     out = torch.empty(64, 4, device=image.device, dtype=torch.int16)
-    check(lib().ce_probe_tr16(ptr(image), c_int(image.numel()), ptr(byte_off), ptr(out), stream()), "ce_probe_tr16")
+    check(lib().ce_probe_tr16(ptr(image), image.numel(), ptr(byte_off), ptr(out), stream()), "ce_probe_tr16")
     return out
 
 
@@ -167,7 +172,7 @@ def quant_rows_fp8(x: torch.Tensor):
     M, K = x.shape
     q = torch.empty(M, K, dtype=torch.uint8, device=x.device)
     scale = torch.empty(M, dtype=torch.float32, device=x.device)
-    check(lib().ce_quant_rows_fp8(ptr(x), c_long(x.stride(0)), ptr(q), c_long(K), ptr(scale), c_int(M), c_int(K), stream()),
+    check(lib().ce_quant_rows_fp8(ptr(x), x.stride(0), ptr(q), K, ptr(scale), M, K, stream()),
           "ce_quant_rows_fp8")
     return q, scale
 
@@ -179,11 +184,9 @@ def gemm_nt_fp8(a8, sa, b8, sb, epilogue: int, *, bias=None, resid=None, aux=Non
     f32_out = epilogue == L.EPI_BIAS_RESID_F32
     out = torch.empty(M, N, device=a8.device, dtype=torch.float32 if f32_out else torch.bfloat16)
     out2 = torch.empty_like(out) if epilogue == L.EPI_BIAS_GELU else colsum
-    check(lib().ce_gemm_nt_fp8(ptr(a8), c_long(a8.stride(0)), ptr(sa), ptr(b8), c_long(b8.stride(0)), ptr(sb), c_int(M),
-                               c_int(N), c_int(K), c_int(epilogue), ptr(bias), ptr(resid),
-                               c_long(resid.stride(0) if resid is not None else 0), ptr(out), c_long(out.stride(0)),
-                               ptr(out2), c_long(out2.stride(0) if epilogue == L.EPI_BIAS_GELU else 0), ptr(aux),
-                               c_long(aux.stride(0) if aux is not None else 0), stream()), "ce_gemm_nt_fp8")
+    ldo2 = out2.stride(0) if epilogue == L.EPI_BIAS_GELU else 0
+    check(lib().ce_gemm_nt_fp8(ptr(a8), a8.stride(0), ptr(sa), ptr(b8), b8.stride(0), ptr(sb), M, N, K,
+                               *_nt_tail(epilogue, bias, resid, out, out2, ldo2, aux)), "ce_gemm_nt_fp8")
     return (out, out2) if epilogue == L.EPI_BIAS_GELU else out
 
 
@@ -193,7 +196,7 @@ def quant_mx_fp8(x: torch.Tensor):
     M, K = x.shape
     q = torch.empty(M, K, dtype=torch.uint8, device=x.device)
     s8 = torch.empty(M, K // 32, dtype=torch.uint8, device=x.device)
-    check(lib().ce_quant_mx_fp8(ptr(x), c_long(x.stride(0)), ptr(q), c_long(K), ptr(s8), c_long(K // 32), c_int(M), c_int(K), stream()),
+    check(lib().ce_quant_mx_fp8(ptr(x), x.stride(0), ptr(q), K, ptr(s8), K // 32, M, K, stream()),
           "ce_quant_mx_fp8")
     return q, s8
 
@@ -205,10 +208,9 @@ def gemm_nt_mx8(a8, sa8, b8, sb8, epilogue: int, *, bias=None, resid=None, aux=N
     dt = torch.float32 if epilogue == L.EPI_BIAS_RESID_F32 else (torch.float16 if epilogue == L.EPI_BIAS_RESID_F16 else torch.bfloat16)
     out = torch.empty(M, N, device=a8.device, dtype=dt)
     out2 = torch.empty_like(out) if epilogue == L.EPI_BIAS_GELU else colsum
-    check(lib().ce_gemm_nt_mx8(ptr(a8), c_long(a8.stride(0)), ptr(sa8), ptr(b8), c_long(b8.stride(0)), ptr(sb8), c_int(M), c_int(N),
-                               c_int(K), c_int(epilogue), ptr(bias), ptr(resid), c_long(resid.stride(0) if resid is not None else 0),
-                               ptr(out), c_long(out.stride(0)), ptr(out2), c_long(out2.stride(0) if epilogue == L.EPI_BIAS_GELU else 0),
-                               ptr(aux), c_long(aux.stride(0) if aux is not None else 0), stream()), "ce_gemm_nt_mx8")
+    ldo2 = out2.stride(0) if epilogue == L.EPI_BIAS_GELU else 0
+    check(lib().ce_gemm_nt_mx8(ptr(a8), a8.stride(0), ptr(sa8), ptr(b8), b8.stride(0), ptr(sb8), M, N, K,
+                               *_nt_tail(epilogue, bias, resid, out, out2, ldo2, aux)), "ce_gemm_nt_mx8")
     return (out, out2) if epilogue == L.EPI_BIAS_GELU else out
 
 
@@ -216,7 +218,6 @@ def score_topk(q: torch.Tensor, keys: torch.Tensor, k: int, logit_scale=None, ta
     """Best ``k`` keys of every query without the [nq, nk] matrix (``ce_score_topk``): ``(values [nq,k] f32, indices [nq,k]
     int64, lse [nq] f32, rank [nq] int64 or None)``.  ``q`` / ``keys`` are used as given (normalise them first);
     ``logit_scale`` a device scalar (the score is exp(logit_scale) <q, key>) or None; ``target`` int64 [nq] or None."""
-    import ctypes
     assert q.dtype == torch.float32 and keys.dtype == torch.float32 and q.is_cuda and keys.is_cuda
     assert q.dim() == 2 and keys.dim() == 2 and q.stride(1) == 1 and keys.stride(1) == 1 and q.shape[1] == keys.shape[1]
     nq, E = q.shape
@@ -226,14 +227,13 @@ def score_topk(q: torch.Tensor, keys: torch.Tensor, k: int, logit_scale=None, ta
     if logit_scale is not None:
         assert logit_scale.dtype == torch.float32 and logit_scale.is_cuda and logit_scale.numel() == 1
     cl = lib()
-    cl.ce_score_topk_workspace_bytes.restype = ctypes.c_size_t
-    nbytes = int(cl.ce_score_topk_workspace_bytes(c_int(nq), c_int(nk), c_int(k), c_int(splits)))
+    nbytes = int(cl.ce_score_topk_workspace_bytes(nq, nk, k, splits))
     ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=q.device)
     top_val = torch.empty(nq, max(k, 0), dtype=torch.float32, device=q.device)
     top_idx = torch.empty(nq, max(k, 0), dtype=torch.int64, device=q.device)
     lse = torch.empty(nq, dtype=torch.float32, device=q.device)
     rank = None if target is None else torch.empty(nq, dtype=torch.int64, device=q.device)
-    check(cl.ce_score_topk(ptr(q), c_long(q.stride(0)), c_int(nq), ptr(keys), c_long(keys.stride(0)), c_int(nk), c_int(E),
-                           ptr(logit_scale), ptr(target), c_int(k), c_int(splits), ptr(top_val), ptr(top_idx), ptr(lse), ptr(rank),
+    check(cl.ce_score_topk(ptr(q), q.stride(0), nq, ptr(keys), keys.stride(0), nk, E,
+                           ptr(logit_scale), ptr(target), k, splits, ptr(top_val), ptr(top_idx), ptr(lse), ptr(rank),
                            ptr(ws), stream()), "ce_score_topk")
     return top_val, top_idx, lse, rank

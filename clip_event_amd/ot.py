@@ -1,8 +1,6 @@
 """IPOT optimal-transport distance on the HIP kernel (reference model_ot.py:66-83)."""
 from __future__ import annotations
 
-from ctypes import c_float, c_int, c_long
-
 import torch
 
 from ._lib import check, lib, ptr, stream
@@ -30,9 +28,9 @@ class _OTDistFn(torch.autograd.Function):
         T = torch.empty(B, N, M, dtype=torch.float32, device=dev)
         xinv = torch.empty(B, M, dtype=torch.float32, device=dev)
         yinv = torch.empty(B, N, dtype=torch.float32, device=dev)
-        check(lib().ce_ot_fwd(ptr(txt), c_long(txt.stride(0)), c_long(txt.stride(1)), ptr(img), c_long(img.stride(0)),
-                              c_long(img.stride(1)), ptr(tp), ptr(ip), ptr(dist), ptr(T), ptr(xinv), ptr(yinv), c_int(B),
-                              c_int(M), c_int(N), c_int(D), c_float(beta), c_int(iters), stream()), "ce_ot_fwd")
+        check(lib().ce_ot_fwd(ptr(txt), txt.stride(0), txt.stride(1), ptr(img), img.stride(0),
+                              img.stride(1), ptr(tp), ptr(ip), ptr(dist), ptr(T), ptr(xinv), ptr(yinv), B,
+                              M, N, D, beta, iters, stream()), "ce_ot_fwd")
         ctx.saved = (txt, img, T, xinv, yinv)
         return dist
 
@@ -44,9 +42,9 @@ class _OTDistFn(torch.autograd.Function):
         g = g.contiguous().float()
         dtxt = torch.empty(B, M, D, dtype=torch.float32, device=txt.device)
         dimg = torch.empty(B, N, D, dtype=torch.float32, device=txt.device)
-        check(lib().ce_ot_bwd(ptr(txt), c_long(txt.stride(0)), c_long(txt.stride(1)), ptr(img), c_long(img.stride(0)),
-                              c_long(img.stride(1)), ptr(T), ptr(xinv), ptr(yinv), ptr(g), ptr(dtxt), ptr(dimg), c_int(B),
-                              c_int(M), c_int(N), c_int(D), stream()), "ce_ot_bwd")
+        check(lib().ce_ot_bwd(ptr(txt), txt.stride(0), txt.stride(1), ptr(img), img.stride(0),
+                              img.stride(1), ptr(T), ptr(xinv), ptr(yinv), ptr(g), ptr(dtxt), ptr(dimg), B,
+                              M, N, D, stream()), "ce_ot_bwd")
         return dtxt, dimg, None, None, None, None
 
 

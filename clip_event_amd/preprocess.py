@@ -97,14 +97,13 @@ def preprocess(images: Sequence[torch.Tensor], rois: Optional[Sequence[Optional[
         max_scale = max(max_scale, w / ow, h / oh)
     kmax = int(math.ceil(2.0 * max_scale)) * 2 + 1
     cl = lib()
-    cl.ce_preprocess_table_bytes.restype = ctypes.c_size_t
-    table = torch.empty(cl.ce_preprocess_table_bytes(c_int(n_out), c_int(n_px), c_int(kmax)), dtype=torch.uint8, device=dev)
+    table = torch.empty(cl.ce_preprocess_table_bytes(n_out, n_px, kmax), dtype=torch.uint8, device=dev)
     tmp = torch.empty(max(tmp_bytes, 1), dtype=torch.uint8, device=dev)
     out = torch.empty(n_out, 3, n_px, n_px, dtype=torch.float32, device=dev)
     descs_d = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
     mean = (c_float * 3)(*MEAN)
     std = (c_float * 3)(*STD)
-    check(cl.ce_preprocess(ptr(descs_d), c_int(n_out), c_int(n_px), c_int(kmax), c_int(max_rows), ptr(table), ptr(tmp),
+    check(cl.ce_preprocess(ptr(descs_d), n_out, n_px, kmax, max_rows, ptr(table), ptr(tmp),
                            ptr(out), mean, std, stream()), "ce_preprocess")
     out._keepalive = (descs_d, table, tmp, list(images))   # until the stream has consumed them
     return out

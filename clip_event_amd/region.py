@@ -9,7 +9,6 @@ indexed by the x range (:439); an image contributes nothing when it has no usabl
 box is None (:450-455)."""
 from __future__ import annotations
 
-from ctypes import c_int, c_long
 from typing import List
 
 import torch
@@ -27,8 +26,8 @@ class _BBoxPoolFn(torch.autograd.Function):
             grid = grid.contiguous()
         nbox, E = boxes.shape[0], grid.shape[-1]
         out = torch.empty(nbox, E, dtype=torch.float32, device=grid.device)
-        check(lib().ce_bbox_pool_fwd(ptr(grid), c_long(grid.stride(0)), c_long(grid.stride(1)), c_long(grid.stride(2)),
-                                     ptr(boxes), ptr(out), c_int(nbox), c_int(E), stream()), "ce_bbox_pool_fwd")
+        check(lib().ce_bbox_pool_fwd(ptr(grid), grid.stride(0), grid.stride(1), grid.stride(2),
+                                     ptr(boxes), ptr(out), nbox, E, stream()), "ce_bbox_pool_fwd")
         ctx.saved, ctx.shape = boxes, tuple(grid.shape)
         return out
 
@@ -38,7 +37,7 @@ class _BBoxPoolFn(torch.autograd.Function):
         B, g, _, E = ctx.shape
         dgrid = torch.zeros(ctx.shape, dtype=torch.float32, device=dout.device)
         dout = dout.contiguous().float()
-        check(lib().ce_bbox_pool_bwd(ptr(dout), ptr(boxes), ptr(dgrid), c_int(g), c_int(boxes.shape[0]), c_int(E), stream()),
+        check(lib().ce_bbox_pool_bwd(ptr(dout), ptr(boxes), ptr(dgrid), g, boxes.shape[0], E, stream()),
               "ce_bbox_pool_bwd")
         return dgrid, None
 
@@ -52,9 +51,9 @@ class _RegionNCEFn(torch.autograd.Function):
         lab_f = lab_f.contiguous().float() if lab_f is not None else None
         ls = logit_scale.detach().reshape(1)
         out = torch.zeros(2, dtype=torch.float32, device=region.device)
-        check(lib().ce_region_nce_fwd(ptr(region), ptr(desc_f), ptr(lab_f), ptr(offsets), c_int(groups), c_int(max_rows),
-                                      c_int(region.shape[1]), ptr(ls), c_int(1 if use_label else 0),
-                                      c_int(1 if role_text else 0), ptr(out[0:1]), ptr(out[1:2]), stream()),
+        check(lib().ce_region_nce_fwd(ptr(region), ptr(desc_f), ptr(lab_f), ptr(offsets), groups, max_rows,
+                                      region.shape[1], ptr(ls), 1 if use_label else 0,
+                                      1 if role_text else 0, ptr(out[0:1]), ptr(out[1:2]), stream()),
               "ce_region_nce_fwd")
         ctx.saved = (region, desc_f, lab_f, ls, offsets)
         ctx.cfg = (groups, max_rows, use_label, role_text)
@@ -73,9 +72,9 @@ class _RegionNCEFn(torch.autograd.Function):
         dr, dd = torch.zeros_like(region), torch.zeros_like(desc_f)
         dl = torch.zeros_like(lab_f) if lab_f is not None else None
         dls = torch.zeros(1, dtype=torch.float32, device=dev)
-        check(lib().ce_region_nce_bwd(ptr(region), ptr(desc_f), ptr(lab_f), ptr(offsets), c_int(groups), c_int(max_rows),
-                                      c_int(region.shape[1]), ptr(ls), c_int(1 if use_label else 0),
-                                      c_int(1 if role_text else 0), ptr(g[0:1]), ptr(g[1:2]), ptr(dr), ptr(dd), ptr(dl),
+        check(lib().ce_region_nce_bwd(ptr(region), ptr(desc_f), ptr(lab_f), ptr(offsets), groups, max_rows,
+                                      region.shape[1], ptr(ls), 1 if use_label else 0,
+                                      1 if role_text else 0, ptr(g[0:1]), ptr(g[1:2]), ptr(dr), ptr(dd), ptr(dl),
                                       ptr(dls), stream()), "ce_region_nce_bwd")
         return dr, dd, dl, dls.reshape(()), None, None, None, None, None
 
