@@ -4,6 +4,8 @@
 //   ce_im2col            image fp32 NCHW -> bf16 patch rows      (Conv2d k=s=patch, model_clip.py:219,235)
 //   ce_vision_assemble   [cls | patches] + positional embedding   (model_clip.py:237-242)
 //   ce_vision_assemble_bwd
+//   ce_patch_keep        patch dropout: counter-based choice of the kept patches (keep list + inverse table)
+//   ce_im2col_rows / ce_vision_assemble_rows / ce_pos_embed_bwd_rows   the input side on the kept patches only
 //   ce_token_embed       token_embedding[ids] + positional        (model_clip.py:400-403)
 //   ce_token_embed_bwd   scatter-add into the embedding gradient
 //   ce_batch_reduce      sum over the batch axis (positional / class embedding gradients)
@@ -18,6 +20,39 @@
 
 namespace {
 
+// columns [8*cg, 8*cg + 8) of the patch row of patch (gy, gx) of image b, written to out_row + 8*cg
+__device__ __forceinline__ void im2col_group(const float* __restrict__ img, bf16_t* __restrict__ out_row, int b, int gy,
+                                             int gx, int cg, int R, int ps) {
+    if (ps % 8 == 0 && R % 4 == 0) {
+        // patch sizes 8 / 16 / 32: the 8 columns are 8 consecutive pixels of one image row -> two 16-byte loads.  3*ps*ps
+        // is a multiple of 8, so a group lies wholly in the patch or wholly in the zero padding behind it (Kp > 3*ps*ps).
+        const int col = cg * 8;
+        u32x4 pk = {0u, 0u, 0u, 0u};
+        if (col < 3 * ps * ps) {
+            const int c = col / (ps * ps), py = (col / ps) % ps, px = col % ps;
+            const float* src = img + (((long)b * 3 + c) * R + gy * ps + py) * R + gx * ps + px;
+            const f32x4 lo = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src));
+            const f32x4 hi = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + 4));
+            pk = u32x4{pack_bf2(lo[0], lo[1]), pack_bf2(lo[2], lo[3]), pack_bf2(hi[0], hi[1]), pack_bf2(hi[2], hi[3])};
+        }
+        *reinterpret_cast<u32x4*>(out_row + cg * 8) = pk;
+        return;
+    }
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int col = cg * 8 + e;
+        float val = 0.f;
+        if (col < 3 * ps * ps) {
+            const int c = col / (ps * ps), py = (col / ps) % ps, px = col % ps;
+            val = img[(((long)b * 3 + c) * R + gy * ps + py) * R + gx * ps + px];
+        }
+        v[e] = val;
+    }
+    u32x4 pk = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
+    *reinterpret_cast<u32x4*>(out_row + cg * 8) = pk;
+}
+
 // one thread = 8 consecutive output columns of one patch row
 __global__ void im2col_kernel(const float* __restrict__ img, bf16_t* __restrict__ out, int B, int R, int ps, int grid,
                               int Kp) {
@@ -26,35 +61,123 @@ __global__ void im2col_kernel(const float* __restrict__ img, bf16_t* __restrict_
         const int cg = (int)(idx % (Kp / 8));
         const long row = idx / (Kp / 8);
         const int gx = (int)(row % grid), gy = (int)((row / grid) % grid), b = (int)(row / ((long)grid * grid));
-        float v[8];
-        if (ps % 8 == 0 && R % 4 == 0) {
-            // patch sizes 8 / 16 / 32: the 8 columns are 8 consecutive pixels of one image row -> two 16-byte loads.  3*ps*ps
-            // is a multiple of 8, so a group lies wholly in the patch or wholly in the zero padding behind it (Kp > 3*ps*ps).
-            const int col = cg * 8;
-            u32x4 pk = {0u, 0u, 0u, 0u};
-            if (col < 3 * ps * ps) {
-                const int c = col / (ps * ps), py = (col / ps) % ps, px = col % ps;
-                const float* src = img + (((long)b * 3 + c) * R + gy * ps + py) * R + gx * ps + px;
-                const f32x4 lo = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src));
-                const f32x4 hi = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + 4));
-                pk = u32x4{pack_bf2(lo[0], lo[1]), pack_bf2(lo[2], lo[3]), pack_bf2(hi[0], hi[1]), pack_bf2(hi[2], hi[3])};
-            }
-            *reinterpret_cast<u32x4*>(out + row * Kp + cg * 8) = pk;
-            continue;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int col = cg * 8 + e;
-            float val = 0.f;
-            if (col < 3 * ps * ps) {
-                const int c = col / (ps * ps), py = (col / ps) % ps, px = col % ps;
-                val = img[(((long)b * 3 + c) * R + gy * ps + py) * R + gx * ps + px];
-            }
-            v[e] = val;
-        }
-        u32x4 pk = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
-        *reinterpret_cast<u32x4*>(out + row * Kp + cg * 8) = pk;
+        im2col_group(img, out + row * Kp, b, gy, gx, cg, R, ps);
     }
+}
+
+// Patch dropout: the same rows for the kept patches only.  Output row b*keep + j is the row of patch keep_idx[b, j]
+// (clamped into 0 .. grid*grid-1: a bad list cannot read outside the image).
+__global__ void im2col_rows_kernel(const float* __restrict__ img, const int* __restrict__ keep_idx,
+                                   bf16_t* __restrict__ out, int B, int keep, int R, int ps, int grid, int Kp) {
+    const long total = (long)B * keep * (Kp / 8);
+    for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int cg = (int)(idx % (Kp / 8));
+        const long row = idx / (Kp / 8);
+        const int b = (int)(row / keep);
+        int p = keep_idx[row];
+        p = p < 0 ? 0 : (p >= grid * grid ? grid * grid - 1 : p);
+        im2col_group(img, out + row * Kp, b, p / grid, p % grid, cg, R, ps);
+    }
+}
+
+__device__ __forceinline__ unsigned int fmix32(unsigned int h) {       // murmur3 finaliser: a bijection on uint32
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+
+// Patch dropout sampler: one block per sample.  Patch t is kept when fewer than `keep` patches of the sample have a smaller
+// key (keys of one sample are pairwise different, include/clip_event_hip.h); its slot is the number of kept patches
+// before it.  N <= 4095: keys and flags of one sample live in LDS.
+constexpr int PK_MAX = 4096;
+constexpr int PK_BLOCK = 256;
+__global__ __launch_bounds__(PK_BLOCK) void patch_keep_kernel(unsigned int seed, unsigned int draw, unsigned int sample0,
+                                                              int N, int keep, int* __restrict__ keep_idx,
+                                                              int* __restrict__ inv) {
+    __shared__ unsigned int keys[PK_MAX];
+    __shared__ unsigned short kept[PK_MAX];
+    __shared__ int seg_count[PK_BLOCK];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const unsigned int c = fmix32(fmix32(fmix32(seed + 0x9E3779B9u) ^ draw) ^ (sample0 + (unsigned int)b));
+    for (int t = tid; t < N; t += PK_BLOCK) keys[t] = fmix32(c ^ (unsigned int)t);
+    __syncthreads();
+    for (int t = tid; t < N; t += PK_BLOCK) {
+        const unsigned int k = keys[t];
+        int rank = 0;
+        for (int u = 0; u < N; ++u) rank += keys[u] < k ? 1 : 0;
+        kept[t] = rank < keep ? 1 : 0;
+    }
+    __syncthreads();
+    // ascending slots: thread `tid` owns patches [tid*per, tid*per + per)
+    const int per = (N + PK_BLOCK - 1) / PK_BLOCK;
+    const int t0 = tid * per, t1 = t0 + per < N ? t0 + per : N;
+    int mine = 0;
+    for (int t = t0; t < t1; ++t) mine += kept[t];
+    seg_count[tid] = mine;
+    __syncthreads();
+    int slot = 0;
+    for (int u = 0; u < tid; ++u) slot += seg_count[u];
+    for (int t = t0; t < t1; ++t) {
+        const bool k = kept[t] != 0 && slot < keep;
+        if (k) keep_idx[(long)b * keep + slot] = t;
+        if (inv) inv[(long)b * N + t] = k ? slot : -1;
+        slot += k ? 1 : 0;
+    }
+}
+
+// x0[b, 0, :] = cls + pos[0, :];  x0[b, 1+j, :] = patch[b*keep + j, :] + pos[1 + keep_idx[b, j], :]   (index clamped to N-1)
+__global__ void vision_assemble_rows_kernel(const float* __restrict__ patch, const int* __restrict__ keep_idx,
+                                            const float* __restrict__ cls, const float* __restrict__ pos,
+                                            float* __restrict__ x0, int B, int N, int keep, int D) {
+    const int Ltok = keep + 1;
+    const long total = (long)B * Ltok * (D / 4);
+    for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(idx % (D / 4)) * 4;
+        const long row = idx / (D / 4);
+        const int t = (int)(row % Ltok);
+        const long b = row / Ltok;
+        f32x4 v;
+        int prow = 0;
+        if (t == 0) {
+            v = *reinterpret_cast<const f32x4*>(cls + c);
+        } else {
+            int p = keep_idx[b * keep + t - 1];
+            p = p < 0 ? 0 : (p >= N ? N - 1 : p);
+            prow = 1 + p;
+            v = *reinterpret_cast<const f32x4*>(patch + (b * keep + t - 1) * D + c);
+        }
+        v += *reinterpret_cast<const f32x4*>(pos + (long)prow * D + c);
+        *reinterpret_cast<f32x4*>(x0 + row * D + c) = v;
+    }
+}
+
+// dpos[0, :] += sum_b dx0[b, 0, :];  dpos[1+t, :] += sum over the samples that kept patch t of dx0[b, 1 + inv[b, t], :].
+// grid = (N + 1, column chunks of 256 floats); every thread sums its 4 columns over b = 0, 1, ... in that order and is
+// the only writer of them: no atomics, the same bits every run.  A row that no sample kept is not written.
+__global__ __launch_bounds__(64) void pos_embed_bwd_rows_kernel(const float* __restrict__ dx0, const int* __restrict__ inv,
+                                                                float* __restrict__ dpos, int B, int N, int keep, int D) {
+    const int t = blockIdx.x;                                // positional row
+    const int c = (blockIdx.y * 64 + threadIdx.x) * 4;
+    if (c >= D) return;
+    const long Ltok = keep + 1;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        int j = 0;
+        if (t > 0) {
+            j = inv[(long)b * N + t - 1];                    // block-uniform
+            if (j < 0) continue;
+            j = 1 + (j >= keep ? keep - 1 : j);
+        }
+        acc += *reinterpret_cast<const f32x4*>(dx0 + ((long)b * Ltok + j) * D + c);
+        any = true;
+    }
+    if (!any) return;
+    float* dst = dpos + (long)t * D + c;
+    *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(dst) + acc;
 }
 
 // x0[b, t, :] = (t == 0 ? cls : patch[b*P + t-1, :]) + pos[t, :]      (fp32, 4 columns per thread)
@@ -382,6 +505,46 @@ extern "C" int ce_vision_assemble_bwd(const float* dx0, void* dpatch, int B, int
     CE_CHECK_ARG(B > 0 && tokens > 1 && D % 4 == 0, "ce_vision_assemble_bwd: bad shape");
     hipLaunchKernelGGL(vision_assemble_bwd_kernel, dim3(grid_for((long)B * (tokens - 1) * (D / 4))), dim3(256), 0,
                        (hipStream_t)stream, dx0, (bf16_t*)dpatch, B, tokens, D);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_patch_keep(long seed, long draw, long sample0, int B, int N, int keep, int* keep_idx, int* inv,
+                             void* stream) {
+    CE_CHECK_ARG(B > 0 && keep >= 1 && keep <= N && N < PK_MAX && keep_idx, "ce_patch_keep: need 1 <= keep <= N <= 4095 (got keep=%d N=%d)", keep, N);
+    hipLaunchKernelGGL(patch_keep_kernel, dim3(B), dim3(PK_BLOCK), 0, (hipStream_t)stream, (unsigned int)(unsigned long)seed,
+                       (unsigned int)(unsigned long)draw, (unsigned int)(unsigned long)sample0, N, keep, keep_idx, inv);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_im2col_rows(const float* image, const int* keep_idx, void* patches, int B, int keep, int resolution,
+                              int patch, int k_padded, void* stream) {
+    CE_CHECK_ARG(B > 0 && patch > 0 && resolution % patch == 0, "ce_im2col_rows: resolution %d not a multiple of patch %d", resolution, patch);
+    CE_CHECK_ARG(k_padded % 8 == 0 && k_padded >= 3 * patch * patch, "ce_im2col_rows: k_padded must be a multiple of 8 >= 3*patch^2");
+    const int grid = resolution / patch;
+    CE_CHECK_ARG(keep_idx && keep >= 1 && keep <= grid * grid, "ce_im2col_rows: keep=%d outside 1..%d", keep, grid * grid);
+    const long threads = (long)B * keep * (k_padded / 8);
+    hipLaunchKernelGGL(im2col_rows_kernel, dim3(grid_for(threads)), dim3(256), 0, (hipStream_t)stream, image, keep_idx,
+                       (bf16_t*)patches, B, keep, resolution, patch, grid, k_padded);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_vision_assemble_rows(const float* patch_out, const int* keep_idx, const float* cls, const float* pos,
+                                       float* x0, int B, int N, int keep, int D, void* stream) {
+    CE_CHECK_ARG(B > 0 && keep_idx && keep >= 1 && keep <= N && D > 0 && D % 4 == 0, "ce_vision_assemble_rows: bad shape");
+    hipLaunchKernelGGL(vision_assemble_rows_kernel, dim3(grid_for((long)B * (keep + 1) * (D / 4))), dim3(256), 0,
+                       (hipStream_t)stream, patch_out, keep_idx, cls, pos, x0, B, N, keep, D);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_pos_embed_bwd_rows(const float* dx0, const int* inv, float* dpos, int B, int N, int keep, int D,
+                                     void* stream) {
+    CE_CHECK_ARG(B > 0 && inv && keep >= 1 && keep <= N && D > 0 && D % 4 == 0, "ce_pos_embed_bwd_rows: bad shape");
+    hipLaunchKernelGGL(pos_embed_bwd_rows_kernel, dim3(N + 1, (D / 4 + 63) / 64), dim3(64), 0, (hipStream_t)stream, dx0,
+                       inv, dpos, B, N, keep, D);
     CE_LAUNCH_CHECK();
     return 0;
 }

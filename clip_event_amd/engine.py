@@ -4,6 +4,7 @@ global-norm clip to 1 and Adam (fused, optim.py).  With more than one rank the f
 all-gathered for a global-batch InfoNCE and parameter gradients are averaged (distributed.py)."""
 from __future__ import annotations
 
+import contextlib
 import functools
 import logging
 import math
@@ -231,9 +232,19 @@ def micro_batched_backward(model, criterion, image, text, labels_per_image, labe
         gs.expect_passes({t: len(chunks) for t in live})
     # every chunk, the shorter last one included, runs in buffers leased for a full chunk (the pool is keyed by byte count)
     model._lease_batch = {"vision": mb, "text": mb * K}
+    # patch dropout: ONE draw for the step; both passes of the chunk [lo, hi) run pinned to it with their samples counted from
+    # lo, so the chunked step drops exactly the patches the unchunked step drops
+    draw = model.next_patch_draw() if model.drops_patches() else None
+
+    def pinned(lo):
+        return contextlib.nullcontext() if draw is None else model.pinned_patch_draw(draw[0], sample0=draw[1] + lo)
+
     try:
         with torch.no_grad():
-            feats = [model.encode_both(img_c, txt_c) for _, _, img_c, txt_c in chunks]
+            feats = []
+            for lo, _, img_c, txt_c in chunks:
+                with pinned(lo):
+                    feats.append(model.encode_both(img_c, txt_c))
         fi = torch.cat([f[0] for f in feats], dim=0).requires_grad_(not locked["visual"])
         ft = torch.cat([f[1] for f in feats], dim=0).requires_grad_(not locked["text"])
         del feats
@@ -241,9 +252,13 @@ def micro_batched_backward(model, criterion, image, text, labels_per_image, labe
         _sum_losses(loss_dict, check_finite).backward()        # fi.grad, ft.grad, logit_scale.grad; no tower node, no exchange
         for lo, hi, img_c, txt_c in (chunks if live else []):
             if len(live) == 2:
-                outs, grads = model.encode_both(img_c, txt_c), [fi.grad[lo:hi], ft.grad[lo * K:hi * K]]
+                with pinned(lo):
+                    outs = model.encode_both(img_c, txt_c)
+                grads = [fi.grad[lo:hi], ft.grad[lo * K:hi * K]]
             elif live[0] == "visual":
-                outs, grads = [model.encode_image(img_c)], [fi.grad[lo:hi]]
+                with pinned(lo):
+                    outs = [model.encode_image(img_c)]
+                grads = [fi.grad[lo:hi]]
             else:
                 outs, grads = [model.encode_text(txt_c)], [ft.grad[lo * K:hi * K]]
             torch.autograd.backward(list(outs), grads)

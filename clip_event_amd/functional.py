@@ -79,15 +79,16 @@ def _tower_backward(model, desc, tower: str, batch: int, rows: int, cu, x0, leas
     cuts = [c for c in cuts if c > stop]        # hand-overs below the stop: nothing is computed there
     # Block l's ln_1 backward also sums the c_proj bias gradient of block l - 1 (tower.cpp: fused into that kernel).  Below the stop
     # that tensor is frozen: the descriptor gets NULL there, as block 0 has for "no block below", and the kernel skips the sum.
-    cut = getattr(desc, "_cut", 0)
+    owner = getattr(desc, "_owner", desc)        # a shorter-sequence copy (_vision_desc) shares the owner's block table
+    cut = getattr(owner, "_cut", 0)
     if cut != stop:
         prefix = "visual.transformer." if tower == "visual" else "transformer."
         if 0 < cut < layers:
             desc.blocks[cut - 1].g_b_proj = model._gview(f"{prefix}resblocks.{cut - 1}.mlp.c_proj.bias").data_ptr()
         if 0 < stop < layers:
             desc.blocks[stop - 1].g_b_proj = None
-        desc._cut = stop
-    model.wait_transposes()       # the blocks' W^T copies may still be in flight on the auxiliary stream (model.refresh_operands)
+        owner._cut = stop
+    model.wait_transposes()      # the blocks' W^T copies may still be in flight on the auxiliary stream (model.refresh_operands)
     # the step's first backward pass of this tower writes the block weight gradients instead of accumulating them
     # (model.zero_grad_first_touch); the flag is consumed here, so later passes of the same step accumulate
     pending = getattr(model, "_first_touch", None)
@@ -279,11 +280,36 @@ def _tower_backward_done(ctx, tower: str, n_inputs: int):
     return (None,) * n_inputs
 
 
+def patch_keep_seed(seed: int, rank: int = 0) -> int:
+    """The seed ``ce_patch_keep`` receives on data-parallel rank ``rank``: ``(seed + rank * 0x632BE5AB) mod 2**32``, so that
+    the ranks drop different patches of their (different) samples."""
+    return (int(seed) + int(rank) * 0x632BE5AB) & 0xFFFFFFFF
+
+
+def _vision_desc(model, tokens: int):
+    """The image tower's descriptor at ``tokens`` rows per image: ``model._vdesc`` itself at the full length, otherwise a
+    copy (cached per length on ``model._vdesc``, so it goes when the device tables are rebuilt) that shares the block table
+    and whose per-pass switches are brought up to date here.  The workspace lease is sized from it: with patch dropout the
+    stash shrinks with the rows."""
+    base = model._vdesc
+    if tokens == base.tokens:
+        return base
+    cache = base.__dict__.setdefault("_by_tokens", {})
+    d = cache.get(tokens)
+    if d is None:
+        d = cache[tokens] = type(base)(base.layers, base.width, base.heads, tokens, base.causal, base.blocks, 0, 0, 0, None)
+        d._keep = base._keep          # the block table the pointer refers to
+        d._owner = base               # _tower_backward keeps the state of that (shared) table on the owner
+    d.fp8, d.stream16 = base.fp8, base.stream16
+    return d
+
+
 class EncodeImageFn(torch.autograd.Function):
-    """VisualTransformer.forward (model_clip.py:232-263) as one autograd node."""
+    """VisualTransformer.forward (model_clip.py:232-263) as one autograd node.  With ``keep_idx`` / ``inv`` (patch dropout,
+    CLIP._patch_tables) the tower sees the class token and the listed patches only; ``use_grid`` is then off."""
 
     @staticmethod
-    def forward(ctx, image, trigger, model, use_grid: bool, infer: bool = False):
+    def forward(ctx, image, trigger, model, use_grid: bool, infer: bool = False, keep_idx=None, inv=None):
         cl, s = lib(), stream()
         v = model.visual
         dev = model._flat.device
@@ -294,15 +320,28 @@ class EncodeImageFn(torch.autograd.Function):
         R, ps, g, D, E = v.input_resolution, v.patch_size, v.patch_num, model.vision_width, model.embed_dim
         if tuple(image.shape[1:]) != (3, R, R):
             raise RuntimeError(f"expected image [B,3,{R},{R}], got {tuple(image.shape)}")
-        T = g * g + 1
+        N = g * g
+        if keep_idx is not None and (use_grid or tuple(keep_idx.shape) != (B, keep_idx.shape[1]) or tuple(inv.shape) != (B, N)):
+            raise RuntimeError("patch dropout tables do not fit this pass")
+        keep = N if keep_idx is None else keep_idx.shape[1]  # patch rows per image
+        T = keep + 1
         M = B * T
         P = model._pmap
-        patches = _empty((B * g * g, model._kp), torch.bfloat16, dev)
-        check(cl.ce_im2col(ptr(image), ptr(patches), B, R, ps, model._kp, s), "ce_im2col")
+        desc = _vision_desc(model, T)
+        patches = _empty((B * keep, model._kp), torch.bfloat16, dev)
+        if keep_idx is None:
+            check(cl.ce_im2col(ptr(image), ptr(patches), B, R, ps, model._kp, s), "ce_im2col")
+        else:
+            check(cl.ce_im2col_rows(ptr(image), ptr(keep_idx), ptr(patches), B, keep, R, ps, model._kp, s), "ce_im2col_rows")
         patch_out = ops.gemm_nt(patches, model._w16["visual.conv1.weight"], L.EPI_F32)
         xpre = _empty((M, D), torch.float32, dev)
-        check(cl.ce_vision_assemble(ptr(patch_out), ptr(P["visual.class_embedding"]), ptr(P["visual.positional_embedding"]),
-                                    ptr(xpre), B, T, D, s), "ce_vision_assemble")
+        if keep_idx is None:
+            check(cl.ce_vision_assemble(ptr(patch_out), ptr(P["visual.class_embedding"]), ptr(P["visual.positional_embedding"]),
+                                        ptr(xpre), B, T, D, s), "ce_vision_assemble")
+        else:
+            check(cl.ce_vision_assemble_rows(ptr(patch_out), ptr(keep_idx), ptr(P["visual.class_embedding"]),
+                                             ptr(P["visual.positional_embedding"]), ptr(xpre), B, N, keep, D, s),
+                  "ce_vision_assemble_rows")
         sdt, _ = _stream_type(model)                          # residual stream: fp32, or fp16 (model.stream16)
         x0, mean_pre, rstd_pre = ops.layernorm_fwd_t(xpre, P["visual.ln_pre.weight"], P["visual.ln_pre.bias"], sdt)
         if use_grid:
@@ -315,15 +354,16 @@ class EncodeImageFn(torch.autograd.Function):
             n = B
         xN = _empty((n, D), sdt, dev)
         if infer:                  # grad mode was off at the call (CLIP.encode_image): no stash, nothing kept for a backward
-            _tower_forward_infer(model, model._vdesc, "vision", B, M, None, x0, xN, rows)
+            _tower_forward_infer(model, desc, "vision", B, M, None, x0, xN, rows)
         else:
-            lease = _tower_workspace(model, model._vdesc, B, "vision")
-            check(cl.ce_tower_forward(ctypes.byref(model._vdesc), B, M, None, ptr(x0), ptr(lease.buf), ptr(xN), ptr(rows), s),
+            lease = _tower_workspace(model, desc, B, "vision")
+            check(cl.ce_tower_forward(ctypes.byref(desc), B, M, None, ptr(x0), ptr(lease.buf), ptr(xN), ptr(rows), s),
                   "ce_tower_forward(vision)")
         feat, hpost, mean_post, rstd_post = _tower_top_forward(model, xN, "visual.ln_post", "visual.proj")
         if infer:
             return feat.view(B, T, E) if use_grid else feat
         ctx.model, ctx.lease, ctx.use_grid, ctx.B = model, lease, use_grid, B
+        ctx.keep, ctx.inv = keep, inv
         ctx.stream16 = sdt == torch.float16
         ctx.main_stream = getattr(model, "_main_stream", None)
         ctx.saved = (patches, xpre, mean_pre, rstd_pre, x0, xN, rows, hpost, mean_post, rstd_post)
@@ -339,34 +379,41 @@ class EncodeImageFn(torch.autograd.Function):
         v = model.visual
         dev = model._flat.device
         B, g, D, E = ctx.B, v.patch_num, model.vision_width, model.embed_dim
-        T = g * g + 1
+        keep, inv = ctx.keep, ctx.inv                         # patch rows per image; patch dropout's inverse table or None
+        T = keep + 1
         M = B * T
+        desc = _vision_desc(model, T)
         model._attach_grads()
         P, G = model._pmap, model._gview
         _check_stream(ctx, model)
         # gradient w.r.t. the tower output (fp32): [B,D] in pruned mode (the tower's dx_sel) or [M,D] in grid mode, where it
         # IS the gradient stream on entry -- an fp16 stream holds gradient * scale, the scale chosen from this tensor
-        dxn, gs = _tower_top_backward(model, model._vdesc, _f32(dfeat).reshape(-1, E), xN, hpost, mean_post, rstd_post,
+        dxn, gs = _tower_top_backward(model, desc, _f32(dfeat).reshape(-1, E), xN, hpost, mean_post, rstd_post,
                                       "visual.ln_post", "visual.proj")
         if rows is None:           # grid mode
             dx = dxn if gs is None else ops.cast_scaled(dxn, xN.dtype, gs)
-            stop = _tower_backward(model, model._vdesc, "visual", B, M, None, x0, lease, dx, None, None)
+            stop = _tower_backward(model, desc, "visual", B, M, None, x0, lease, dx, None, None)
         else:
             dx = _empty((M, D), xN.dtype, dev)
-            stop = _tower_backward(model, model._vdesc, "visual", B, M, None, x0, lease, dx, rows, dxn)
+            stop = _tower_backward(model, desc, "visual", B, M, None, x0, lease, dx, rows, dxn)
         lease.release()
         if stop > 0:      # everything below block `stop` is frozen, the input side included: ln_pre, the embedding sums and the
             #               conv1 weight gradient have no reader
-            return _tower_backward_done(ctx, "visual", 5)
+            return _tower_backward_done(ctx, "visual", 7)
         # ln_pre: x0 = LN(xpre); its dy is the gradient stream
         dxpre = ops.layernorm_bwd_t(dx, xpre, mean_pre, rstd_pre, P["visual.ln_pre.weight"], G("visual.ln_pre.weight"),
                                     G("visual.ln_pre.bias"), _empty((M, D), torch.float32, dev), gscale=gs)
-        # positional / class embedding gradients: sums over the batch axis
-        check(cl.ce_batch_reduce(ptr(dxpre), ptr(G("visual.positional_embedding")), B, T * D, T * D, 1, s),
-              "ce_batch_reduce(pos)")
+        # positional / class embedding gradients: sums over the batch axis (with patch dropout a sample adds to the
+        # positional rows of the patches it kept)
+        if inv is None:
+            check(cl.ce_batch_reduce(ptr(dxpre), ptr(G("visual.positional_embedding")), B, T * D, T * D, 1, s),
+                  "ce_batch_reduce(pos)")
+        else:
+            check(cl.ce_pos_embed_bwd_rows(ptr(dxpre), ptr(inv), ptr(G("visual.positional_embedding")), B, g * g, keep, D, s),
+                  "ce_pos_embed_bwd_rows")
         check(cl.ce_batch_reduce(ptr(dxpre), ptr(G("visual.class_embedding")), B, T * D, D, 1, s), "ce_batch_reduce(cls)")
         # conv1 weight gradient: dW[width, 3*p*p] += dpatch^T patches   (no input gradient is ever needed)
-        dpatch = _empty((B * g * g, D), torch.bfloat16, dev)
+        dpatch = _empty((B * keep, D), torch.bfloat16, dev)
         check(cl.ce_vision_assemble_bwd(ptr(dxpre), ptr(dpatch), B, T, D, s), "ce_vision_assemble_bwd")
         if model._conv_pad is None:        # the gradient view has the weight's 4-D shape: its rows are model._kp apart
             ops.gemm_tn(dpatch, patches, G("visual.conv1.weight"), ldo=model._kp)
@@ -376,7 +423,7 @@ class EncodeImageFn(torch.autograd.Function):
             ops.gemm_tn(dpatch, patches, gp)
             check(cl.ce_add_cols(ptr(gp), model._kp, ptr(G("visual.conv1.weight")), model._kp_real, D, model._kp_real, s),
                   "ce_add_cols(conv1)")
-        return _tower_backward_done(ctx, "visual", 5)
+        return _tower_backward_done(ctx, "visual", 7)
 
 
 class EncodeTextFn(torch.autograd.Function):

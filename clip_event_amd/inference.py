@@ -12,6 +12,12 @@ from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 
+def _dense(model):
+    """Context in which the image tower sees every patch: inference never applies patch dropout, even on a model that was
+    left in training mode (``CLIP.no_patch_dropout``)."""
+    return getattr(model, "module", model).no_patch_dropout()
+
+
 @torch.no_grad()
 def zero_shot(model, image: torch.Tensor, text: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``image`` [B,3,R,R], ``text`` [N,77] candidate descriptions shared by all images ->
@@ -19,7 +25,8 @@ def zero_shot(model, image: torch.Tensor, text: torch.Tensor) -> Tuple[torch.Ten
     saved = model.constrastive_overbatch
     model.constrastive_overbatch = True
     try:
-        logits_per_image, _ = model(image, text)
+        with _dense(model):
+            logits_per_image, _ = model(image, text)
     finally:
         model.constrastive_overbatch = saved
     probs = logits_per_image.softmax(dim=-1)
@@ -78,7 +85,8 @@ def encode_bank(model, image: Optional[torch.Tensor] = None, text: Optional[torc
     out = []
     for i in range(0, x.shape[0], chunk):
         part = x[i:i + chunk].to(dev)
-        f = model.encode_image(part) if text is None else model.encode_text(part)
+        with _dense(model):
+            f = model.encode_image(part) if text is None else model.encode_text(part)
         out.append(_l2norm(f))
     return out[0] if len(out) == 1 else torch.cat(out)
 
@@ -87,7 +95,8 @@ def encode_bank(model, image: Optional[torch.Tensor] = None, text: Optional[torc
 def zero_shot_topk(model, image: torch.Tensor, bank: torch.Tensor, k: int = 5) -> Tuple[torch.Tensor, torch.Tensor]:
     """``zero_shot`` against a bank from ``encode_bank(model, text=...)``: ``(probs [B,k], idx [B,k])``, the k most
     probable candidates of every image and their softmax probabilities over the whole bank."""
-    q = _l2norm(model.encode_image(image.to(bank.device)))
+    with _dense(model):
+        q = _l2norm(model.encode_image(image.to(bank.device)))
     top = score_topk(q, bank, k, logit_scale=model.logit_scale, normalized=True)
     return torch.exp(top.values - top.lse[:, None]), top.indices
 

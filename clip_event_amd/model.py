@@ -15,6 +15,7 @@ and transposed) are refreshed from the masters when their version counters move.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -122,6 +123,13 @@ class VisualTransformer(nn.Module):
         self.ln_pre = _Affine(width)
         self.transformer = Transformer(width, layers, heads)
         self.ln_post = _Affine(width)
+        self.patch_dropout = 0.0          # CLIP.set_patch_dropout: fraction of the patches a training pass leaves out
+
+    def patch_keep(self, p: Optional[float] = None) -> int:
+        """Patches a pass keeps at dropout rate ``p`` (default: this tower's): ``max(1, int(N * (1 - p)))``, open_clip's rule."""
+        p = self.patch_dropout if p is None else p
+        n = self.patch_num ** 2
+        return max(1, int(n * (1.0 - p)))
 
 
 class _Embedding(nn.Module):
@@ -314,13 +322,17 @@ class CLIP(nn.Module):
         # gradient may see on its way down: measured x17-34 in the text tower, x1.1-1.3 in the image tower, tools/diag/grad_growth.py).  CE_STREAM16=0 keeps both streams in fp32 as the reference does.
         self.stream16 = os.environ.get("CE_STREAM16", "1") != "0"
         self.grad_target = float(os.environ.get("CE_GRAD_TARGET", "64"))
+        # patch dropout (set_patch_dropout): the sampler's seed and the draw counter; neither is a parameter or a buffer, so
+        # neither enters state_dict() or a checkpoint
+        self.patch_seed = 0
+        self.patch_draw = 0
 
     # ---- copy / pickle: the device-side tables (ctypes descriptors, workspace pool, streams, operand copies) are
     # rebuilt lazily by _prepare(); only the parameters and the plain attributes travel --------------------------
     _RUNTIME = ("_flat", "_flat_grad", "_flat16", "_offsets", "_ranges", "_layer_end", "_pmap", "_pool", "_trigger",
                 "_versions", "_w16", "_w16t", "_kp", "_kp_real", "_conv_pad", "_conv_gpad", "_cast_list", "_tjobs",
                 "_tjobs_bwd", "_adam_tiles_ok", "_wt_fresh", "_wt_event", "_aux_stream", "_mirror_fresh", "_mirror_versions", "_vdesc", "_tdesc", "_vblocks", "_tblocks",
-                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch", "_lease_batch", "_plist", "_plans")
+                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch", "_lease_batch", "_plist", "_plans", "_patch_pin", "_patch_off")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -909,17 +921,119 @@ class CLIP(nn.Module):
         if self.grad_sync is not None and torch.is_grad_enabled() and not locked and hasattr(self.grad_sync, "note_forward"):
             self.grad_sync.note_forward(tower)
 
-    def encode_image(self, image, use_grid: bool = False):
-        """model_clip.py:390-391 -> VisualTransformer.forward (:232-263)."""
+    # ---- patch dropout (FLIP; open_clip's PatchDropout): a training pass of the image tower sees the class token and a random
+    # subset of the patches.  DESIGN.md 4e.
+    def set_patch_dropout(self, p: float, seed: int = 0):
+        """Leave out the fraction ``p`` of the patches (``0 <= p < 1``; 0 switches it off) in every ``encode_image`` pass with
+        ``use_grid=False`` while the model is in training mode: ``visual.patch_keep()`` patches per image remain.  The kept
+        patches are a pure function of ``seed``, the rank, ``patch_draw`` and the sample's row (``ce_patch_keep``)."""
+        p = float(p)
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"patch dropout rate must lie in [0, 1) (got {p})")
+        self.visual.patch_dropout = p
+        self.patch_seed = int(seed)
+
+    @contextlib.contextmanager
+    def pinned_patch_draw(self, draw: int, sample0: int = 0):
+        """Inside, every dropping pass uses draw ``draw`` and counts its samples from ``sample0``; ``patch_draw`` does not
+        move.  This is how a pass is replayed (the two passes of a micro-batched chunk, a test against a reference)."""
+        saved = getattr(self, "_patch_pin", None)
+        self._patch_pin = (int(draw), int(sample0))
+        try:
+            yield self
+        finally:
+            self._patch_pin = saved
+
+    @contextlib.contextmanager
+    def no_patch_dropout(self):
+        """Inside, no pass drops patches whatever ``training`` says (the inference helpers)."""
+        saved = getattr(self, "_patch_off", False)
+        self._patch_off = True
+        try:
+            yield self
+        finally:
+            self._patch_off = saved
+
+    def drops_patches(self) -> bool:
+        """Whether an ``encode_image(use_grid=False)`` call without an explicit keep list would drop patches now."""
+        return bool(self.training and getattr(self.visual, "patch_dropout", 0.0) > 0.0 and not getattr(self, "_patch_off", False))
+
+    def next_patch_draw(self) -> Tuple[int, int]:
+        """``(draw, sample0)`` of the next dropping pass: the pinned pair, or the counter, which then advances."""
+        pin = getattr(self, "_patch_pin", None)
+        if pin is not None:
+            return pin
+        d = self.patch_draw
+        self.patch_draw = d + 1
+        return d, 0
+
+    def _check_keep_idx(self, keep_idx, B: int, use_grid: bool):
+        """Validate an explicit keep list that lives on the host (list, array, CPU tensor) -> int32 array [B, keep]; a device
+        tensor is trusted (the kernels clamp what they read from it) and returned as it is."""
+        if use_grid:
+            raise ValueError("keep_idx with use_grid=True: a grid pass never drops patches, the grid is its output")
+        n = self.visual.patch_num ** 2
+        if isinstance(keep_idx, torch.Tensor) and keep_idx.device.type != "cpu":
+            if keep_idx.dtype != torch.int32 or keep_idx.dim() != 2 or keep_idx.shape[0] != B or not 1 <= keep_idx.shape[1] <= n:
+                raise ValueError(f"a device keep_idx must be int32 [{B}, 1..{n}] (got {keep_idx.dtype} {tuple(keep_idx.shape)})")
+            return keep_idx.contiguous()
+        try:
+            a = np.asarray(keep_idx.numpy() if isinstance(keep_idx, torch.Tensor) else keep_idx)
+        except Exception as e:       # ragged rows
+            raise ValueError(f"keep_idx is not a rectangular [B, keep] list: {e}") from None
+        if a.ndim != 2 or a.shape[0] != B or not 1 <= a.shape[1] <= n or a.dtype.kind not in "iu":
+            raise ValueError(f"keep_idx must be integers of shape [{B}, 1..{n}] (got {a.dtype} {a.shape})")
+        a = a.astype(np.int64)
+        if a.min() < 0 or a.max() >= n:
+            raise ValueError(f"keep_idx entries must lie in 0..{n - 1}")
+        if a.shape[1] > 1 and not (np.diff(a, axis=1) > 0).all():
+            raise ValueError("every row of keep_idx must be strictly ascending")
+        return a.astype(np.int32)
+
+    def _patch_tables(self, B: int, keep_idx):
+        """Device tables of a dropping pass: ``(keep_idx int32 [B,keep], inv int32 [B,N])``, from the explicit list or from the
+        sampler; None for a dense pass."""
+        dev = self._flat.device
+        n = self.visual.patch_num ** 2
+        if keep_idx is not None:
+            if isinstance(keep_idx, np.ndarray):
+                keep_idx = torch.from_numpy(keep_idx).to(dev)
+            # inverse table of a given list (not a training path: the sampler's launch writes both)
+            inv = torch.full((B, n), -1, dtype=torch.int32, device=dev)
+            slots = torch.arange(keep_idx.shape[1], dtype=torch.int32, device=dev).expand(B, -1)
+            inv.scatter_(1, keep_idx.long().clamp_(0, n - 1), slots)
+            return keep_idx, inv
+        from .functional import patch_keep_seed
+        keep = self.visual.patch_keep()
+        draw, sample0 = self.next_patch_draw()
+        rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
+        keep_idx = torch.empty((B, keep), dtype=torch.int32, device=dev)
+        inv = torch.empty((B, n), dtype=torch.int32, device=dev)
+        check(lib().ce_patch_keep(patch_keep_seed(self.patch_seed, rank), draw, sample0, B, n, keep, ptr(keep_idx), ptr(inv),
+                                  stream()), "ce_patch_keep")
+        return keep_idx, inv
+
+    def encode_image(self, image, use_grid: bool = False, keep_idx=None):
+        """model_clip.py:390-391 -> VisualTransformer.forward (:232-263).
+
+        Patch dropout: with ``use_grid=False``, in training mode and ``visual.patch_dropout > 0`` (``set_patch_dropout``) the
+        tower runs on the class token and the sampled patches only -- in either grad mode, so that the micro-batched step's
+        stash-free pass drops what its second pass drops.  ``keep_idx`` ([B, keep] patch indices, ascending per row) names
+        the kept patches itself, in any mode.  A ``use_grid=True`` pass never drops: the grid is its output."""
+        if keep_idx is not None:
+            keep_idx = self._check_keep_idx(keep_idx, int(image.shape[0]), bool(use_grid))
         self._ready()
         locked = self.trainable_plan().locked["visual"]
         self._note_pass("visual", locked)
         from .functional import EncodeImageFn
+        tables = (None, None)
+        if keep_idx is not None or (not use_grid and self.drops_patches()):
+            tables = self._patch_tables(int(image.shape[0]), keep_idx)
         if locked:       # nothing in the tower trains: forward-only even with grad mode on -- no stash, no autograd node
             with torch.no_grad():
-                return EncodeImageFn.apply(image, self._trigger, self, bool(use_grid), True)
+                return EncodeImageFn.apply(image, self._trigger, self, bool(use_grid), True, *tables)
         # decided HERE: inside autograd.Function.forward grad mode is always off.  Without grad the tower keeps no stash.
-        return EncodeImageFn.apply(image, self._trigger, self, bool(use_grid), not torch.is_grad_enabled())
+        return EncodeImageFn.apply(image, self._trigger, self, bool(use_grid), not torch.is_grad_enabled(), *tables)
 
     def encode_text(self, text, lengths=None):
         """model_clip.py:398-417.  ``lengths`` (optional, host integers: tokens up to and including each caption's EOT) spares
@@ -935,15 +1049,17 @@ class CLIP(nn.Module):
                 return EncodeTextFn.apply(text, self._trigger, self, True)
         return EncodeTextFn.apply(text, self._trigger, self, not torch.is_grad_enabled())
 
-    def encode_both(self, image, text, use_grid: bool = False):
-        """Image and text towers of one step.  They are independent until the logits, so with
+    def encode_both(self, image, text, use_grid: bool = False, keep_idx=None):
+        """Image and text towers of one step (``keep_idx``: as in ``encode_image``).  They are independent until the logits, so with
         ``tower_streams`` (default) they run on two HIP streams: the ramp-up / tail of every kernel of one
         tower (and the CUs a ragged tile grid leaves idle) is filled by the other tower's kernels.  The
         autograd engine replays each tower's backward on its forward stream, so the backward overlaps too."""
+        if keep_idx is not None:      # checked before anything is enqueued on the side streams
+            keep_idx = self._check_keep_idx(keep_idx, int(image.shape[0]), bool(use_grid))
         self._ready()
         if not getattr(self, "tower_streams", True):
             self._main_stream = None
-            return self.encode_image(image, use_grid), self.encode_text(text)
+            return self.encode_image(image, use_grid, keep_idx), self.encode_text(text)
         if getattr(self, "_side_streams", None) is None or self._side_streams[0].device != self._flat.device:
             # the image tower is the longer chain: its stream gets the higher priority, the text tower's kernels fill
             # in around it (measured 0.7 % on the step; CE_IMG_STREAM_PRIORITY / CE_TXT_STREAM_PRIORITY override)
@@ -956,7 +1072,7 @@ class CLIP(nn.Module):
         s_img.wait_stream(cur)
         s_txt.wait_stream(cur)
         with torch.cuda.stream(s_img):
-            image_features = self.encode_image(image, use_grid)
+            image_features = self.encode_image(image, use_grid, keep_idx)
         with torch.cuda.stream(s_txt):
             text_features = self.encode_text(text)
         cur.wait_stream(s_img)

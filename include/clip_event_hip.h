@@ -200,6 +200,31 @@ int ce_im2col(const float* image, void* patches, int B, int resolution, int patc
 int ce_vision_assemble(const float* patch_out, const float* cls, const float* pos, float* x0, int B, int tokens,
                        int D, void* stream);
 int ce_vision_assemble_bwd(const float* dx0, void* dpatch, int B, int tokens, int D, void* stream);
+/* ---- patch dropout (FLIP): the image tower trains on `keep` of the N = (R/p)^2 patches of every image ----
+ * ce_patch_keep chooses them.  The choice is counter-based (no generator state; a pass can be replayed exactly).  With
+ * fmix32 the murmur3 finaliser on uint32, shifts and multiplies mod 2^32:
+ *     h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16
+ * the key of patch t of sample s = sample0 + b (b the row in the pass), for seed S and draw d (all taken mod 2^32), is
+ *     a = fmix32(S + 0x9E3779B9);  b' = fmix32(a ^ d);  c = fmix32(b' ^ s);  key = fmix32(c ^ t)
+ * fmix32 is a bijection, so the keys of one sample are pairwise different; the kept set is the `keep` patches with the
+ * smallest keys.  One launch writes keep_idx [B,keep] (the kept patches in ascending patch order) and, when `inv` is not
+ * NULL, inv [B,N] (slot j of patch t in keep_idx, or -1 for a dropped patch).  1 <= keep <= N <= 4095. */
+int ce_patch_keep(long seed, long draw, long sample0, int B, int N, int keep, int* keep_idx, int* inv, void* stream);
+/* The kernels below clamp every index they read from keep_idx / inv into range: a bad device-side list cannot make them
+ * read outside their buffers.
+ * ce_im2col's rows for the kept patches only: patches [B*keep, k_padded], row b*keep+j bit-identical to row
+ * b*N + keep_idx[b,j] of ce_im2col (same 16-byte path for patch 8 / 16 / 32, same generic path, same zero padding). */
+int ce_im2col_rows(const float* image, const int* keep_idx, void* patches, int B, int keep, int resolution, int patch,
+                   int k_padded, void* stream);
+/* x0 [B, keep+1, D]:  x0[b,0,:] = class_embedding + positional_embedding[0,:];
+ * x0[b,1+j,:] = patch_out[b*keep+j,:] + positional_embedding[1 + keep_idx[b,j],:].  N bounds the index.  Its patch-row
+ * backward is ce_vision_assemble_bwd at tokens = keep+1. */
+int ce_vision_assemble_rows(const float* patch_out, const int* keep_idx, const float* cls, const float* pos, float* x0,
+                            int B, int N, int keep, int D, void* stream);
+/* dx0 [B, keep+1, D] -> dpos [N+1, D]:  dpos[0,:] += sum_b dx0[b,0,:];
+ * dpos[1+t,:] += sum_{b : inv[b,t] >= 0} dx0[b, 1+inv[b,t], :].  b ascends and no atomics are used: bit-identical run to
+ * run.  A row that no sample kept is not touched. */
+int ce_pos_embed_bwd_rows(const float* dx0, const int* inv, float* dpos, int B, int N, int keep, int D, void* stream);
 /* x0[r,:] = token_embedding[ids[e],:] + positional_embedding[e % tokens,:], e = src_rows ? src_rows[r] : r
  * (model_clip.py:400-403).  src_rows selects the LIVE tokens of a packed batch: under the causal mask
  * (model_clip.py:377-384) the rows after a caption's EOT can influence neither its feature (taken at the EOT,

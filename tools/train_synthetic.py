@@ -10,7 +10,9 @@ activation stash does not fit).
 
 Partial fine-tuning: ``--lock-image-tower`` / ``--lock-text-tower`` freeze a tower (``--unlocked-layers N``: except its top N blocks
 and its output side), ``--no-decay-groups`` puts gains, biases and ``logit_scale`` into a parameter group without weight decay,
-``--adamw`` decouples the decay (both with ``--optimizer adam`` and a weight decay of 0.1; the fused step stays in use)."""
+``--adamw`` decouples the decay (both with ``--optimizer adam`` and a weight decay of 0.1; the fused step stays in use).
+
+``--patch-dropout P`` trains the image tower on a random ``1 - P`` of the patches of every image (CLIP.set_patch_dropout)."""
 import argparse
 import os
 import sys
@@ -49,6 +51,8 @@ def main():
     ap.add_argument("--unlocked-layers", type=int, default=0, metavar="N", help="blocks a locked tower keeps trainable, from the top")
     ap.add_argument("--no-decay-groups", action="store_true", help="optim.no_decay_groups: no weight decay on gains, biases, logit_scale")
     ap.add_argument("--adamw", action="store_true", help="decoupled weight decay (FusedAdam(decoupled=True))")
+    ap.add_argument("--patch-dropout", type=float, default=0.0, metavar="P",
+                    help="train the image tower on a random 1 - P of the patches (CLIP.set_patch_dropout)")
     args = ap.parse_args()
     if args.adamw and args.optimizer != "adam":
         ap.error("--adamw goes with --optimizer adam")
@@ -80,6 +84,7 @@ def main():
         return FusedSGD(m, lr=cfg["lr"], momentum=cfg["momentum"], weight_decay=cfg["weight_decay"], max_norm=1.0, groups=groups)
 
     lock(model)
+    model.set_patch_dropout(args.patch_dropout, seed=0)
     optimizer = make_optimizer(model)
     scheduler = build_lr_scheduler(cfg, optimizer, 0)                           # engine.py:154-176
     data = batch(rng, B, K, dev)                                                # one fixed batch: the loss must fall
@@ -89,12 +94,16 @@ def main():
         scheduler.step()
         losses.append(float(sum(v.detach() for v in ld.values())))
     print("loss:", " ".join(f"{v:.3f}" for v in losses[::3]), "lr", optimizer.param_groups[0]["lr"])
-    # (a locked tower cannot follow the fixed batch as fast: the loss must still fall)
-    assert losses[-1] < (0.5 if not (args.lock_image_tower or args.lock_text_tower) else 1.0) * losses[0]
+    # (a locked tower, or an image tower that sees other patches every step, cannot follow the fixed batch as fast: the loss
+    # must still fall)
+    assert losses[-1] < (0.5 if not (args.lock_image_tower or args.lock_text_tower or args.patch_dropout) else 1.0) * losses[0]
     with tempfile.TemporaryDirectory() as d:
         path = checkpoint.save_model_on_master(model, d, cfg["task"], 20, 0.0, optimizer)      # engine.py:202-218
         model2, opt_state, begin_epoch, _ = checkpoint.load_checkpoint(path, device=dev)       # train.py:101-124
         lock(model2)
+        # neither the rate nor the draw counter is in the checkpoint: a resumed run sets them again
+        model2.set_patch_dropout(args.patch_dropout, seed=0)
+        model2.patch_draw = model.patch_draw
         optimizer2 = make_optimizer(model2)
         optimizer2.load_state_dict(opt_state)
         scheduler2 = build_lr_scheduler(cfg, optimizer2, begin_epoch)
