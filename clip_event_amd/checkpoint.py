@@ -7,6 +7,10 @@ and shapes, ``optimizer`` is ``torch.optim.Adam``'s format (optim.FusedAdam spea
 Loading follows train.py:101-124 (resume) and also accepts a bare state dict such as the OpenAI ViT-B/32 weights
 (fp16 tensors are widened to the fp32 masters by ``build_model``).  Files are read with ``weights_only=True``:
 nothing in a checkpoint is executed.
+
+An optimiser with a weight average (``optimizer.enable_ema``) adds one entry, ``'ema'``: ``optimizer.ema_state_dict()`` with
+its tensors on the CPU, read back by ``load_ema``.  Without one the file has exactly the reference's five keys.  A checkpoint
+OF the averaged weights in the reference's layout is ``with optimizer.averaged(): save_model_on_master(...)``.
 """
 from __future__ import annotations
 
@@ -29,7 +33,11 @@ def checkpoint_dict(model, optimizer, task: str, epoch: int, best_perf: float) -
         opt = {"state": {i: {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in st.items()}
                          for i, st in opt["state"].items()},
                "param_groups": opt["param_groups"]}
-    return {"epoch": epoch, "model": task, "state_dict": states, "perf": best_perf, "optimizer": opt}
+    ckpt = {"epoch": epoch, "model": task, "state_dict": states, "perf": best_perf, "optimizer": opt}
+    if getattr(optimizer, "ema_enabled", False):
+        ema = optimizer.ema_state_dict()
+        ckpt["ema"] = {**ema, "shadow": {k: v.detach().cpu() for k, v in ema["shadow"].items()}}
+    return ckpt
 
 
 def save_model_on_master(model, ckpt_dir: str, task: str, epoch: int, best_perf: float, optimizer=None) -> Optional[str]:
@@ -63,3 +71,11 @@ def load_checkpoint(path: str, device=None, is_train: bool = True) -> Tuple[Any,
     if device is not None:
         model = model.to(device)
     return model, opt_state, begin_epoch, best_perf
+
+
+def load_ema(path: str) -> Optional[dict]:
+    """The ``'ema'`` entry of a checkpoint (``optimizer.load_ema_state_dict`` takes it), or None when the file has none."""
+    if not os.path.exists(path):
+        raise FileNotFoundError("=> error when loading checkpoint (cannot find checkpoint): {}".format(path))
+    blob = torch.load(path, map_location="cpu", weights_only=True)
+    return blob.get("ema") if isinstance(blob, dict) else None

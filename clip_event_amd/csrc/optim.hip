@@ -96,6 +96,16 @@ __device__ __forceinline__ void sgd_elem(float& p, float g, float& buf, float co
     p = __builtin_fmaf(-lr, upd, p);
 }
 
+// One element of the weight average, e <- e + rate (p_new - e) with rate = 1 - decay, in torch's lerp_ form: below a weight of 0.5
+// fma(p_new - e, rate, e), from 0.5 on p_new - (p_new - e) (1 - rate), so that rate 1 gives p_new itself (the branch is uniform
+// over the launch).  p_new is the fp32 master exactly as the rule just wrote it.  As adam_elem / sgd_elem: the subtraction and the
+// multiply-add are spelled out, so that every traversal gives the same bits.
+__device__ __forceinline__ void ema_elem(float& e, float p_new, float rate) {
+#pragma clang fp contract(off)
+    const float d = p_new - e;
+    e = rate < 0.5f ? __builtin_fmaf(d, rate, e) : p_new - d * (1.0f - rate);
+}
+
 __device__ __forceinline__ float clip_coef(const float* __restrict__ sumsq, float max_norm) {
     return sumsq ? fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f)) : 1.0f;
 }
@@ -226,19 +236,40 @@ __device__ __forceinline__ void elem4(const Rule& rule, f32x4& p, f32x4 g, f32x4
     }
 }
 
+// the four lanes of a 16-byte chunk of the average through ema_elem
+__device__ __forceinline__ void ema4(f32x4& e, const f32x4& p_new, float rate) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float ek = e[k];
+        ema_elem(ek, p_new[k], rate);
+        e[k] = ek;
+    }
+}
+
 // ---- the traversals --------------------------------------------------------------------------------------------------------------
 // Each is one kernel template over the rule.  The state streams are the kernel parameters s0, s1 (NULL beyond Rule::NS; parameters
 // rather than an array so that they keep __restrict__) and are named only under `k < Rule::NS`: a rule with NS == 0 issues no
 // state traffic at all.  Cache policy: p and the state through CE_ADAM_LD / CE_ADAM_ST, g always nontemporal.
+// EMA (compile time): the traversal also carries the weight average `ema` -- one more stream, requested with the others, updated
+// from the new master in registers (ema_elem) and stored like the state.  Without it `ema` / `ema_rate` are never named.
 
-// the request for one 16-byte chunk of every stream at element offset `at`: p, g, then the state streams
-template <class Rule>
-__device__ __forceinline__ void load_chunk(float* p, const float* g, float* const (&st)[2], long at, f32x4& pv, f32x4& gv,
-                                           f32x4 (&sv)[kSlots<Rule>]) {
+// the request for one 16-byte chunk of every stream at element offset `at`: p, g, then the state streams, then the average
+template <class Rule, bool EMA>
+__device__ __forceinline__ void load_chunk(float* p, const float* g, float* const (&st)[2], float* ema, long at, f32x4& pv, f32x4& gv,
+                                           f32x4 (&sv)[kSlots<Rule>], f32x4& ev) {
     pv = CE_ADAM_LD(reinterpret_cast<f32x4*>(p + at));
     gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + at));
 #pragma unroll
     for (int k = 0; k < Rule::NS; ++k) sv[k] = CE_ADAM_LD(reinterpret_cast<f32x4*>(st[k] + at));
+    if constexpr (EMA) ev = CE_ADAM_LD(reinterpret_cast<f32x4*>(ema + at));
+}
+// the average of one chunk from its new masters, and its store
+template <bool EMA>
+__device__ __forceinline__ void update_ema(float* ema, long at, f32x4& ev, const f32x4& p_new, float rate) {
+    if constexpr (EMA) {
+        ema4(ev, p_new, rate);
+        CE_ADAM_ST(ev, reinterpret_cast<f32x4*>(ema + at));
+    }
 }
 template <class Rule>
 __device__ __forceinline__ void store_state(float* const (&st)[2], long at, const f32x4 (&sv)[kSlots<Rule>]) {
@@ -249,19 +280,19 @@ __device__ __forceinline__ u32x2 pack_bf4(const f32x4& v) { return u32x2{pack_bf
 
 // Flat: grid-stride over [0, n).  Two 16-byte chunks per lane and iteration, every load issued before the first use: the pass is
 // pure streaming (Adam: 16 B read + 14 B written per parameter) and wants as many bytes in flight as the registers allow.
-template <class Rule>
+template <class Rule, bool EMA>
 __global__ __launch_bounds__(256) void optim_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
                                                          float* __restrict__ s1, bf16_t* __restrict__ p16, long n,
-                                                         typename Rule::Args a) {
+                                                         typename Rule::Args a, float* __restrict__ ema, float ema_rate) {
     const Rule rule(a, 0);
     float* const st[2] = {s0, s1};
     const long stride = gridDim.x * 2048L;
     for (long i0 = blockIdx.x * 2048L + threadIdx.x * 4; i0 < n; i0 += stride) {
         const long i1 = i0 + 1024;
         if (i1 + 3 < n) {
-            f32x4 pv[2], gv[2], sv[2][kSlots<Rule>] = {};
+            f32x4 pv[2], gv[2], sv[2][kSlots<Rule>] = {}, ev[2] = {};
 #pragma unroll
-            for (int u = 0; u < 2; ++u) load_chunk<Rule>(p, g, st, u ? i1 : i0, pv[u], gv[u], sv[u]);
+            for (int u = 0; u < 2; ++u) load_chunk<Rule, EMA>(p, g, st, ema, u ? i1 : i0, pv[u], gv[u], sv[u], ev[u]);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const long i = u ? i1 : i0;
@@ -269,6 +300,7 @@ __global__ __launch_bounds__(256) void optim_flat_kernel(float* __restrict__ p, 
                 CE_ADAM_ST(pv[u], reinterpret_cast<f32x4*>(p + i));
                 if (p16) *reinterpret_cast<u32x2*>(p16 + i) = pack_bf4(pv[u]);
                 store_state<Rule>(st, i, sv[u]);
+                update_ema<EMA>(ema, i, ev[u], pv[u], ema_rate);
             }
         } else {
             for (int u = 0; u < 2; ++u) {
@@ -282,6 +314,11 @@ __global__ __launch_bounds__(256) void optim_flat_kernel(float* __restrict__ p, 
 #pragma unroll
                     for (int q = 0; q < Rule::NS; ++q) st[q][k] = sk[q];
                     if (p16) p16[k] = f2bf(pk);
+                    if constexpr (EMA) {
+                        float ek = ema[k];
+                        ema_elem(ek, pk, ema_rate);
+                        ema[k] = ek;
+                    }
                 }
             }
         }
@@ -381,18 +418,19 @@ __global__ __launch_bounds__(256) void multi_transpose_kernel(const ce_transpose
 // tile, the W^T copy the input-gradient GEMMs read (`job.dst`, [cols][rows]) -- so that no separate transpose pass re-reads the
 // mirror (`multi_transpose_kernel`: 0.17 GB read + a launch beside the next forward's first kernels).  `job.src` points into the
 // flat mirror `p16`: its offset there is the matrix's offset in every flat buffer.  rows, cols multiples of 8.
-template <class Rule>
+template <class Rule, bool EMA>
 __global__ __launch_bounds__(256) void optim_tiles_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
                                                           float* __restrict__ s1, bf16_t* __restrict__ p16,
-                                                          const ce_transpose_job* __restrict__ jobs, int njobs, typename Rule::Args a) {
+                                                          const ce_transpose_job* __restrict__ jobs, int njobs, typename Rule::Args a,
+                                                          float* __restrict__ ema, float ema_rate) {
     __shared__ bf16_t tile[64][66];
     Rule rule(a, 0);
     float* const st[2] = {s0, s1};
     const tile_at t = find_tile(jobs, njobs);
     if constexpr (Rule::GROUPED) rule.set_group(a, t.job.pad_);
     const long off = reinterpret_cast<const bf16_t*>(t.job.src) - p16;
-    // 64 rows x 16 four-element chunks; all loads of a thread (Adam: sixteen) in flight before the first use
-    f32x4 pv[4] = {}, gv[4] = {}, sv[4][kSlots<Rule>] = {};
+    // 64 rows x 16 four-element chunks; all loads of a thread (Adam: sixteen, with the average twenty) in flight before the first use
+    f32x4 pv[4] = {}, gv[4] = {}, sv[4][kSlots<Rule>] = {}, ev[4] = {};
     bool ok[4];
     long at[4];
 #pragma unroll
@@ -401,7 +439,7 @@ __global__ __launch_bounds__(256) void optim_tiles_kernel(float* __restrict__ p,
         const int r = idx >> 4, ch = idx & 15;
         ok[k] = t.r0 + r < t.job.rows && t.c0 + ch * 4 < t.job.cols;
         at[k] = off + (long)(t.r0 + r) * t.job.cols + t.c0 + ch * 4;
-        if (ok[k]) load_chunk<Rule>(p, g, st, at[k], pv[k], gv[k], sv[k]);
+        if (ok[k]) load_chunk<Rule, EMA>(p, g, st, ema, at[k], pv[k], gv[k], sv[k], ev[k]);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -416,6 +454,7 @@ __global__ __launch_bounds__(256) void optim_tiles_kernel(float* __restrict__ p,
             __builtin_nontemporal_store(pk, reinterpret_cast<u32x2*>(p16 + at[k]));       // (nt on the mirror and on W^T: 1034 -> 986 us for
                                                                                           //  the ViT-B/32 Adam step in a loop of its own)
             store_state<Rule>(st, at[k], sv[k]);
+            update_ema<EMA>(ema, at[k], ev[k], pv[k], ema_rate);
         }
     }
     __syncthreads();
@@ -424,23 +463,24 @@ __global__ __launch_bounds__(256) void optim_tiles_kernel(float* __restrict__ p,
 
 // Segments: the same update over a table of [lo, hi) chunks of the flat buffers (everything that is not one of the matrices
 // above): one workgroup per chunk of at most 2048 elements, both 16-byte pieces of a thread requested before the first use
-template <class Rule>
+template <class Rule, bool EMA>
 __global__ __launch_bounds__(256) void optim_segments_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
                                                              float* __restrict__ s1, bf16_t* __restrict__ p16,
-                                                             const long* __restrict__ table, typename Rule::Args a) {
+                                                             const long* __restrict__ table, typename Rule::Args a,
+                                                             float* __restrict__ ema, float ema_rate) {
     int group = 0;
     if constexpr (Rule::GROUPED) group = a.groups.segment_group ? a.groups.segment_group[blockIdx.x] : 0;
     const Rule rule(a, group);
     float* const st[2] = {s0, s1};
     const long lo = table[2 * blockIdx.x], hi = table[2 * blockIdx.x + 1];
-    f32x4 pv[2] = {}, gv[2] = {}, sv[2][kSlots<Rule>] = {};
+    f32x4 pv[2] = {}, gv[2] = {}, sv[2][kSlots<Rule>] = {}, ev[2] = {};
     long at[2];
     bool ok[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         at[u] = lo + threadIdx.x * 4 + u * 1024;
         ok[u] = at[u] + 3 < hi;
-        if (ok[u]) load_chunk<Rule>(p, g, st, at[u], pv[u], gv[u], sv[u]);
+        if (ok[u]) load_chunk<Rule, EMA>(p, g, st, ema, at[u], pv[u], gv[u], sv[u], ev[u]);
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -449,6 +489,29 @@ __global__ __launch_bounds__(256) void optim_segments_kernel(float* __restrict__
         CE_ADAM_ST(pv[u], reinterpret_cast<f32x4*>(p + at[u]));
         if (p16) *reinterpret_cast<u32x2*>(p16 + at[u]) = pack_bf4(pv[u]);
         store_state<Rule>(st, at[u], sv[u]);
+        update_ema<EMA>(ema, at[u], ev[u], pv[u], ema_rate);
+    }
+}
+
+// a <-> b element for element, and a16 = the bf16 mirror (f2bf, as ce_cast_bf16) of what lands in a: the swap between the masters
+// and their average in one pass (16 B read + 18 B written per element), 16-byte chunks and a scalar tail
+__global__ __launch_bounds__(256) void swap_cast_kernel(float* __restrict__ a, float* __restrict__ b, bf16_t* __restrict__ a16, long n) {
+    const long stride = gridDim.x * 1024L;
+    for (long i = blockIdx.x * 1024L + threadIdx.x * 4; i < n; i += stride) {
+        if (i + 3 < n) {
+            const f32x4 av = CE_ADAM_LD(reinterpret_cast<f32x4*>(a + i));
+            const f32x4 bv = CE_ADAM_LD(reinterpret_cast<f32x4*>(b + i));
+            CE_ADAM_ST(bv, reinterpret_cast<f32x4*>(a + i));
+            CE_ADAM_ST(av, reinterpret_cast<f32x4*>(b + i));
+            *reinterpret_cast<u32x2*>(a16 + i) = pack_bf4(bv);
+        } else {
+            for (long k = i; k < n; ++k) {
+                const float ak = a[k], bk = b[k];
+                a[k] = bk;
+                b[k] = ak;
+                a16[k] = f2bf(bk);
+            }
+        }
     }
 }
 
@@ -487,22 +550,48 @@ unsigned flat_blocks(long n) {
     const long blocks = (n + 2047) / 2048;
     return (unsigned)(blocks > cap ? cap : blocks);
 }
+// `ema` (every launcher): NULL = the step as it is without a weight average (the kernels' EMA = false instantiations, which never name
+// the pointer); otherwise the EMA instantiation of the same kernels
 template <class Rule>
-void launch_flat(float* p, const float* g, float* s0, float* s1, void* p_bf16, long n, const typename Rule::Args& a, void* stream) {
-    hipLaunchKernelGGL(optim_flat_kernel<Rule>, dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, s0, s1,
-                       (bf16_t*)p_bf16, n, a);
+void launch_flat(float* p, const float* g, float* s0, float* s1, void* p_bf16, long n, const typename Rule::Args& a, void* stream,
+                 float* ema = nullptr, float ema_rate = 0.f) {
+    if (ema)
+        hipLaunchKernelGGL((optim_flat_kernel<Rule, true>), dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, s0, s1,
+                           (bf16_t*)p_bf16, n, a, ema, ema_rate);
+    else
+        hipLaunchKernelGGL((optim_flat_kernel<Rule, false>), dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, s0, s1,
+                           (bf16_t*)p_bf16, n, a, ema, 0.f);
 }
 
 // the matrices of the job table in tiles, then the [lo, hi) table in segments; either table may be empty
 template <class Rule>
 void launch_tiles(float* p, const float* g, float* s0, float* s1, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
-                  int total_tiles, const long* segments_device, int nsegments, const typename Rule::Args& a, void* stream) {
-    if (jobs_device && njobs > 0 && total_tiles > 0)
-        hipLaunchKernelGGL(optim_tiles_kernel<Rule>, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, p, g, s0, s1,
-                           (bf16_t*)p_bf16, jobs_device, njobs, a);
-    if (segments_device && nsegments > 0)
-        hipLaunchKernelGGL(optim_segments_kernel<Rule>, dim3((unsigned)nsegments), dim3(256), 0, (hipStream_t)stream, p, g, s0, s1,
-                           (bf16_t*)p_bf16, segments_device, a);
+                  int total_tiles, const long* segments_device, int nsegments, const typename Rule::Args& a, void* stream,
+                  float* ema = nullptr, float ema_rate = 0.f) {
+    const hipStream_t s = (hipStream_t)stream;
+    if (jobs_device && njobs > 0 && total_tiles > 0) {
+        if (ema)
+            hipLaunchKernelGGL((optim_tiles_kernel<Rule, true>), dim3((unsigned)total_tiles), dim3(256), 0, s, p, g, s0, s1,
+                               (bf16_t*)p_bf16, jobs_device, njobs, a, ema, ema_rate);
+        else
+            hipLaunchKernelGGL((optim_tiles_kernel<Rule, false>), dim3((unsigned)total_tiles), dim3(256), 0, s, p, g, s0, s1,
+                               (bf16_t*)p_bf16, jobs_device, njobs, a, ema, 0.f);
+    }
+    if (segments_device && nsegments > 0) {
+        if (ema)
+            hipLaunchKernelGGL((optim_segments_kernel<Rule, true>), dim3((unsigned)nsegments), dim3(256), 0, s, p, g, s0, s1,
+                               (bf16_t*)p_bf16, segments_device, a, ema, ema_rate);
+        else
+            hipLaunchKernelGGL((optim_segments_kernel<Rule, false>), dim3((unsigned)nsegments), dim3(256), 0, s, p, g, s0, s1,
+                               (bf16_t*)p_bf16, segments_device, a, ema, 0.f);
+    }
+}
+
+// what every _ema entry point asks of its two extra arguments; 0 or -EINVAL with a message
+int ema_check(const char* who, const float* ema, float ema_rate) {
+    CE_CHECK_ARG(ema, "%s: ema is NULL", who);
+    CE_CHECK_ARG(ema_rate > 0.f && ema_rate <= 1.f, "%s: ema_rate %g is outside (0, 1]", who, (double)ema_rate);
+    return 0;
 }
 
 }  // namespace
@@ -531,53 +620,151 @@ extern "C" int ce_sumsq(const float* g, long n, float* out, void* stream) {
 }
 
 
+// ---- the step entry points: each form once, for the plain entry point (ema NULL) and its _ema twin ------------------------------
+namespace {
+
+int adam_step(const char* who, float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* sumsq, float max_norm,
+              float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* ema, float ema_rate, void* stream) {
+    CE_CHECK_ARG(n > 0 && step >= 1, "%s: need n>0 and step>=1", who);
+    launch_flat<AdamRule>(p, g, m, v, p_bf16, n, adam_args(sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step), stream, ema,
+                          ema_rate);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+int adam_step_tiles(const char* who, float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
+                    int njobs, int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
+                    float beta1, float beta2, float eps, float weight_decay, int step, float* ema, float ema_rate, void* stream) {
+    CE_CHECK_ARG(p && g && m && v && p_bf16 && step >= 1, "%s: null buffer or step < 1", who);
+    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
+    launch_tiles<AdamRule>(p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                           adam_args(sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step), stream, ema, ema_rate);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+int sgd_step(const char* who, float* p, const float* g, float* buf, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+             float momentum, float dampening, float weight_decay, int nesterov, int first_step, float* ema, float ema_rate,
+             void* stream) {
+    CE_CHECK_ARG(n > 0, "%s: need n>0", who);
+    if (int rc = sgd_check(who, buf, momentum, dampening, nesterov)) return rc;
+    CE_CHECK_ARG(p && g, "%s: null buffer", who);
+    const sgd_args a = {sumsq, max_norm, lr, momentum, 1.0f - dampening, weight_decay, first_step != 0, nesterov != 0};
+    if (momentum > 0.f) launch_flat<SgdRule<true>>(p, g, buf, nullptr, p_bf16, n, a, stream, ema, ema_rate);
+    else launch_flat<SgdRule<false>>(p, g, nullptr, nullptr, p_bf16, n, a, stream, ema, ema_rate);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+int sgd_step_tiles(const char* who, float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                   int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
+                   float momentum, float dampening, float weight_decay, int nesterov, int first_step, float* ema, float ema_rate,
+                   void* stream) {
+    if (int rc = sgd_check(who, buf, momentum, dampening, nesterov)) return rc;
+    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
+    CE_CHECK_ARG(p && g && p_bf16, "%s: null buffer", who);
+    const sgd_args a = {sumsq, max_norm, lr, momentum, 1.0f - dampening, weight_decay, first_step != 0, nesterov != 0};
+    if (momentum > 0.f)
+        launch_tiles<SgdRule<true>>(p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream,
+                                    ema, ema_rate);
+    else
+        launch_tiles<SgdRule<false>>(p, g, nullptr, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a,
+                                     stream, ema, ema_rate);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+int adam_step_groups(const char* who, float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
+                     int njobs, int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
+                     const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float beta1, float beta2, float eps,
+                     int step, float* ema, float ema_rate, void* stream) {
+    CE_CHECK_ARG(p && g && m && v && p_bf16 && step >= 1, "%s: null buffer or step < 1", who);
+    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
+    AdamGroupRule::Args a = {sumsq, max_norm, beta1, beta2, eps, adam_bc1(beta1, step), adam_bc2_sqrt(beta2, step), {}};
+    if (int rc = fill_groups(who, a.groups, groups, ngroups, segment_group, true)) return rc;
+    launch_tiles<AdamGroupRule>(p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream, ema, ema_rate);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+int sgd_step_groups(const char* who, float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                    int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
+                    float max_norm, const ce_optim_group* groups, int ngroups, float momentum, float dampening, int nesterov,
+                    int first_step, float* ema, float ema_rate, void* stream) {
+    if (int rc = sgd_check(who, buf, momentum, dampening, nesterov)) return rc;
+    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
+    CE_CHECK_ARG(p && g && p_bf16, "%s: null buffer", who);
+    sgd_group_args a = {sumsq, max_norm, momentum, 1.0f - dampening, first_step != 0, nesterov != 0, {}};
+    if (int rc = fill_groups(who, a.groups, groups, ngroups, segment_group, false)) return rc;
+    if (momentum > 0.f)
+        launch_tiles<SgdGroupRule<true>>(p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a,
+                                         stream, ema, ema_rate);
+    else
+        launch_tiles<SgdGroupRule<false>>(p, g, nullptr, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                                          a, stream, ema, ema_rate);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
 extern "C" int ce_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* sumsq,
                             float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                             void* stream) {
-    CE_CHECK_ARG(n > 0 && step >= 1, "ce_adam_step: need n>0 and step>=1");
-    launch_flat<AdamRule>(p, g, m, v, p_bf16, n, adam_args(sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step), stream);
-    CE_LAUNCH_CHECK();
-    return 0;
+    return adam_step("ce_adam_step", p, g, m, v, p_bf16, n, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step, nullptr, 0.f,
+                     stream);
+}
+extern "C" int ce_adam_step_ema(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* sumsq,
+                                float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                float* ema, float ema_rate, void* stream) {
+    if (int rc = ema_check("ce_adam_step_ema", ema, ema_rate)) return rc;
+    return adam_step("ce_adam_step_ema", p, g, m, v, p_bf16, n, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step, ema,
+                     ema_rate, stream);
 }
 
 extern "C" int ce_adam_step_tiles(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
                                   int njobs, int total_tiles, const long* segments_device, int nsegments, const float* sumsq,
                                   float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                   void* stream) {
-    CE_CHECK_ARG(p && g && m && v && p_bf16 && step >= 1, "ce_adam_step_tiles: null buffer or step < 1");
-    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "ce_adam_step_tiles: nothing to update");
-    launch_tiles<AdamRule>(p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
-                           adam_args(sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step), stream);
-    CE_LAUNCH_CHECK();
-    return 0;
+    return adam_step_tiles("ce_adam_step_tiles", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, sumsq,
+                           max_norm, lr, beta1, beta2, eps, weight_decay, step, nullptr, 0.f, stream);
+}
+extern "C" int ce_adam_step_tiles_ema(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
+                                      int njobs, int total_tiles, const long* segments_device, int nsegments, const float* sumsq,
+                                      float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                      float* ema, float ema_rate, void* stream) {
+    if (int rc = ema_check("ce_adam_step_tiles_ema", ema, ema_rate)) return rc;
+    return adam_step_tiles("ce_adam_step_tiles_ema", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                           sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step, ema, ema_rate, stream);
 }
 
 extern "C" int ce_sgd_step(float* p, const float* g, float* buf, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
                            float momentum, float dampening, float weight_decay, int nesterov, int first_step, void* stream) {
-    CE_CHECK_ARG(n > 0, "ce_sgd_step: need n>0");
-    if (int rc = sgd_check("ce_sgd_step", buf, momentum, dampening, nesterov)) return rc;
-    CE_CHECK_ARG(p && g, "ce_sgd_step: null buffer");
-    const sgd_args a = {sumsq, max_norm, lr, momentum, 1.0f - dampening, weight_decay, first_step != 0, nesterov != 0};
-    if (momentum > 0.f) launch_flat<SgdRule<true>>(p, g, buf, nullptr, p_bf16, n, a, stream);
-    else launch_flat<SgdRule<false>>(p, g, nullptr, nullptr, p_bf16, n, a, stream);
-    CE_LAUNCH_CHECK();
-    return 0;
+    return sgd_step("ce_sgd_step", p, g, buf, p_bf16, n, sumsq, max_norm, lr, momentum, dampening, weight_decay, nesterov, first_step,
+                    nullptr, 0.f, stream);
+}
+extern "C" int ce_sgd_step_ema(float* p, const float* g, float* buf, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+                               float momentum, float dampening, float weight_decay, int nesterov, int first_step, float* ema,
+                               float ema_rate, void* stream) {
+    if (int rc = ema_check("ce_sgd_step_ema", ema, ema_rate)) return rc;
+    return sgd_step("ce_sgd_step_ema", p, g, buf, p_bf16, n, sumsq, max_norm, lr, momentum, dampening, weight_decay, nesterov,
+                    first_step, ema, ema_rate, stream);
 }
 
 extern "C" int ce_sgd_step_tiles(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
                                  int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm,
                                  float lr, float momentum, float dampening, float weight_decay, int nesterov, int first_step,
                                  void* stream) {
-    if (int rc = sgd_check("ce_sgd_step_tiles", buf, momentum, dampening, nesterov)) return rc;
-    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "ce_sgd_step_tiles: nothing to update");
-    CE_CHECK_ARG(p && g && p_bf16, "ce_sgd_step_tiles: null buffer");
-    const sgd_args a = {sumsq, max_norm, lr, momentum, 1.0f - dampening, weight_decay, first_step != 0, nesterov != 0};
-    if (momentum > 0.f)
-        launch_tiles<SgdRule<true>>(p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
-    else
-        launch_tiles<SgdRule<false>>(p, g, nullptr, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
-    CE_LAUNCH_CHECK();
-    return 0;
+    return sgd_step_tiles("ce_sgd_step_tiles", p, g, buf, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, sumsq,
+                          max_norm, lr, momentum, dampening, weight_decay, nesterov, first_step, nullptr, 0.f, stream);
+}
+extern "C" int ce_sgd_step_tiles_ema(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                                     int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm,
+                                     float lr, float momentum, float dampening, float weight_decay, int nesterov, int first_step,
+                                     float* ema, float ema_rate, void* stream) {
+    if (int rc = ema_check("ce_sgd_step_tiles_ema", ema, ema_rate)) return rc;
+    return sgd_step_tiles("ce_sgd_step_tiles_ema", p, g, buf, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, sumsq,
+                          max_norm, lr, momentum, dampening, weight_decay, nesterov, first_step, ema, ema_rate, stream);
 }
 
 extern "C" int ce_sumsq_segments(const float* g, const long* table_device, int nchunks, float* out, void* stream) {
@@ -591,28 +778,41 @@ extern "C" int ce_adam_step_groups(float* p, const float* g, float* m, float* v,
                                    int njobs, int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
                                    const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float beta1,
                                    float beta2, float eps, int step, void* stream) {
-    CE_CHECK_ARG(p && g && m && v && p_bf16 && step >= 1, "ce_adam_step_groups: null buffer or step < 1");
-    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "ce_adam_step_groups: nothing to update");
-    AdamGroupRule::Args a = {sumsq, max_norm, beta1, beta2, eps, adam_bc1(beta1, step), adam_bc2_sqrt(beta2, step), {}};
-    if (int rc = fill_groups("ce_adam_step_groups", a.groups, groups, ngroups, segment_group, true)) return rc;
-    launch_tiles<AdamGroupRule>(p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
-    CE_LAUNCH_CHECK();
-    return 0;
+    return adam_step_groups("ce_adam_step_groups", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                            segment_group, sumsq, max_norm, groups, ngroups, beta1, beta2, eps, step, nullptr, 0.f, stream);
+}
+extern "C" int ce_adam_step_groups_ema(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
+                                       int njobs, int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
+                                       const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float beta1,
+                                       float beta2, float eps, int step, float* ema, float ema_rate, void* stream) {
+    if (int rc = ema_check("ce_adam_step_groups_ema", ema, ema_rate)) return rc;
+    return adam_step_groups("ce_adam_step_groups_ema", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                            segment_group, sumsq, max_norm, groups, ngroups, beta1, beta2, eps, step, ema, ema_rate, stream);
 }
 
 extern "C" int ce_sgd_step_groups(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
                                   int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
                                   const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float momentum,
                                   float dampening, int nesterov, int first_step, void* stream) {
-    if (int rc = sgd_check("ce_sgd_step_groups", buf, momentum, dampening, nesterov)) return rc;
-    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "ce_sgd_step_groups: nothing to update");
-    CE_CHECK_ARG(p && g && p_bf16, "ce_sgd_step_groups: null buffer");
-    sgd_group_args a = {sumsq, max_norm, momentum, 1.0f - dampening, first_step != 0, nesterov != 0, {}};
-    if (int rc = fill_groups("ce_sgd_step_groups", a.groups, groups, ngroups, segment_group, false)) return rc;
-    if (momentum > 0.f)
-        launch_tiles<SgdGroupRule<true>>(p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
-    else
-        launch_tiles<SgdGroupRule<false>>(p, g, nullptr, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream);
+    return sgd_step_groups("ce_sgd_step_groups", p, g, buf, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                           segment_group, sumsq, max_norm, groups, ngroups, momentum, dampening, nesterov, first_step, nullptr, 0.f,
+                           stream);
+}
+extern "C" int ce_sgd_step_groups_ema(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                                      int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
+                                      const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float momentum,
+                                      float dampening, int nesterov, int first_step, float* ema, float ema_rate, void* stream) {
+    if (int rc = ema_check("ce_sgd_step_groups_ema", ema, ema_rate)) return rc;
+    return sgd_step_groups("ce_sgd_step_groups_ema", p, g, buf, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                           segment_group, sumsq, max_norm, groups, ngroups, momentum, dampening, nesterov, first_step, ema, ema_rate,
+                           stream);
+}
+
+extern "C" int ce_swap_cast_bf16(float* a, float* b, void* a_bf16, long n, void* stream) {
+    CE_CHECK_ARG(a && b && a_bf16 && a != b && n > 0, "ce_swap_cast_bf16: null or identical buffers, or n <= 0");
+    CE_CHECK_ARG((reinterpret_cast<size_t>(a) | reinterpret_cast<size_t>(b)) % 16 == 0 && reinterpret_cast<size_t>(a_bf16) % 8 == 0,
+                 "ce_swap_cast_bf16: a and b must be 16-byte aligned, a_bf16 8-byte aligned");
+    hipLaunchKernelGGL(swap_cast_kernel, dim3(flat_blocks(2 * n)), dim3(256), 0, (hipStream_t)stream, a, b, (bf16_t*)a_bf16, n);
     CE_LAUNCH_CHECK();
     return 0;
 }

@@ -4,6 +4,7 @@ synchronisation -- and the learning-rate schedules of utils.py:310-416 / build_l
 (host arithmetic: one float per step)."""
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from bisect import bisect_right
@@ -21,6 +22,16 @@ MAX_GROUPS = 8
 class OptimGroup(ctypes.Structure):
     """``ce_optim_group`` of include/clip_event_hip.h."""
     _fields_ = [("lr", c_float), ("weight_decay", c_float), ("decoupled", c_int), ("pad_", c_int)]
+
+
+def ema_rate(decay: float, warmup: bool, updates: int) -> float:
+    """The weight of the new masters in the ``updates + 1``-th update of the weight average: ``1 - decay``, or with ``warmup``
+    ``1 - min(decay, (1 + updates) / (10 + updates))`` (the TF / timm rule: 0.9, 9/11, ... until the cap, so that a young
+    average is not dominated by its start).  Python floats; the kernels take it rounded once to fp32."""
+    d = float(decay)
+    if warmup:
+        d = min(d, (1.0 + updates) / (10.0 + updates))
+    return 1.0 - d
 
 
 class _FusedFlatOptimizer(torch.optim.Optimizer):
@@ -41,7 +52,16 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
     ``segment_group`` behind ``nsegments`` and ``groups, ngroups`` in place of lr / weight decay) and its torch counterpart
     (``_stock``), and provides ``_state()`` (allocate the flat state buffers and ``sumsq``), ``_step_args(sumsq)`` /
     ``_group_args(sumsq)`` (the state buffers the kernels take and the rule's scalar arguments, without lr / weight decay in the
-    grouped form) and ``_after_step(sharded)`` (what to note once the step is launched)."""
+    grouped form) and ``_after_step(sharded)`` (what to note once the step is launched).
+
+    Weight EMA (``enable_ema``; off by default, and then every launch is what it is without it): one more flat fp32 buffer,
+    ``ema <- ema + rate (p - ema)`` with ``rate = ema_rate(decay, warmup, ema_updates)``, carried by the SAME kernels as the
+    update (the ``_ema`` twin of whichever entry point the step takes) from the fp32 masters as the update wrote them.  It is
+    not one of ``state_buffers()``: the average of a frozen parameter is the parameter, and stays that when the parameter
+    wakes (a woken parameter's moments restart from zero, its average does not).  The average belongs to the model's flat
+    buffer: if that buffer is re-created (the model moved to another device, a new layout), the average starts again from the
+    new masters and ``ema_updates`` from 0.  ``averaged()`` swaps the average into the model for evaluation or a checkpoint
+    and swaps the training weights back on exit."""
 
     _GROUP_KEYS = ("lr", "weight_decay")       # what a group may set for itself; everything else is shared
 
@@ -61,6 +81,10 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         self.step_count = 0                # steps taken by THIS object (Adam's bias correction; the telemetry cadence)
         self.sat_poll_every = int(os.environ.get("CE_SAT_POLL_EVERY", "16"))     # 0 = never
         self.sumsq = None
+        self.ema = None                    # the weight average (flat fp32, the layout of model._flat), or None: EMA off
+        self.ema_decay, self.ema_warmup, self.ema_updates = None, False, 0
+        self._ema_of = None                # the flat master buffer the average was started from
+        self._averaging = False            # inside averaged(): the average sits in model._flat, the masters in self.ema
         # group specs: (own hyper-parameters, names); names None = whatever no group lists, with the constructor's values
         by_id, known = {id(p): n for n, p in named}, {n for n, _ in named}
         if len(groups or ()) > MAX_GROUPS:
@@ -159,12 +183,117 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
                   "ce_sumsq_segments")
         state, args = self._group_args(sumsq)
         tj, tn_, tt = plan.tjobs
-        check(getattr(lib(), self._groups_op)(ptr(m._flat), ptr(m._flat_grad), *(ptr(b) for b in state), ptr(m._flat16), ptr(tj),
-                                              tn_, tt, ptr(plan.segments), plan.segments.shape[0],
-                                              ptr(plan.segment_group), ptr(sumsq), self.max_norm or 0.0, garr,
-                                              len(garr), *args, s), self._groups_op)
+        suffix, ema = self._ema_args()
+        check(getattr(lib(), self._groups_op + suffix)(ptr(m._flat), ptr(m._flat_grad), *(ptr(b) for b in state), ptr(m._flat16),
+                                                       ptr(tj), tn_, tt, ptr(plan.segments), plan.segments.shape[0],
+                                                       ptr(plan.segment_group), ptr(sumsq), self.max_norm or 0.0, garr,
+                                                       len(garr), *args, *ema, s), self._groups_op + suffix)
         # a frozen range was not touched: its mirror and W^T copy were current before the step and its master did not move
         m.mark_operands_stale(mirror_fresh=True, wt_fresh=tiles)
+
+    # ---- weight EMA ----
+    @property
+    def ema_enabled(self) -> bool:
+        return self.ema_decay is not None
+
+    def _refuse_while_averaged(self, what):
+        if self._averaging:
+            raise RuntimeError(f"{type(self).__name__}.{what} inside averaged(): the model holds the averaged weights; leave the "
+                               "context first")
+
+    def enable_ema(self, decay: float = 0.9999, warmup: bool = False):
+        """Start a weight average at the current weights: one flat fp32 buffer, a copy of the model's flat master buffer
+        (alignment padding included), updated by every ``step()`` from here on; ``ema_updates`` = 0.  ``warmup``: see
+        ``ema_rate``.  Enabling again starts again."""
+        self._refuse_while_averaged("enable_ema")
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"{type(self).__name__}.enable_ema: decay must lie in [0, 1) (got {decay})")
+        self.ema_decay, self.ema_warmup = decay, bool(warmup)
+        self.ema = self._ema_of = None
+        self._state()
+        self._ema_ready()
+
+    def disable_ema(self):
+        """Stop averaging and free the buffer."""
+        self._refuse_while_averaged("disable_ema")
+        self.ema = self._ema_of = None
+        self.ema_decay, self.ema_warmup, self.ema_updates = None, False, 0
+
+    def _ema_ready(self):
+        """(Re-)start the average from the masters when there is none for the model's present flat buffer (after ``_state()``)."""
+        flat = self.model._flat
+        if self.ema_enabled and (self.ema is None or self._ema_of is not flat):
+            self.ema = flat.detach().clone()
+            self._ema_of = flat
+            self.ema_updates = 0
+
+    def _ema_args(self, lo=None, hi=None):
+        """``(suffix of the entry point, the two arguments in front of the stream)`` of this step."""
+        if not self.ema_enabled:
+            return "", ()
+        e = self.ema if lo is None else self.ema[lo:hi]
+        return "_ema", (ptr(e), ema_rate(self.ema_decay, self.ema_warmup, self.ema_updates))
+
+    def _swap_average(self):
+        m = self.model
+        m.wait_transposes()           # an asynchronous W^T rebuild may still be reading the mirror the swap rewrites
+        check(lib().ce_swap_cast_bf16(ptr(m._flat), ptr(self.ema), ptr(m._flat16), m._flat.numel(), stream()), "ce_swap_cast_bf16")
+        # the mirror is that of the new content; the W^T copies (and the fp8 operands) are rebuilt from it by the next _ready()
+        m.mark_operands_stale(mirror_fresh=True, wt_fresh=False)
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Inside, the model holds the averaged weights (``encode_*``, ``inference.*``, ``model.state_dict()``, a checkpoint
+        written here) and this object holds the training weights: one pass exchanges the two flat buffers and writes the bf16
+        mirror.  On exit -- also when the body raises -- the same pass puts everything back, bit for bit.  ``step()``,
+        ``enable_ema`` and ``disable_ema`` raise inside; not re-entrant."""
+        if not self.ema_enabled:
+            raise RuntimeError(f"{type(self).__name__}.averaged: enable_ema() first")
+        self._refuse_while_averaged("averaged")
+        self._state()
+        self._ema_ready()
+        self._swap_average()
+        self._averaging = True
+        try:
+            yield self.model
+        finally:
+            self._averaging = False
+            self._swap_average()
+
+    def _named_offsets(self):
+        m = self.model
+        return [(n, p, m._offsets[n]) for n, p in m.named_parameters()]
+
+    def ema_state_dict(self):
+        """``{"decay", "warmup", "updates", "shadow": {parameter name: the average, in the parameter's shape}}`` (copies; every
+        parameter, frozen ones too)."""
+        if not self.ema_enabled:
+            raise RuntimeError(f"{type(self).__name__}.ema_state_dict: EMA is off")
+        if not self._averaging:
+            self._state()
+            self._ema_ready()
+        src = self.model._flat if self._averaging else self.ema
+        shadow = {n: src[o:o + p.numel()].view(p.shape).clone() for n, p, o in self._named_offsets()}
+        return {"decay": self.ema_decay, "warmup": self.ema_warmup, "updates": self.ema_updates, "shadow": shadow}
+
+    def load_ema_state_dict(self, sd):
+        """Take the average, its decay / warm-up and its update count from ``ema_state_dict()``'s format (enables EMA if it is
+        off); names and shapes must be the model's."""
+        self._refuse_while_averaged("load_ema_state_dict")
+        shadow = sd["shadow"]
+        named = {n: p for n, p in self.model.named_parameters()}
+        missing, extra = sorted(set(named) - set(shadow)), sorted(set(shadow) - set(named))
+        if missing or extra:
+            raise ValueError(f"EMA state does not match the model: missing {missing[:3]}, unexpected {extra[:3]}")
+        for n, p in named.items():
+            if tuple(shadow[n].shape) != tuple(p.shape):
+                raise ValueError(f"EMA state does not match the model: {n} is {tuple(shadow[n].shape)}, expected {tuple(p.shape)}")
+        self.enable_ema(sd["decay"], sd.get("warmup", False))
+        with torch.no_grad():
+            for n, p, o in self._named_offsets():
+                self.ema[o:o + p.numel()].view(p.shape).copy_(shadow[n])
+        self.ema_updates = int(sd.get("updates", 0))
 
     # kept as attributes of the first (only) group so that schedulers and user code see one source of truth
     @property
@@ -197,7 +326,9 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         frozen parameters, several groups or decoupled decay: the same over the tables of ``model.trainable_plan`` (``_grouped_step``)."""
         if closure is not None:
             raise RuntimeError(f"{type(self).__name__}.step takes no closure")
+        self._refuse_while_averaged("step")
         self._state()
+        self._ema_ready()
         m = self.model
         self._follow_flags()            # a parameter frozen or unfrozen since the last step
         m._settle_first_touch()         # a tower that saw no backward since zero_grad_first_touch
@@ -208,10 +339,14 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         from . import distributed as D
         plan = getattr(getattr(m, "grad_sync", None), "plan", None)
         sharded = plan is not None and D.active()
+        if sharded and self.ema_enabled:
+            raise NotImplementedError(f"{type(self).__name__}: the sharded optimiser step (CE_SHARDED_ADAM) does not carry the weight "
+                                      "EMA; use the replicated step (every rank then computes the same average)")
         sumsq = self.sumsq if self.max_norm is not None else None
         if not self._plain():
             self._grouped_step(sumsq, s)
             self._after_step(False)
+            self.ema_updates += int(self.ema_enabled)
             if self.sat_poll_every and self.step_count % self.sat_poll_every == 0 and hasattr(m, "poll_stream16_saturation"):
                 m.poll_stream16_saturation()
             return
@@ -221,9 +356,10 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
             check(lib().ce_sumsq(ptr(m._flat_grad[lo:hi]), hi - lo, ptr(self.sumsq), s), "ce_sumsq")
 
         def update(lo, hi):
-            check(getattr(lib(), self._flat_op)(ptr(m._flat[lo:hi]), ptr(m._flat_grad[lo:hi]),
-                                                *(ptr(b if b is None else b[lo:hi]) for b in state),      # (None: SGD without momentum)
-                                                ptr(m._flat16[lo:hi]), hi - lo, *args, s), self._flat_op)
+            suffix, ema = self._ema_args(lo, hi)
+            check(getattr(lib(), self._flat_op + suffix)(ptr(m._flat[lo:hi]), ptr(m._flat_grad[lo:hi]),
+                                                         *(ptr(b if b is None else b[lo:hi]) for b in state),      # (None: SGD without momentum)
+                                                         ptr(m._flat16[lo:hi]), hi - lo, *args, *ema, s), self._flat_op + suffix)
 
         if sharded:
             # sharded step (distributed.ShardPlan; DESIGN 5 lever 2): the gradient pieces arrived reduce-SCATTERED, this rank updates
@@ -240,13 +376,16 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
                 # next step); everything else by the chunk table of the first-touch zero-fill (= the complement of the block weights)
                 tj, tn_, tt = m._tjobs_bwd
                 seg = m._adam_segment_table()
-                check(getattr(lib(), self._tiles_op)(ptr(m._flat), ptr(m._flat_grad), *(ptr(b) for b in state), ptr(m._flat16), ptr(tj),
-                                                     tn_, tt, ptr(seg), seg.shape[0], *args, s), self._tiles_op)
+                suffix, ema = self._ema_args()
+                check(getattr(lib(), self._tiles_op + suffix)(ptr(m._flat), ptr(m._flat_grad), *(ptr(b) for b in state), ptr(m._flat16),
+                                                              ptr(tj), tn_, tt, ptr(seg), seg.shape[0], *args, *ema, s),
+                      self._tiles_op + suffix)
                 m.mark_operands_stale(mirror_fresh=True, wt_fresh=True)
             else:
                 update(0, n)
                 m.mark_operands_stale(mirror_fresh=True)
         self._after_step(sharded)
+        self.ema_updates += int(self.ema_enabled)
         # fp16 streams: look at the clamp counters every few steps, without a synchronisation (the copy started by one poll is
         # examined by the next); raises model.Stream16Saturation.  On every exit of step(), the sharded one included.
         if self.sat_poll_every and self.step_count % self.sat_poll_every == 0 and hasattr(m, "poll_stream16_saturation"):

@@ -383,6 +383,37 @@ int ce_sgd_step_groups(float* p, const float* g, float* buf, void* p_bf16, const
                        int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
                        float max_norm, const ce_optim_group* groups, int ngroups, float momentum, float dampening, int nesterov,
                        int first_step, void* stream);
+/* ---- weight EMA: every step entry point above with an exponential moving average of the weights carried along ----
+ * `ema` (fp32, the flat layout of p) is one more stream of the same traversal: ema += ema_rate * (p_new - ema), ema_rate = 1 - decay,
+ * in torch's lerp_ form (fma(p_new - ema, ema_rate, ema) below 0.5, p_new - (p_new - ema) (1 - ema_rate) from 0.5 on: ema_rate 1
+ * copies), from the fp32 master exactly as the update wrote it.  p, the state, the bf16 mirror and the W^T copies get the bits of the
+ * entry point without _ema; all forms give the same bits in ema.  In the grouped forms, what is in no table is neither read nor
+ * written in ema.  -EINVAL for ema == NULL, ema_rate outside (0, 1], and whatever the parent refuses. */
+int ce_adam_step_ema(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* sumsq, float max_norm,
+                     float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* ema, float ema_rate,
+                     void* stream);
+int ce_adam_step_tiles_ema(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                           int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
+                           float beta1, float beta2, float eps, float weight_decay, int step, float* ema, float ema_rate,
+                           void* stream);
+int ce_adam_step_groups_ema(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                            int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
+                            float max_norm, const ce_optim_group* groups, int ngroups, float beta1, float beta2, float eps, int step,
+                            float* ema, float ema_rate, void* stream);
+int ce_sgd_step_ema(float* p, const float* g, float* buf, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+                    float momentum, float dampening, float weight_decay, int nesterov, int first_step, float* ema, float ema_rate,
+                    void* stream);
+int ce_sgd_step_tiles_ema(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                          int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
+                          float momentum, float dampening, float weight_decay, int nesterov, int first_step, float* ema,
+                          float ema_rate, void* stream);
+int ce_sgd_step_groups_ema(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                           int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
+                           float max_norm, const ce_optim_group* groups, int ngroups, float momentum, float dampening, int nesterov,
+                           int first_step, float* ema, float ema_rate, void* stream);
+/* a[i] <-> b[i] for i < n, and a_bf16[i] = bf16(new a[i]) (ce_cast_bf16's rounding): the masters and their average change places
+ * and the bf16 mirror follows, in one pass.  a, b 16-byte aligned, a_bf16 8-byte aligned, a != b.  Calling it twice restores both. */
+int ce_swap_cast_bf16(float* a, float* b, void* a_bf16, long n, void* stream);
 
 /* ---- transformer tower runner (tower.cpp): the 12x ResidualAttentionBlock loop of
  * Transformer.forward (model_clip.py:171-211) and its backward, all launches issued from C++ ---- */

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the HBM-bound kernels at the step's shapes with COLD operands: every call works on the next of
 NSETS buffer sets (together larger than the 256 MiB Infinity Cache), as in the step, where a kernel's inputs were written
-tens of kernels earlier.  Prints us per call and GB/s on the algorithmic bytes.   python tools/bench_hbm.py [ln adam sgd attn]"""
+tens of kernels earlier.  Prints us per call and GB/s on the algorithmic bytes.   python tools/bench_hbm.py [ln adam sgd attn]
+adam_ema / sgd_ema: the tiled update with the weight average fused in, beside the same update without it and beside "update, then
+``ema.lerp_(masters, rate)``" -- what the fusion replaces -- in alternation in one process."""
 import os
 import sys
 from ctypes import c_float, c_int, c_long
@@ -152,6 +154,43 @@ def bench_sgd():
               flush=True)
 
 
+def bench_ema(kinds, rounds=3):
+    """The step's tiled update over the ViT-B/32 layout (same parameter count as ``adam`` / ``sgd``) in three forms, measured in
+    alternation (same box, same minute), ``rounds`` times: without the average (Adam 32 B, SGD 24 B per parameter); with the
+    average in the same kernels (+ 8 B: read and write it); and the reference point, the update without it followed by one
+    ``ema.lerp_(masters, rate)`` over the flat buffers (+ 12 B: read both, write one, and one more launch)."""
+    t = _tiled_model()
+    m, seg, (tj, tn_, tt) = t["m"], t["seg"], t["m"]._tjobs_bwd
+    n = sum(q.numel() for q in m.parameters())
+    ema = m._flat.detach().clone()
+    rate = 1e-4
+    tables = (ptr(m._flat16), ptr(tj), c_int(tn_), c_int(tt), ptr(seg), c_int(seg.shape[0]), ptr(t["ss"]), c_float(1.0), c_float(1e-6))
+    tails = {"adam": (c_float(0.9), c_float(0.999), c_float(1e-8), c_float(0.0), c_int(3)),
+             "sgd": (c_float(0.9), c_float(0.0), c_float(0.0), c_int(0), c_int(0))}
+    state = {"adam": (ptr(t["a"]), ptr(t["b"])), "sgd": (ptr(t["a"]),)}
+    base_bytes = {"adam": 32, "sgd": 24}
+
+    def step(kind, fused):
+        name = f"ce_{kind}_step_tiles" + ("_ema" if fused else "")
+        extra = (ptr(ema), c_float(rate)) if fused else ()
+        check(getattr(lib(), name)(ptr(m._flat), ptr(m._flat_grad), *state[kind], *tables, *tails[kind], *extra, stream()), name)
+
+    def then_lerp(kind):
+        step(kind, False)
+        ema.lerp_(m._flat, rate)
+
+    for r in range(rounds):
+        for kind in kinds:
+            b = base_bytes[kind]
+            plain = timeit([lambda: step(kind, False)], iters=10, warm=2)
+            fused = timeit([lambda: step(kind, True)], iters=10, warm=2)
+            ref = timeit([lambda: then_lerp(kind)], iters=10, warm=2)
+            print(f"{kind}_ema round {r} n={n}: tiles {plain * 1e6:7.1f} us {n * b / plain / 1e12:5.2f} TB/s | tiles + fused average "
+                  f"{fused * 1e6:7.1f} us {n * (b + 8) / fused / 1e12:5.2f} TB/s (+{(fused - plain) * 1e6:6.1f} us) | tiles, then lerp_ "
+                  f"{ref * 1e6:7.1f} us {n * (b + 12) / ref / 1e12:5.2f} TB/s (+{(ref - plain) * 1e6:6.1f} us) | fused / reference "
+                  f"{fused / ref:.3f}", flush=True)
+
+
 def bench_attn():
     for name, B, Ltok, H, causal in (("image", 256, 50, 12, False), ("text", 256, 77, 8, True)):
         sets = []
@@ -177,5 +216,7 @@ if __name__ == "__main__":
         bench_adam()
     if "sgd" in which:
         bench_sgd()
+    if "adam_ema" in which or "sgd_ema" in which:
+        bench_ema([k for k in ("adam", "sgd") if k + "_ema" in which])
     if "attn" in which:
         bench_attn()

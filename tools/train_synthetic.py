@@ -12,7 +12,11 @@ Partial fine-tuning: ``--lock-image-tower`` / ``--lock-text-tower`` freeze a tow
 and its output side), ``--no-decay-groups`` puts gains, biases and ``logit_scale`` into a parameter group without weight decay,
 ``--adamw`` decouples the decay (both with ``--optimizer adam`` and a weight decay of 0.1; the fused step stays in use).
 
-``--patch-dropout P`` trains the image tower on a random ``1 - P`` of the patches of every image (CLIP.set_patch_dropout)."""
+``--patch-dropout P`` trains the image tower on a random ``1 - P`` of the patches of every image (CLIP.set_patch_dropout).
+
+``--ema DECAY`` keeps an exponential moving average of the weights in the fused step (``optimizer.enable_ema``; ``--ema-warmup``:
+the ramped decay of ``optim.ema_rate``); the checkpoint carries it, the resumed run restores it, and the end prints
+``inference.retrieval_metrics`` on the fixed batch for the raw and for the averaged weights (``optimizer.averaged()``)."""
 import argparse
 import os
 import sys
@@ -22,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from clip_event_amd import checkpoint, clip, distributed as D, synthetic as S
+from clip_event_amd import checkpoint, clip, distributed as D, inference, synthetic as S
 from clip_event_amd.engine import train_step
 from clip_event_amd.losses import CriterionContrastive
 from clip_event_amd.optim import FusedAdam, FusedSGD, build_lr_scheduler, build_optimizer, no_decay_groups
@@ -53,7 +57,11 @@ def main():
     ap.add_argument("--adamw", action="store_true", help="decoupled weight decay (FusedAdam(decoupled=True))")
     ap.add_argument("--patch-dropout", type=float, default=0.0, metavar="P",
                     help="train the image tower on a random 1 - P of the patches (CLIP.set_patch_dropout)")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="weight EMA in the fused step (optimizer.enable_ema)")
+    ap.add_argument("--ema-warmup", action="store_true", help="with --ema: ramp the decay up (optim.ema_rate)")
     args = ap.parse_args()
+    if args.ema_warmup and args.ema is None:
+        ap.error("--ema-warmup goes with --ema")
     if args.adamw and args.optimizer != "adam":
         ap.error("--adamw goes with --optimizer adam")
     mb = args.micro_batch
@@ -86,6 +94,8 @@ def main():
     lock(model)
     model.set_patch_dropout(args.patch_dropout, seed=0)
     optimizer = make_optimizer(model)
+    if args.ema is not None:
+        optimizer.enable_ema(args.ema, warmup=args.ema_warmup)
     scheduler = build_lr_scheduler(cfg, optimizer, 0)                           # engine.py:154-176
     data = batch(rng, B, K, dev)                                                # one fixed batch: the loss must fall
     losses = []
@@ -106,6 +116,11 @@ def main():
         model2.patch_draw = model.patch_draw
         optimizer2 = make_optimizer(model2)
         optimizer2.load_state_dict(opt_state)
+        ema = checkpoint.load_ema(path)
+        assert (ema is not None) == (args.ema is not None)
+        if ema is not None:
+            optimizer2.load_ema_state_dict(ema)                                               # decay, warm-up, update count, average
+            assert optimizer2.ema_updates == optimizer.ema_updates == 20
         scheduler2 = build_lr_scheduler(cfg, optimizer2, begin_epoch)
     assert begin_epoch == 20 and abs(optimizer2.param_groups[0]["lr"] - optimizer.param_groups[0]["lr"]) < 1e-12
     a = train_step(model, criterion, optimizer, *data, micro_batch=mb)
@@ -132,6 +147,20 @@ def main():
     dt = (time.perf_counter() - t0) / 96
     assert all(torch.isfinite(v) for v in ld.values()) and model2.stream16_saturation() == (0, 0)
     print(f"96 steps at B = 32, K = {K}: {dt * 1e3:.2f} ms/step, clamp counters {model2.stream16_saturation()}")
+    if args.ema is not None:
+        image, text, _, _, ip = data
+
+        def retrieval():                                                        # the fixed batch: every image against its own caption
+            with torch.no_grad():
+                fi, ft = model2.encode_image(image), model2.encode_text(text.to(dev)[ip])
+            return inference.retrieval_metrics(fi, ft)
+
+        raw = retrieval()
+        with optimizer2.averaged():
+            avg = retrieval()
+        for name, r in (("raw", raw), ("averaged", avg)):
+            print(f"retrieval on the fixed batch, {name:8s} weights:", " ".join(f"{k} {v:.3f}" for k, v in r.items()))
+        assert optimizer2.ema_updates == 20 + 2 + 4 + 96 and retrieval() == raw
     print("train_synthetic OK")
 
 
