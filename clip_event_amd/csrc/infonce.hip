@@ -20,6 +20,17 @@
 //     lane movement: cdna_hip_programming.md "An accumulator tile as the next MFMA's operand"); each wave owns a quarter of
 //     E; the result leaves through an LDS transpose as whole rows (plain stores when the streamed range is not split,
 //     float atomics otherwise).
+//
+// Two loss policies share the skeleton (template parameter LOSS).  LOSS_SOFTMAX is the above.  LOSS_SIGMOID is the pairwise
+// sigmoid loss of SigLIP over queries x keys, one direction:
+//   x[r,c] = s <q_r, k_c> + b,  z[r,c] = +1 if c == y_r else -1,  loss = -(1/nq) sum_r sum_c log sigma(z x)
+//   G[r,c] = -(g/nq) z sigma(-z x);  dq, dk as above;  db = sum G;  dlogit_scale = sum G (x - b)
+// Every pair is an independent term: no row statistic, no merge by maximum, nothing saved for the backward.  Three sites differ:
+//   * FWD sums stable softplus terms, each wave taking 16 / NW of the tile's accumulator rows (the softmax FWD lets every wave
+//     reduce the whole tile); one partial per workgroup goes to a workspace and a one-workgroup kernel adds the partials in a
+//     fixed order and applies 1/nq: the loss is bit-identical from run to run (no float atomics on it).
+//   * G in DQ / DK; qinfo carries the label only.
+//   * zero-padded tile positions are NOT neutral (softplus(0) = log 2): every term is masked by row and column validity.
 #include <stdlib.h>
 
 #include <mutex>
@@ -31,6 +42,7 @@ namespace {
 
 constexpr int HB = 32;          // rows per resident / streamed block
 enum { MODE_FWD = 0, MODE_DQ = 1, MODE_DK = 2 };
+enum { LOSS_SOFTMAX = 0, LOSS_SIGMOID = 1 };
 
 struct HeadArgs {
     const float* res; long ldres; int nres;       // resident matrix (queries for FWD / DQ, keys for DK)
@@ -44,19 +56,39 @@ struct HeadArgs {
     float* dres;                                  // DQ / DK: gradient of the resident matrix [rows, E] (+=)
     float* dls;                                   // DQ: logit_scale gradient (+=)
     int E, nq, splits, blocks_per_split;
+    // LOSS_SIGMOID only
+    const float* logit_bias;
+    float* dbias;                                 // DQ: logit_bias gradient (+=)
+    float* loss_part;                             // FWD: [splits][row blocks] loss partial of each workgroup
 };
 
 __device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // 32x32 C/D row of reg r
 
+// log(1 + e) for 0 <= e <= 1, accurate where e is tiny (with the usual bias near -10 a negative pair's term is ~ 4.5e-5 and
+// log(1.f + e) alone keeps four of its digits): u = fl(1 + e) carries the rounding of the sum, and log(u) * e / (u - 1) takes it
+// out again (the classic log1p correction); u == 1 leaves e itself.  One v_log_f32, one v_rcp_f32.
+__device__ __forceinline__ float log1p_unit(float e) {
+    const float u = 1.f + e, d = u - 1.f;
+    return d == 0.f ? e : __logf(u) * (e * __frcp_rn(d));
+}
+// -log sigma(y) = softplus(-y) = max(-y, 0) + log1p(exp(-|y|)): exp never sees a positive argument
+__device__ __forceinline__ float neg_log_sigmoid(float y) { return fmaxf(-y, 0.f) + log1p_unit(__expf(-fabsf(y))); }
+// sigma(-y) = e / (1 + e) for y >= 0, 1 / (1 + e) for y < 0, e = exp(-|y|)
+__device__ __forceinline__ float sigmoid_neg(float y) {
+    const float e = __expf(-fabsf(y));
+    return (y >= 0.f ? e : 1.f) * __frcp_rn(1.f + e);
+}
+
 // NW waves per workgroup: 4 (E a multiple of 128) or 8 (E a multiple of 256: two waves per SIMD cover the global operand
 // loads that feed the MFMAs; each wave then owns an eighth of E)
-template <int MODE, int NW>
+template <int MODE, int NW, int LOSS = LOSS_SOFTMAX>
 __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int E = a.E, pitch = E + 4;
     float* res_l = reinterpret_cast<float*>(smem);                       // [32][E+4]
     float* part_l = res_l + HB * pitch;                                  // [NW][32][33]: partial tiles / output transpose
     float* qinfo = part_l + NW * HB * 33;                                 // [2][32]: lse, label (as float bits) of the streamed queries (DK)
+                                                                          //          (sigmoid: label only; FWD: the waves' loss sums)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int r0 = blockIdx.x * HB;
@@ -79,13 +111,15 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
     if (MODE != MODE_DK && jvalid) {
         jsrc = a.sel ? a.sel[r0 + j] : (long)(r0 + j);
         jlabel = a.labels[jsrc];
-        if (MODE == MODE_DQ) jlse = a.lse[r0 + j];
+        if (MODE == MODE_DQ && LOSS == LOSS_SOFTMAX) jlse = a.lse[r0 + j];
     }
+    const float bias = (LOSS == LOSS_SIGMOID) ? *a.logit_bias : 0.f;
     const float coef = (MODE == MODE_FWD) ? 0.f : (*a.grad / (float)a.nq);
     __syncthreads();
 
     float run_m = -INFINITY, run_l = 0.f;                 // FWD: online statistics of query j over this split
     float dls_acc = 0.f;
+    float loss_acc = 0.f, dbias_acc = 0.f;                // sigmoid: FWD loss terms / DQ bias gradient of this lane
     constexpr int GT = 32 / NW;                           // gradient accumulators: up to 1024 / NW / 32 e-tiles of 32 per wave
     f32x16 gacc[MODE == MODE_FWD ? 1 : GT];
     const int etiles = E / (32 * NW);                     // e-tiles of 32 columns per wave (E/NW columns per wave)
@@ -126,10 +160,25 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
         if (MODE == MODE_DK && tid < HB) {                // lse / label of the 32 streamed queries
             const bool v = c0 + tid < a.nstr;
             const long src = v ? (a.sel ? a.sel[c0 + tid] : (long)(c0 + tid)) : 0;
-            qinfo[tid] = v ? a.lse[c0 + tid] : 0.f;
+            if (LOSS == LOSS_SOFTMAX) qinfo[tid] = v ? a.lse[c0 + tid] : 0.f;
             qinfo[HB + tid] = v ? (float)a.labels[src] : -1.f;          // key indices < 2^24: exact in fp32
         }
         __syncthreads();
+        if (MODE == MODE_FWD && LOSS == LOSS_SIGMOID) {
+            // pairs are independent: wave w takes the accumulator rows r = w * 16 / NW ... of every lane's column
+            constexpr int RPW = 16 / NW;
+#pragma unroll
+            for (int rr = 0; rr < RPW; ++rr) {
+                const int i = row_of(wave * RPW + rr, h);
+                float t = 0.f;
+#pragma unroll
+                for (int w = 0; w < NW; ++w) t += part_l[(w * HB + i) * 33 + j];
+                const float x = scale * t + bias;
+                // a zero-padded row or column would add softplus(0) = log 2
+                if (jvalid && c0 + i < a.nstr) loss_acc += neg_log_sigmoid((long)(c0 + i) == jlabel ? x : -x);
+            }
+            continue;
+        }
         float S[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -159,7 +208,14 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
             for (int r = 0; r < 16; ++r) {
                 const int i = row_of(r, h);
                 float g = 0.f;
-                if (MODE == MODE_DQ) {
+                if (LOSS == LOSS_SIGMOID) {
+                    if (jvalid && c0 + i < a.nstr) {
+                        const bool pos = (MODE == MODE_DQ) ? (long)(c0 + i) == jlabel : (float)(r0 + j) == qinfo[HB + i];
+                        const float x = S[r] + bias;
+                        g = (pos ? -coef : coef) * sigmoid_neg(pos ? x : -x);
+                    }
+                    if (MODE == MODE_DQ) dbias_acc += g;
+                } else if (MODE == MODE_DQ) {
                     if (jvalid && c0 + i < a.nstr) g = coef * (__expf(S[r] - jlse) - ((long)(c0 + i) == jlabel ? 1.f : 0.f));
                 } else {
                     if (jvalid && c0 + i < a.nstr)
@@ -188,6 +244,19 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
         }
     }
 
+    if (MODE == MODE_FWD && LOSS == LOSS_SIGMOID) {
+        loss_acc = wave_sum(loss_acc);
+        __syncthreads();                                  // the last tile's readers of part_l are done (qinfo sits behind it)
+        if (lane == 0) qinfo[wave] = loss_acc;
+        __syncthreads();
+        if (tid == 0) {
+            float t = 0.f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) t += qinfo[w];
+            a.loss_part[(long)blockIdx.y * gridDim.x + blockIdx.x] = t;
+        }
+        return;
+    }
     if (MODE == MODE_FWD) {
         if (wave == 0 && h == 0 && jvalid) {
             float* o = a.part + ((long)blockIdx.y * a.nq + r0 + j) * 2;
@@ -200,6 +269,10 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
     if (MODE == MODE_DQ) {
         dls_acc = wave_sum(dls_acc);
         if (lane == 0 && wave == 0) atomicAdd(a.dls, dls_acc);        // every wave holds the same tile sums: count once
+        if (LOSS == LOSS_SIGMOID) {
+            dbias_acc = wave_sum(dbias_acc);
+            if (lane == 0 && wave == 0) atomicAdd(a.dbias, dbias_acc);
+        }
     }
     __syncthreads();
     float* tile = part_l + wave * HB * 33;                            // [j][e'] for this wave
@@ -247,22 +320,36 @@ __global__ __launch_bounds__(256) void infonce_merge_kernel(HeadArgs a, float* _
     }
 }
 
+// sum the workgroups' loss partials in index order and apply 1/nq: one workgroup, a fixed tree, no atomics
+__global__ __launch_bounds__(256) void sigmoid_loss_sum_kernel(const float* __restrict__ part, int n, int nq, float* __restrict__ loss) {
+    __shared__ float red[256];
+    float t = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) t += part[i];
+    red[threadIdx.x] = t;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss = red[0] / (float)nq;
+}
+
 size_t head_lds_bytes(int E, int nw) { return (size_t)(HB * (E + 4) + nw * HB * 33 + 2 * HB) * 4; }
 
-template <int MODE>
+template <int MODE, int LOSS = LOSS_SOFTMAX>
 int launch_head(HeadArgs& a, hipStream_t s) {
     static std::once_flag flag;
     std::call_once(flag, [] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(infonce_kernel<MODE, 4>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipFuncSetAttribute(reinterpret_cast<const void*>(infonce_kernel<MODE, 4, LOSS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)head_lds_bytes(1024, 4));
-        hipFuncSetAttribute(reinterpret_cast<const void*>(infonce_kernel<MODE, 8>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipFuncSetAttribute(reinterpret_cast<const void*>(infonce_kernel<MODE, 8, LOSS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)head_lds_bytes(768, 8));      // E = 1024 with eight partial tiles exceeds 160 KiB
     });
     const int rb = ce_div_up(a.nres, HB);
     static const int force_nw = getenv("CE_HEAD_WAVES") ? atoi(getenv("CE_HEAD_WAVES")) : 0;
     const bool eight = a.E % 256 == 0 && a.E <= 768 && force_nw != 4;
-    if (eight) hipLaunchKernelGGL((infonce_kernel<MODE, 8>), dim3(rb, a.splits), dim3(512), head_lds_bytes(a.E, 8), s, a);
-    else hipLaunchKernelGGL((infonce_kernel<MODE, 4>), dim3(rb, a.splits), dim3(256), head_lds_bytes(a.E, 4), s, a);
+    if (eight) hipLaunchKernelGGL((infonce_kernel<MODE, 8, LOSS>), dim3(rb, a.splits), dim3(512), head_lds_bytes(a.E, 8), s, a);
+    else hipLaunchKernelGGL((infonce_kernel<MODE, 4, LOSS>), dim3(rb, a.splits), dim3(256), head_lds_bytes(a.E, 4), s, a);
     return 0;
 }
 
@@ -331,6 +418,60 @@ extern "C" int ce_infonce_bwd(const float* q, long ldq, const int64_t* sel, int 
     a.blocks_per_split = ce_div_up(ce_div_up(nq, HB), a.splits);
     a.splits = ce_div_up(ce_div_up(nq, HB), a.blocks_per_split);
     launch_head<MODE_DK>(a, s);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- sigmoid pairwise loss (SigLIP) on the same sweep ----------------------------------------------------------------
+
+extern "C" size_t ce_sigmoid_head_workspace_bytes(int nq, int nk) {
+    if (nq <= 0 || nk <= 0) return 0;
+    return (size_t)ce_div_up(nq, HB) * pick_splits(nq, nk, CE_INFONCE_MAX_SPLITS) * sizeof(float);
+}
+
+extern "C" int ce_sigmoid_head_fwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                                   const float* logit_scale, const float* logit_bias, const int64_t* labels, float* loss,
+                                   void* workspace, void* stream) {
+    if (int rc = check_common("ce_sigmoid_head_fwd", q, ldq, nq, k, ldk, nk, E, logit_scale, labels)) return rc;
+    CE_CHECK_ARG(logit_bias && loss && workspace, "ce_sigmoid_head_fwd: null buffer");
+    HeadArgs a{};
+    a.res = q; a.ldres = ldq; a.nres = nq; a.str = k; a.ldstr = ldk; a.nstr = nk;
+    a.sel = (const long*)sel; a.labels = (const long*)labels; a.logit_scale = logit_scale; a.logit_bias = logit_bias;
+    a.loss_part = (float*)workspace; a.E = E; a.nq = nq;
+    a.splits = pick_splits(nq, nk, CE_INFONCE_MAX_SPLITS);
+    a.blocks_per_split = ce_div_up(ce_div_up(nk, HB), a.splits);
+    a.splits = ce_div_up(ce_div_up(nk, HB), a.blocks_per_split);          // never more than the workspace was sized for
+    hipStream_t s = (hipStream_t)stream;
+    launch_head<MODE_FWD, LOSS_SIGMOID>(a, s);
+    CE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sigmoid_loss_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)workspace, ce_div_up(nq, HB) * a.splits, nq,
+                       loss);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_sigmoid_head_bwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                                   const float* logit_scale, const float* logit_bias, const int64_t* labels, const float* grad,
+                                   float* dq, float* dk, float* dlogit_scale, float* dlogit_bias, void* stream) {
+    if (int rc = check_common("ce_sigmoid_head_bwd", q, ldq, nq, k, ldk, nk, E, logit_scale, labels)) return rc;
+    CE_CHECK_ARG(logit_bias && grad && dq && dk && dlogit_scale && dlogit_bias, "ce_sigmoid_head_bwd: null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    HeadArgs a{};
+    a.sel = (const long*)sel; a.labels = (const long*)labels; a.logit_scale = logit_scale; a.logit_bias = logit_bias; a.grad = grad;
+    a.E = E; a.nq = nq; a.dls = dlogit_scale; a.dbias = dlogit_bias;
+    // dq: resident = queries, streamed = keys (also the scale and bias gradients)
+    a.res = q; a.ldres = ldq; a.nres = nq; a.str = k; a.ldstr = ldk; a.nstr = nk; a.dres = dq;
+    a.splits = pick_splits(nq, nk, 1 << 20);
+    a.blocks_per_split = ce_div_up(ce_div_up(nk, HB), a.splits);
+    a.splits = ce_div_up(ce_div_up(nk, HB), a.blocks_per_split);
+    launch_head<MODE_DQ, LOSS_SIGMOID>(a, s);
+    CE_LAUNCH_CHECK();
+    // dk: resident = keys, streamed = queries
+    a.res = k; a.ldres = ldk; a.nres = nk; a.str = q; a.ldstr = ldq; a.nstr = nq; a.dres = dk;
+    a.splits = pick_splits(nk, nq, 1 << 20);
+    a.blocks_per_split = ce_div_up(ce_div_up(nq, HB), a.splits);
+    a.splits = ce_div_up(ce_div_up(nq, HB), a.blocks_per_split);
+    launch_head<MODE_DK, LOSS_SIGMOID>(a, s);
     CE_LAUNCH_CHECK();
     return 0;
 }

@@ -17,8 +17,8 @@ import numpy as np
 import torch
 
 from . import distributed as D
-from .functional import (attach_lengths, fused_contrastive_losses, fused_head_ok, logits_from_features, small_contrastive_losses,
-                         small_head_ok, tokens_to_device)
+from .functional import (attach_lengths, fused_contrastive_losses, fused_head_ok, logits_from_features, sigmoid_contrastive_losses,
+                         small_contrastive_losses, small_head_ok, tokens_to_device)
 from .losses import CriterionAlignment, CriterionContrastive
 
 
@@ -36,6 +36,8 @@ def _contrastive_from_features(model, criterion, fi, ft, labels_per_image, label
     # 1280 and 512 x 512: fused ahead by 0.1-0.2 ms).  CE_FUSED_HEAD=1 / 0 forces either.
     force = os.environ.get("CE_FUSED_HEAD", "")
     dist_global = D.active() and global_batch
+    if getattr(criterion, "kind", None) == "sigmoid":
+        return _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_global)
     logits = int(fi.shape[0]) * int(ft.shape[0]) * (D.world_size() if dist_global else 1)
     fused = (force != "0" and (force == "1" or logits >= (1 << 17)) and getattr(criterion, "kind", None) == "ce"
              and model.constrastive_overbatch and fused_head_ok(model.embed_dim))
@@ -54,6 +56,25 @@ def _contrastive_from_features(model, criterion, fi, ft, labels_per_image, label
     else:
         lpi, lpt = logits_from_features(fi, ft, model.logit_scale, overbatch)
     return criterion(lpi, lpt, labels_per_image, labels_per_text, index_pos=index_pos, constrastive_overbatch=overbatch)
+
+
+def _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_global):
+    """``CriterionSigmoid``: the local images against all texts, one direction.  Across ranks only the TEXT features are gathered
+    (half of ``gather_feature_pair``'s bytes): the rank's loss is over its own rows, DDP's mean over the ranks makes it the global
+    loss, and the reduce-scatter in the gather's backward brings the other ranks' text gradients home.  The fused head (three
+    sweeps, no logits matrix) at every size the kernels take -- the three-launch small head is 'ce'-only -- else logits +
+    criterion.  CE_FUSED_HEAD=0 forces the latter."""
+    if not model.constrastive_overbatch:
+        raise RuntimeError("the sigmoid loss needs constrastive_overbatch=True: the per-instance layout has no negatives from other "
+                           "images")
+    bias = getattr(model, "logit_bias", None)
+    if bias is None:
+        raise RuntimeError("the sigmoid loss needs a logit bias: call model.enable_logit_bias() before building the optimiser")
+    ft_all = D.gather_features(ft) if dist_global else ft
+    if os.environ.get("CE_FUSED_HEAD", "") != "0" and fused_head_ok(model.embed_dim):
+        return sigmoid_contrastive_losses(fi, ft_all, model.logit_scale, bias, labels_per_image)
+    lpi, _ = logits_from_features(fi, ft_all, model.logit_scale, True, want="image")
+    return criterion(lpi, None, labels_per_image, constrastive_overbatch=True, logit_bias=bias)
 
 
 def contrastive_step_losses(model, criterion: CriterionContrastive, image, text, labels_per_image, labels_per_text,

@@ -763,3 +763,44 @@ def fused_contrastive_losses(fi, ft, fi_all, ft_all, logit_scale, labels_per_ima
         return {"loss_i": loss_i, "loss_t": loss_t}
     return {"loss_i": InfoNCEFn.apply(fi, ft_all, logit_scale, labels_per_image, None),
             "loss_t": InfoNCEFn.apply(ft, fi_all, logit_scale, labels_per_text, index_pos)}
+
+
+class SigmoidHeadFn(torch.autograd.Function):
+    """The sigmoid pairwise loss of SigLIP, -(1/nq) sum_r sum_c log sigma(z (s q^_r . k^_c + b)) with z = +1 where c is the label
+    of query r and -1 elsewhere, over the query rows ``sel`` of ``q`` against all rows of ``k`` -- without the [nq, nk] logits
+    matrix (``ce_sigmoid_head_fwd/bwd``: three sweeps, nothing saved but the normalised features).  Returns the scalar loss;
+    gradients for both raw feature matrices, ``logit_scale`` and ``logit_bias``."""
+
+    @staticmethod
+    def forward(ctx, q, k, logit_scale, logit_bias, labels, sel):
+        dev = q.device
+        q, k = _f32(q), _f32(k)
+        E = q.shape[1]
+        qn, inv_q = _l2norm(q)
+        kn, inv_k = _l2norm(k)
+        labels, sel = _index64(labels, dev), _index64(sel, dev)
+        nq = q.shape[0] if sel is None else sel.shape[0]
+        ls, lb = logit_scale.detach().reshape(1), logit_bias.detach().float().reshape(1)
+        loss = _empty((), torch.float32, dev)
+        ws = _empty((lib().ce_sigmoid_head_workspace_bytes(nq, k.shape[0]),), torch.uint8, dev)
+        check(lib().ce_sigmoid_head_fwd(ptr(qn), E, ptr(sel), nq, ptr(kn), E, k.shape[0], E, ptr(ls), ptr(lb), ptr(labels), ptr(loss),
+                                        ptr(ws), stream()), "ce_sigmoid_head_fwd")
+        ctx.saved = (qn, kn, inv_q, inv_k, ls, lb, labels, sel)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        qn, kn, inv_q, inv_k, ls, lb, labels, sel = ctx.saved
+        E = qn.shape[1]
+        nq = qn.shape[0] if sel is None else sel.shape[0]
+        g = g.contiguous().float().reshape(1)
+        acc = torch.zeros(qn.numel() + kn.numel() + 4, dtype=torch.float32, device=qn.device)     # dqn | dkn | dscale, dbias: one fill
+        dqn, dkn, ds = acc[:qn.numel()].view_as(qn), acc[qn.numel():qn.numel() + kn.numel()].view_as(kn), acc[qn.numel() + kn.numel():]
+        check(lib().ce_sigmoid_head_bwd(ptr(qn), E, ptr(sel), nq, ptr(kn), E, kn.shape[0], E, ptr(ls), ptr(lb), ptr(labels), ptr(g),
+                                        ptr(dqn), ptr(dkn), ptr(ds[0:1]), ptr(ds[1:2]), stream()), "ce_sigmoid_head_bwd")
+        return _l2norm_bwd(dqn, qn, inv_q), _l2norm_bwd(dkn, kn, inv_k), ds[0].reshape(()), ds[1].reshape(()), None, None
+
+
+def sigmoid_contrastive_losses(fi, ft_all, logit_scale, logit_bias, labels_per_image):
+    """``CriterionSigmoid`` over the batch on raw features: the local images against all (gathered) texts, one direction."""
+    return {"loss_sig": SigmoidHeadFn.apply(fi, ft_all, logit_scale, logit_bias, labels_per_image, None)}

@@ -97,6 +97,32 @@ class CriterionContrastive(nn.Module):
         return {"loss_i": loss_i, "loss_t": loss_t}
 
 
+class CriterionSigmoid(nn.Module):
+    """The sigmoid pairwise loss of SigLIP (open_clip's ``SigLipLoss``) on a materialised ``logits_per_image`` [nq, nk]: every
+    (image, text) pair is its own binary term, positive where the column is the image's label,
+    loss = -(1/nq) sum_r sum_c log sigma(z (logits + logit_bias)).  One direction: ``logits_per_text`` and its labels are
+    accepted for the common call and not used.  This is the general path, for embed dims the fused head
+    (``functional.SigmoidHeadFn``) does not take; ``engine`` picks between them."""
+
+    kind = "sigmoid"
+
+    def forward(self, logits_per_image, logits_per_text, labels_per_image=None, labels_per_text=None,
+                index_pos=None, constrastive_overbatch=True, logit_bias=None):
+        if not constrastive_overbatch:
+            raise RuntimeError("CriterionSigmoid needs constrastive_overbatch=True: the per-instance layout scores an image against "
+                               "its own descriptions only, so it has no negatives from other images")
+        if logit_bias is None:
+            raise RuntimeError("CriterionSigmoid needs logit_bias (model.enable_logit_bias())")
+        nq, nk = logits_per_image.shape
+        dev = logits_per_image.device
+        if labels_per_image is None:
+            labels_per_image = torch.arange(nq, device=dev)
+        onehot = torch.zeros(nq, nk, dtype=torch.float32, device=dev)
+        onehot.scatter_(1, labels_per_image.to(device=dev, dtype=torch.int64).reshape(nq, 1), 1.0)
+        # BCE-with-logits is the mean over nq * nk elements; times nk it is the sum over pairs divided by nq
+        return {"loss_sig": _ElemLossFn.apply(logits_per_image + logit_bias, onehot, 0) * nk}
+
+
 class CriterionAlignment(nn.Module):
     """model_clip.py:664-715: IPOT optimal-transport distance between entity-text and object
     features (object slot 0 = whole image is dropped), summed over the batch, times 0.01."""

@@ -197,7 +197,7 @@ SEGMENT, CHUNK = 2048, 1 << 16       # longest range of one workgroup: the optim
 
 
 def tower_of(name: str) -> str:
-    """'visual', 'text' or 'head' (``logit_scale``): the range of the flat layout a parameter lives in."""
+    """'visual', 'text' or 'head' (``logit_scale``, ``logit_bias``): the range of the flat layout a parameter lives in."""
     if name.startswith("visual."):
         return "visual"
     return "text" if name.startswith(("transformer.", "token_embedding.", "positional_embedding", "ln_final.", "text_projection")) else "head"
@@ -356,6 +356,33 @@ class CLIP(nn.Module):
         self.constrastive_overbatch = constrastive_overbatch
         self.alignment = alignment
         self.multiattention = multiattention
+
+    def enable_logit_bias(self, init: float = -10.0):
+        """Register the scalar parameter ``logit_bias`` (the sigmoid pairwise loss adds it to every logit; SigLIP starts it at
+        -10).  Opt-in: without this call the model has exactly the reference's parameters.  Call it before the optimiser is
+        built.  The flat buffers, if they exist already, are dropped and rebuilt lazily with one more 64-element slot in the
+        ``head`` range (``tower_of`` answers 'head').  A second call sets the value."""
+        if getattr(self, "logit_bias", None) is not None:
+            with torch.no_grad():
+                self.logit_bias.fill_(float(init))
+            return self.logit_bias
+        dev = self.logit_scale.device
+        self.logit_bias = nn.Parameter(torch.full([], float(init), dtype=torch.float32, device=dev))
+        for k in ("_plist", "_plans"):
+            self.__dict__.pop(k, None)
+        if self._flat is not None:   # drop the device state as pickling does: _prepare() lays the parameters out anew on the next forward
+            state = self.__getstate__()          # (the parameters stay views of the old buffer until then)
+            self.__dict__.clear()
+            self.__setstate__(state)
+        return self.logit_bias
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        """``nn.Module.load_state_dict``; a state dict without ``logit_bias`` (a reference checkpoint) loaded into a model that has
+        the bias leaves the current bias value in place."""
+        if getattr(self, "logit_bias", None) is not None and "logit_bias" not in state_dict:
+            state_dict = dict(state_dict)
+            state_dict["logit_bias"] = self.logit_bias.detach().clone()
+        return super().load_state_dict(state_dict, strict=strict, **kw)
 
     def initialize_parameters(self):
         """model_clip.py:348-375 (text tower only; the vision tower keeps its constructor init)."""
@@ -1137,5 +1164,7 @@ def build_model(state_dict: dict) -> CLIP:
     for key in ["input_resolution", "context_length", "vocab_size"]:
         if key in state_dict:
             del state_dict[key]
+    if "logit_bias" in state_dict:          # a checkpoint of a model trained with the sigmoid loss
+        model.enable_logit_bias(float(state_dict["logit_bias"]))
     model.load_state_dict(state_dict)
     return model

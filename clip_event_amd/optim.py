@@ -680,12 +680,12 @@ class WarmupCosineLR(torch.optim.lr_scheduler._LRScheduler):
 
 def no_decay_groups(model, weight_decay: float):
     """The usual fine-tuning split as ``groups`` for ``FusedAdam`` / ``FusedSGD``: gains, biases, every other tensor of one
-    dimension or none and ``logit_scale`` get weight decay 0, the matrices (and embeddings) ``weight_decay``.  Trainable
+    dimension or none, ``logit_scale`` and ``logit_bias`` get weight decay 0, the matrices (and embeddings) ``weight_decay``.  Trainable
     parameters only, by name."""
     decay, no_decay = [], []
     for n, p in model.named_parameters():
         if p.requires_grad:
-            (no_decay if p.ndim < 2 or n.endswith(".bias") or n == "logit_scale" else decay).append(n)
+            (no_decay if p.ndim < 2 or n.endswith(".bias") or n in ("logit_scale", "logit_bias") else decay).append(n)
     return [g for g in ({"params": decay, "weight_decay": float(weight_decay)}, {"params": no_decay, "weight_decay": 0.0}) if g["params"]]
 
 

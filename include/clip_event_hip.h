@@ -522,6 +522,21 @@ int ce_infonce_bwd(const float* q, long ldq, const int64_t* sel, int nq, const f
                    const float* logit_scale, const int64_t* labels, const float* lse, const float* grad, float* dq, float* dk,
                    float* dlogit_scale, void* stream);
 
+/* Sigmoid pairwise loss (SigLIP) on the same sweep, one direction, with a logit bias; q, k, sel, labels as ce_infonce_fwd:
+ *   x[r,c] = s <q_r, k_c> + b,  z[r,c] = +1 if c == labels[sel[r]] else -1,  s = exp(*logit_scale), b = *logit_bias
+ *   fwd: *loss = -(1/nq) sum_r sum_c log sigma(z x)   (WRITTEN, not added: the workgroups' partials go to `workspace`,
+ *        ce_sigmoid_head_workspace_bytes(nq, nk) bytes, and are summed in a fixed order -- the same inputs give the same bits)
+ *   bwd: G[r,c] = -(*grad / nq) z sigma(-z x); dq[sel[r],:] += s sum_c G k_c, dk[c,:] += s sum_r G q_r,
+ *        *dlogit_scale += sum G (x - b), *dlogit_bias += sum G; nothing is saved by the forward.  dq and dk as for ce_infonce_bwd.
+ * fp32 on v_mfma_f32_32x32x2_f32; E a multiple of 128, 128..1024; nk < 2^24.  No allocation, no synchronisation. */
+size_t ce_sigmoid_head_workspace_bytes(int nq, int nk);
+int ce_sigmoid_head_fwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                        const float* logit_scale, const float* logit_bias, const int64_t* labels, float* loss, void* workspace,
+                        void* stream);
+int ce_sigmoid_head_bwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                        const float* logit_scale, const float* logit_bias, const int64_t* labels, const float* grad, float* dq,
+                        float* dk, float* dlogit_scale, float* dlogit_bias, void* stream);
+
 /* Scoring without the [nq, nk] logits matrix (retrieval.hip): best-k keys per query, log-sum-exp and the rank of one target,
  * on the similarity sweep of ce_infonce_fwd.  q [nq,E], keys [nk,E] are used as given (the caller normalises them:
  * ce_l2norm_fwd).  score(r, c) = s <q_r, keys_c>, s = exp(*logit_scale) (logit_scale nullable: s = 1).  Candidates are

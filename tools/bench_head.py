@@ -1,57 +1,93 @@
 #!/usr/bin/env python3
-"""Contrastive head at BASELINE config 3's per-rank shape (W = 8, B = 512, K = 5: 512 image rows against 20,480 gathered
-text columns; 512 positive text rows against 4,096 gathered image columns), forward + backward: the fused kernels
-(no logits matrix) against the logits + cross-entropy path.  Features are synthetic gathered matrices."""
-import os, sys
+"""The loss heads alone, forward + backward, on synthetic features: the fused sigmoid pairwise head (``SigmoidHeadFn``: one
+direction, three sweeps) against the fused InfoNCE pair head (``InfoNCEPairFn``: both directions, six sweeps and two merges) at
+the same shape in the same process, alternating, each sample one HIP-event interval around one forward + backward; the median
+and the spread (min .. max) of the samples are printed, and one JSON line at the end.
+
+Shapes (images x texts x embed dim): 256 x 256 x 512 (config 2), 512 x 2560 x 512 (B = 512, K = 5, one process) and
+4096 x 20480 x 512 (config 3's whole batch in one process: an 84 M-element logits matrix that neither head forms).
+``--logits`` adds the logits + criterion path of both losses where its matrix stays below 1 GB."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from clip_event_amd.functional import InfoNCEFn, logits_from_features
-from clip_event_amd.losses import cross_entropy
+
+from clip_event_amd.functional import InfoNCEPairFn, SigmoidHeadFn, logits_from_features
+from clip_event_amd.losses import CriterionContrastive, CriterionSigmoid
 
 DEV = "cuda:0"
+SHAPES = ((256, 256, 512), (512, 2560, 512), (4096, 20480, 512))
 
 
-def timeit(fn, iters=10, warm=2):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
+def sample(fn):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    for _ in range(iters):
-        fn()
+    fn()
     e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
+    e1.synchronize()
+    return e0.elapsed_time(e1)
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--iters", type=int, default=30, help="timed samples per head and shape")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--logits", action="store_true", help="also time logits + criterion")
+    args = ap.parse_args()
     torch.manual_seed(0)
-    E = 512
-    for B, K, W in ((512, 5, 8), (256, 1, 8), (256, 1, 1)):
-        N = B * W
-        fi = torch.randn(B, E, device=DEV, requires_grad=True)
-        ft = torch.randn(B * K, E, device=DEV, requires_grad=True)
-        fi_all = torch.randn(N, E, device=DEV, requires_grad=True)
-        ft_all = torch.randn(N * K, E, device=DEV, requires_grad=True)
+    results = []
+    for nq, nk, E in SHAPES:
+        K = nk // nq
+        fi = torch.randn(nq, E, device=DEV, requires_grad=True)
+        ft = torch.randn(nk, E, device=DEV, requires_grad=True)
         ls = torch.tensor(2.659, device=DEV, requires_grad=True)
-        yi = torch.arange(B, device=DEV) * K
-        yt = torch.arange(B, device=DEV).repeat_interleave(K)
-        ip = torch.arange(0, B * K, K, device=DEV)
+        lb = torch.tensor(-10.0, device=DEV, requires_grad=True)
+        yi = torch.arange(nq, device=DEV) * K
+        yt = torch.arange(nq, device=DEV).repeat_interleave(K)
+        ip = torch.arange(0, nk, K, device=DEV)
 
-        def fused():
-            l = InfoNCEFn.apply(fi, ft_all, ls, yi, None) + InfoNCEFn.apply(ft, fi_all, ls, yt, ip)
-            l.backward()
+        def sigmoid():
+            SigmoidHeadFn.apply(fi, ft, ls, lb, yi, None).backward()
 
-        def unfused():
-            lpi, _ = logits_from_features(fi, ft_all, ls, True, want="image")
-            _, lpt = logits_from_features(fi_all, ft, ls, True, want="text")
-            l = cross_entropy(lpi, yi) + cross_entropy(lpt, yt, ip)
-            l.backward()
+        def infonce():
+            li, lt = InfoNCEPairFn.apply(fi, ft, ls, yi, yt, ip)
+            (li + lt).backward()
 
-        tf, tu = timeit(fused), timeit(unfused)
-        flops = 3 * 2.0 * E * (B * N * K + B * N)          # fwd + two backward products, both directions (the fused path's work)
-        print(f"B={B} K={K} W={W}: fused {tf:.3f} ms ({flops / tf / 1e9:.1f} TF/s on 6*nq*nk*E), logits+CE path {tu:.3f} ms "
-              f"(logits_per_image {B * N * K * 4 / 1e6:.0f} MB + logits_per_text {B * K * N * 4 / 1e6:.0f} MB materialised)", flush=True)
+        heads = {"sigmoid": sigmoid, "infonce_pair": infonce}
+        if args.logits and nq * nk * 4 < (1 << 30):
+            crit_s, crit_c = CriterionSigmoid(), CriterionContrastive("ce")
+
+            def sigmoid_logits():
+                lpi, _ = logits_from_features(fi, ft, ls, True, want="image")
+                crit_s(lpi, None, yi, logit_bias=lb)["loss_sig"].backward()
+
+            def infonce_logits():
+                ld = crit_c(*logits_from_features(fi, ft, ls, True), yi, yt, index_pos=ip)
+                (ld["loss_i"] + ld["loss_t"]).backward()
+
+            heads.update(sigmoid_logits=sigmoid_logits, infonce_logits=infonce_logits)
+        for fn in heads.values():
+            for _ in range(args.warmup):
+                fn()
+        torch.cuda.synchronize()
+        times = {name: [] for name in heads}
+        for _ in range(args.iters):                      # alternate: both heads see the same clocks and neighbours
+            for name, fn in heads.items():
+                times[name].append(sample(fn))
+        row = {"nq": nq, "nk": nk, "E": E}
+        for name, ts in times.items():
+            row[name] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
+        row["sigmoid_over_infonce_pair"] = row["sigmoid"]["median_ms"] / row["infonce_pair"]["median_ms"]
+        results.append(row)
+        print(f"{nq} x {nk} x {E}: " + "; ".join(f"{name} {r['median_ms']:.3f} ms ({r['min_ms']:.3f} .. {r['max_ms']:.3f})"
+                                                 for name, r in row.items() if isinstance(r, dict))
+              + f"; sigmoid / InfoNCE pair {row['sigmoid_over_infonce_pair']:.2f}", flush=True)
+        del fi, ft
+    print(json.dumps({"bench": "head", "iters": args.iters, "results": results}))
 
 
 if __name__ == "__main__":

@@ -14,6 +14,9 @@ and its output side), ``--no-decay-groups`` puts gains, biases and ``logit_scale
 
 ``--patch-dropout P`` trains the image tower on a random ``1 - P`` of the patches of every image (CLIP.set_patch_dropout).
 
+``--loss sigmoid`` trains with the sigmoid pairwise loss of SigLIP (losses.CriterionSigmoid on the fused sigmoid head) and its
+learnable logit bias (``CLIP.enable_logit_bias``; ``--logit-bias INIT``, default -10); the checkpoint carries the bias.
+
 ``--ema DECAY`` keeps an exponential moving average of the weights in the fused step (``optimizer.enable_ema``; ``--ema-warmup``:
 the ramped decay of ``optim.ema_rate``); the checkpoint carries it, the resumed run restores it, and the end prints
 ``inference.retrieval_metrics`` on the fixed batch for the raw and for the averaged weights (``optimizer.averaged()``)."""
@@ -28,7 +31,7 @@ import torch
 
 from clip_event_amd import checkpoint, clip, distributed as D, inference, synthetic as S
 from clip_event_amd.engine import train_step
-from clip_event_amd.losses import CriterionContrastive
+from clip_event_amd.losses import CriterionContrastive, CriterionSigmoid
 from clip_event_amd.optim import FusedAdam, FusedSGD, build_lr_scheduler, build_optimizer, no_decay_groups
 from clip_event_amd.preprocess import preprocess
 
@@ -59,7 +62,12 @@ def main():
                     help="train the image tower on a random 1 - P of the patches (CLIP.set_patch_dropout)")
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="weight EMA in the fused step (optimizer.enable_ema)")
     ap.add_argument("--ema-warmup", action="store_true", help="with --ema: ramp the decay up (optim.ema_rate)")
+    ap.add_argument("--loss", choices=("ce", "sigmoid"), default="ce", help="contrastive criterion: InfoNCE or the sigmoid pairwise loss")
+    ap.add_argument("--logit-bias", type=float, default=None, metavar="INIT",
+                    help="with --loss sigmoid: initial logit bias (default -10)")
     args = ap.parse_args()
+    if args.logit_bias is not None and args.loss != "sigmoid":
+        ap.error("--logit-bias goes with --loss sigmoid")
     if args.ema_warmup and args.ema is None:
         ap.error("--ema-warmup goes with --ema")
     if args.adamw and args.optimizer != "adam":
@@ -73,7 +81,9 @@ def main():
     rng = np.random.default_rng(0)
     model = S.synthetic_model("vit_b32", seed=0).to(dev)
     model.set_hyps(constrastive_overbatch=True, alignment=False, multiattention=False)
-    criterion = CriterionContrastive("ce")
+    criterion = CriterionContrastive("ce") if args.loss == "ce" else CriterionSigmoid()
+    if args.loss == "sigmoid":
+        model.enable_logit_bias(-10.0 if args.logit_bias is None else args.logit_bias)      # before the optimiser is built
     if args.no_decay_groups or args.adamw:
         cfg["weight_decay"] = 0.1
 
@@ -105,11 +115,14 @@ def main():
         losses.append(float(sum(v.detach() for v in ld.values())))
     print("loss:", " ".join(f"{v:.3f}" for v in losses[::3]), "lr", optimizer.param_groups[0]["lr"])
     # (a locked tower, or an image tower that sees other patches every step, cannot follow the fixed batch as fast: the loss
-    # must still fall)
-    assert losses[-1] < (0.5 if not (args.lock_image_tower or args.lock_text_tower or args.patch_dropout) else 1.0) * losses[0]
+    # must still fall; so must the sigmoid loss, which starts at about |logit_bias| per image -- every positive pair far on the
+    # wrong side -- and has 20 steps at lr 1e-5 to pull the positives up)
+    slow = args.lock_image_tower or args.lock_text_tower or args.patch_dropout or args.loss == "sigmoid"
+    assert losses[-1] < (0.5 if not slow else 1.0) * losses[0]
     with tempfile.TemporaryDirectory() as d:
         path = checkpoint.save_model_on_master(model, d, cfg["task"], 20, 0.0, optimizer)      # engine.py:202-218
         model2, opt_state, begin_epoch, _ = checkpoint.load_checkpoint(path, device=dev)       # train.py:101-124
+        assert (getattr(model2, "logit_bias", None) is not None) == (args.loss == "sigmoid")   # build_model enables it from the key
         lock(model2)
         # neither the rate nor the draw counter is in the checkpoint: a resumed run sets them again
         model2.set_patch_dropout(args.patch_dropout, seed=0)
