@@ -462,7 +462,8 @@ __device__ __forceinline__ void long_block_coords(int xcd_order, int& blk, int& 
 // SLOWER in the forward (3.27-3.58 vs 3.00-3.19) and in dK / dV with two key tiles (10.97 vs 9.9), slightly faster in dQ
 // (9.34 vs 9.49, 9.86 vs 9.96 for the whole backward) -- the 138-200 registers of the wider forms halve the resident waves and
 // these kernels live on occupancy (barriers, dependent exp chains), not on LDS bandwidth.  Defaults: forward 1, dQ 2, dK / dV 1;
-// every form is parity-tested (CE_ATTN_NS_FWD / CE_ATTN_NS / CE_ATTN_NK).
+// every form (CE_ATTN_NS_FWD / CE_ATTN_NS / CE_ATTN_NK, and CE_ATTN_XCD=0) runs tests/test_attention_ops.py's long table against
+// fp64 in a process of its own.
 template <int NS>
 __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const bf16_t* __restrict__ qkv, long ld, bf16_t* __restrict__ o,
                                                             long ldo, float* __restrict__ lse, int L, int H, int D,
