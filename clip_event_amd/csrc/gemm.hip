@@ -2052,6 +2052,10 @@ template <int EPI, int F8>
 int launch_nt(NTArgs a, hipStream_t stream) {
     const NTPlan p = nt_plan(NTShape{a.M, a.N, a.K, a.lda, a.ldb, a.ldo, a.ldo2, a.ldaux, a.ldr}, EPI, F8, g_knobs);
     if (!p.taken) return 1;
+    // the 128x128 kernel's column sums are a second launch (ce_colsum_bf16, 8-column accesses): refuse what it would refuse
+    // before anything is launched, not after `out` has been written
+    CE_CHECK_ARG(!(p.needs_colsum_pass && a.out2) || (a.N % 8 == 0 && a.ldo % 8 == 0),
+                 "ce_gemm_nt: GELUGRAD column sums on the 128x128 kernel need N and ldo multiples of 8 (N=%d ldo=%ld)", a.N, a.ldo);
     g_last_plan = p;
     const double operand_bytes = (F8 ? 1.0 : 2.0) * ((double)a.M * a.K + (double)a.N * a.K);
     CeProfScope prof(nt_prof_class(EPI) + p.family, 2.0 * a.M * a.N * a.K, operand_bytes + epi_traffic_bytes(EPI) * a.M * a.N, stream);

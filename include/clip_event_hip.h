@@ -41,7 +41,9 @@ enum {
     CE_EPI_BIAS_GELU = 5,     /* a = acc + bias; out(bf16) = dQuickGELU(a) = s + 1.702 a s (1 - s), s = sigmoid(1.702 a): the
                                * factor the backward needs, from the fp32 a; out2(bf16) = QuickGELU(a) = a s */
     CE_EPI_GELUGRAD_BF16 = 6, /* out(bf16) = acc * aux(bf16), aux = the derivative BIAS_GELU saved; out2 (nullable) is reused as
-                               * a float[N] that receives += the column sums of out (bias gradient)      */
+                               * a float[N] that receives += the column sums of out (bias gradient); where the launch
+                               * policy picks the 128x128 kernel (ce_gemm_nt_plan) the sums are a second pass over out,
+                               * which takes N % 8 == 0 and ldo % 8 == 0 only: refused otherwise, before anything is launched */
     CE_EPI_BIAS_RESID_F16 = 7,/* out(f16)  = resid(f16) + acc + bias[n]: the residual add on an fp16 stream (CE_T_F16;
                                * resid / out point at IEEE half data, ldr / ldo in elements; stores saturate at 65504) */
     CE_EPI_BIAS_QGELU_BF16 = 8/* out(bf16) = QuickGELU(acc + bias[n]): BIAS_GELU's out2 bit for bit (same tile variant at the same
