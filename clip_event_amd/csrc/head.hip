@@ -8,6 +8,7 @@
 //   ce_l2norm_fwd / _bwd   f / ||f||  (no eps, as the reference)
 //   ce_sgemm               C = alpha * op(A) op(B) (+ beta*C), arbitrary strides, fp32 LDS-tiled
 //   ce_xent_fwd / _bwd     row-wise cross entropy on selected rows (index_pos), mean reduction
+//   ce_soft_xent_fwd/_bwd  the same against a teacher's softmax instead of labels (distillation on materialised logits)
 //   ce_dot                 out += sum a*b   (logit_scale gradient)
 #include "common.hpp"
 #include "../../include/clip_event_hip.h"
@@ -148,6 +149,57 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__
     }
 }
 
+// soft targets: per selected row, lse of the logits x and of the teacher's t, loss_r = lse_x - sum_c exp(t_c - lse_t) x_c
+__global__ __launch_bounds__(256) void soft_xent_fwd_kernel(const float* __restrict__ logits, long ld,
+                                                            const float* __restrict__ teacher, long ldt,
+                                                            const long* __restrict__ sel, float* __restrict__ row_lse,
+                                                            float* __restrict__ row_lse_t, float* __restrict__ loss,
+                                                            int nrows, int C) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= nrows) return;
+    const long src = sel ? sel[r] : (long)r;
+    const float* x = logits + src * ld;
+    const float* t = teacher + src * ldt;
+    float mx = -INFINITY, mt = -INFINITY;
+    for (int c = lane; c < C; c += 64) {
+        mx = fmaxf(mx, x[c]);
+        mt = fmaxf(mt, t[c]);
+    }
+    mx = wave_max(mx);
+    mt = wave_max(mt);
+    float sx = 0.f, st = 0.f, stx = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        const float e = __expf(t[c] - mt);
+        sx += __expf(x[c] - mx);
+        st += e;
+        stx += e * x[c];
+    }
+    sx = wave_sum(sx);
+    st = wave_sum(st);
+    stx = wave_sum(stx);
+    if (lane == 0) {
+        const float l = mx + __logf(sx);
+        row_lse[r] = l;
+        row_lse_t[r] = mt + __logf(st);
+        atomicAdd(loss, (l - stx / st) / (float)nrows);
+    }
+}
+
+// dlogits[src, c] = g / nrows * (exp(x - lse_x) - exp(t - lse_t)); rows not selected are left untouched
+__global__ __launch_bounds__(256) void soft_xent_bwd_kernel(const float* __restrict__ logits, long ld,
+                                                            const float* __restrict__ teacher, long ldt,
+                                                            const long* __restrict__ sel, const float* __restrict__ row_lse,
+                                                            const float* __restrict__ row_lse_t, const float* __restrict__ gptr,
+                                                            float* __restrict__ dlogits, long ldd, int nrows, int C) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= nrows) return;
+    const long src = sel ? sel[r] : (long)r;
+    const float g = *gptr / (float)nrows;
+    const float l = row_lse[r], lt = row_lse_t[r];
+    for (int c = lane; c < C; c += 64)
+        dlogits[src * ldd + c] = g * (__expf(logits[src * ld + c] - l) - __expf(teacher[src * ldt + c] - lt));
+}
+
 __global__ __launch_bounds__(256) void dot_kernel(const float* __restrict__ a, const float* __restrict__ b, long n,
                                                   float* __restrict__ out) {
     __shared__ float red[4];
@@ -270,6 +322,27 @@ extern "C" int ce_xent_bwd(const float* logits, long ld, const int64_t* labels, 
     CE_CHECK_ARG(nrows > 0 && C > 0, "ce_xent_bwd: empty");
     hipLaunchKernelGGL(xent_bwd_kernel, dim3(ce_div_up(nrows, 4)), dim3(256), 0, (hipStream_t)stream, logits, ld,
                        (const long*)labels, (const long*)sel, row_lse, grad, dlogits, ldd, nrows, C);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_soft_xent_fwd(const float* logits, long ld, const float* teacher_logits, long ldt, const int64_t* sel,
+                                float* row_lse, float* row_lse_t, float* loss, int nrows, int C, void* stream) {
+    CE_CHECK_ARG(logits && teacher_logits && row_lse && row_lse_t && loss, "ce_soft_xent_fwd: null buffer");
+    CE_CHECK_ARG(nrows > 0 && C > 0 && ld >= C && ldt >= C, "ce_soft_xent_fwd: bad shape");
+    hipLaunchKernelGGL(soft_xent_fwd_kernel, dim3(ce_div_up(nrows, 4)), dim3(256), 0, (hipStream_t)stream, logits, ld,
+                       teacher_logits, ldt, (const long*)sel, row_lse, row_lse_t, loss, nrows, C);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_soft_xent_bwd(const float* logits, long ld, const float* teacher_logits, long ldt, const int64_t* sel,
+                                const float* row_lse, const float* row_lse_t, const float* grad, float* dlogits, long ldd,
+                                int nrows, int C, void* stream) {
+    CE_CHECK_ARG(logits && teacher_logits && row_lse && row_lse_t && grad && dlogits, "ce_soft_xent_bwd: null buffer");
+    CE_CHECK_ARG(nrows > 0 && C > 0 && ld >= C && ldt >= C && ldd >= C, "ce_soft_xent_bwd: bad shape");
+    hipLaunchKernelGGL(soft_xent_bwd_kernel, dim3(ce_div_up(nrows, 4)), dim3(256), 0, (hipStream_t)stream, logits, ld,
+                       teacher_logits, ldt, (const long*)sel, row_lse, row_lse_t, grad, dlogits, ldd, nrows, C);
     CE_LAUNCH_CHECK();
     return 0;
 }

@@ -31,6 +31,9 @@
 //     fixed order and applies 1/nq: the loss is bit-identical from run to run (no float atomics on it).
 //   * G in DQ / DK; qinfo carries the label only.
 //   * zero-padded tile positions are NOT neutral (softplus(0) = log 2): every term is masked by row and column validity.
+// LOSS_DISTILL (cross entropy against a teacher's softmax; the entry points at the end of the file compose it from sweeps):
+// FWD leaves the log-sum-exp partials only; in DQ / DK G = c exp(x - lse) with no label, the gradient product streams a VALUE
+// matrix of its own width (HeadArgs::val) in place of the streamed operand, and the write has a scale of its own.
 #include <stdlib.h>
 
 #include <mutex>
@@ -42,14 +45,14 @@ namespace {
 
 constexpr int HB = 32;          // rows per resident / streamed block
 enum { MODE_FWD = 0, MODE_DQ = 1, MODE_DK = 2 };
-enum { LOSS_SOFTMAX = 0, LOSS_SIGMOID = 1 };
+enum { LOSS_SOFTMAX = 0, LOSS_SIGMOID = 1, LOSS_DISTILL = 2 };
 
 struct HeadArgs {
     const float* res; long ldres; int nres;       // resident matrix (queries for FWD / DQ, keys for DK)
     const float* str; long ldstr; int nstr;       // streamed matrix
     const long* sel;                              // query row gather (nullable): query r = row sel[r] of its matrix
     const long* labels;                           // key index per query SOURCE row (labels[sel[r]])
-    const float* lse;                             // [nq]            (DQ / DK)
+    const float* lse;                             // [nq]            (DQ / DK; LOSS_DISTILL: [nq][2] = (max, log sum), see lse_merge_kernel)
     const float* logit_scale;
     const float* grad;                            // upstream scalar (DQ / DK)
     float* part;                                  // FWD: [splits][nq][2] partial (max, sum)
@@ -60,6 +63,13 @@ struct HeadArgs {
     const float* logit_bias;
     float* dbias;                                 // DQ: logit_bias gradient (+=)
     float* loss_part;                             // FWD: [splits][row blocks] loss partial of each workgroup
+    // LOSS_DISTILL only
+    const float* val; long ldval; int Eval;       // DQ / DK: value matrix of the gradient product (rows gathered as the streamed rows)
+    const long* osel;                             // DQ: row of dres that resident r adds to (nullable: row r)
+    const float* out_logit_scale;                 // DQ / DK: the write multiplies by exp(*out_logit_scale) (nullable: by 1)
+    const float* sub;                             // DQ: [nres, Eval], the write also subtracts c exp(*out_logit_scale) sub[r] (nullable)
+    const float* dot; long lddot;                 // DQ: part[split][r] = <dot[sel[r]], this split's share of output row r> (nullable)
+    float csign;                                  // c = csign * (grad ? *grad / nq : 1)
 };
 
 __device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // 32x32 C/D row of reg r
@@ -92,7 +102,9 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int r0 = blockIdx.x * HB;
-    const float scale = __expf(*a.logit_scale);
+    // distillation: the correctly rounded exp.  __expf(log 100) is off by 2e-7 of itself (the rounding of x log2(e)), which moves
+    // logits near 40 by 1e-5, and the teacher's scale reshapes the target distribution
+    const float scale = (LOSS == LOSS_DISTILL) ? expf(*a.logit_scale) : __expf(*a.logit_scale);
 
     // ---- resident block -> LDS (gathered through sel when the residents are queries) ----
     for (int idx = tid; idx < HB * (E / 4); idx += 64 * NW) {
@@ -107,14 +119,19 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
     // per-lane facts about resident row j
     const bool jvalid = r0 + j < a.nres;
     long jsrc = 0, jlabel = -1;
-    float jlse = 0.f;
+    float jlse = 0.f, jlse_lo = 0.f;
     if (MODE != MODE_DK && jvalid) {
         jsrc = a.sel ? a.sel[r0 + j] : (long)(r0 + j);
-        jlabel = a.labels[jsrc];
+        if (LOSS != LOSS_DISTILL) jlabel = a.labels[jsrc];
         if (MODE == MODE_DQ && LOSS == LOSS_SOFTMAX) jlse = a.lse[r0 + j];
+        if (MODE == MODE_DQ && LOSS == LOSS_DISTILL) {
+            jlse = a.lse[2 * (r0 + j)];
+            jlse_lo = a.lse[2 * (r0 + j) + 1];
+        }
     }
     const float bias = (LOSS == LOSS_SIGMOID) ? *a.logit_bias : 0.f;
-    const float coef = (MODE == MODE_FWD) ? 0.f : (*a.grad / (float)a.nq);
+    const float coef = (MODE == MODE_FWD) ? 0.f
+                       : (LOSS == LOSS_DISTILL) ? a.csign * (a.grad ? *a.grad / (float)a.nq : 1.f) : (*a.grad / (float)a.nq);
     __syncthreads();
 
     float run_m = -INFINITY, run_l = 0.f;                 // FWD: online statistics of query j over this split
@@ -122,7 +139,12 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
     float loss_acc = 0.f, dbias_acc = 0.f;                // sigmoid: FWD loss terms / DQ bias gradient of this lane
     constexpr int GT = 32 / NW;                           // gradient accumulators: up to 1024 / NW / 32 e-tiles of 32 per wave
     f32x16 gacc[MODE == MODE_FWD ? 1 : GT];
-    const int etiles = E / (32 * NW);                     // e-tiles of 32 columns per wave (E/NW columns per wave)
+    // the gradient product runs over the value matrix: the streamed matrix itself, or (distillation) one of another width
+    const int EV = (LOSS == LOSS_DISTILL && MODE != MODE_FWD) ? a.Eval : E;
+    const float* const vmat = (LOSS == LOSS_DISTILL && MODE != MODE_FWD) ? a.val : a.str;
+    const long ldv = (LOSS == LOSS_DISTILL && MODE != MODE_FWD) ? a.ldval : a.ldstr;
+    const int etiles = EV / (32 * NW);                    // e-tiles of 32 columns per wave (EV/NW columns per wave)
+    const int ev_lo = wave * (EV / NW);
     if (MODE != MODE_FWD) {
 #pragma unroll
         for (int t = 0; t < GT; ++t)
@@ -161,7 +183,11 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
             const bool v = c0 + tid < a.nstr;
             const long src = v ? (a.sel ? a.sel[c0 + tid] : (long)(c0 + tid)) : 0;
             if (LOSS == LOSS_SOFTMAX) qinfo[tid] = v ? a.lse[c0 + tid] : 0.f;
-            qinfo[HB + tid] = v ? (float)a.labels[src] : -1.f;          // key indices < 2^24: exact in fp32
+            if (LOSS != LOSS_DISTILL) qinfo[HB + tid] = v ? (float)a.labels[src] : -1.f;          // key indices < 2^24: exact in fp32
+            if (LOSS == LOSS_DISTILL) {                   // no label: the second slot carries the low part of the log-sum-exp
+                qinfo[tid] = v ? a.lse[2 * (c0 + tid)] : 0.f;
+                qinfo[HB + tid] = v ? a.lse[2 * (c0 + tid) + 1] : 0.f;
+            }
         }
         __syncthreads();
         if (MODE == MODE_FWD && LOSS == LOSS_SIGMOID) {
@@ -215,6 +241,9 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
                         g = (pos ? -coef : coef) * sigmoid_neg(pos ? x : -x);
                     }
                     if (MODE == MODE_DQ) dbias_acc += g;
+                } else if (LOSS == LOSS_DISTILL) {                      // no label term: c softmax
+                    if (jvalid && c0 + i < a.nstr)
+                        g = coef * __expf((S[r] - (MODE == MODE_DQ ? jlse : qinfo[i])) - (MODE == MODE_DQ ? jlse_lo : qinfo[HB + i]));
                 } else if (MODE == MODE_DQ) {
                     if (jvalid && c0 + i < a.nstr) g = coef * (__expf(S[r] - jlse) - ((long)(c0 + i) == jlabel ? 1.f : 0.f));
                 } else {
@@ -222,20 +251,20 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
                         g = coef * (__expf(S[r] - qinfo[i]) - ((float)(r0 + j) == qinfo[HB + i] ? 1.f : 0.f));
                 }
                 G[r] = g;
-                if (MODE == MODE_DQ) dls_acc += g * S[r];
+                if (MODE == MODE_DQ && LOSS != LOSS_DISTILL) dls_acc += g * S[r];
             }
             // ---- gradient product: dres^T[e][j] += sum_i streamed[i][e] G^T[i][j]; A = streamed[i(r,h)][e0 + (lane&31)] ----
 #pragma unroll
             for (int t = 0; t < GT; ++t) {
                 if (t < etiles) {
-                const int e0 = e_lo + 32 * t + j;
+                const int e0 = ev_lo + 32 * t + j;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int i = c0 + row_of(r, h);
                     float av = 0.f;
                     if (i < a.nstr) {
                         const long src = (MODE == MODE_DK && a.sel) ? a.sel[i] : (long)i;
-                        av = a.str[src * a.ldstr + e0];
+                        av = vmat[src * ldv + e0];
                     }
                     gacc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, G[r], gacc[t], 0, 0, 0);
                 }
@@ -266,7 +295,7 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
         return;
     }
     // ---- gradient out: transpose each 32(e) x 32(j) tile through LDS, then whole 128-byte row segments ----
-    if (MODE == MODE_DQ) {
+    if (MODE == MODE_DQ && LOSS != LOSS_DISTILL) {
         dls_acc = wave_sum(dls_acc);
         if (lane == 0 && wave == 0) atomicAdd(a.dls, dls_acc);        // every wave holds the same tile sums: count once
         if (LOSS == LOSS_SIGMOID) {
@@ -274,20 +303,50 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
             if (lane == 0 && wave == 0) atomicAdd(a.dbias, dbias_acc);
         }
     }
+    if (LOSS == LOSS_DISTILL && MODE == MODE_DQ && a.dot) {
+        // <dot_j, this split's share of row j>, one plain store per (split, row): the caller adds the splits in index order,
+        // so what is built on it repeats bit for bit although the rows themselves are accumulated by float atomics.
+        // gacc[t][r] is element e = ev_lo + 32 t + row_of(r, h) of resident row j.
+        float d = 0.f;
+        if (jvalid) {
+            const float* drow = a.dot + jsrc * a.lddot + ev_lo;
+#pragma unroll
+            for (int t = 0; t < GT; ++t) {
+                if (t >= etiles) continue;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) d += gacc[t][r] * drow[32 * t + row_of(r, h)];
+            }
+        }
+        d += __shfl_xor(d, 32, 64);
+        __syncthreads();                                              // the last tile's readers of part_l are done
+        if (h == 0) part_l[wave * HB + j] = d;
+        __syncthreads();
+        if (tid < HB && r0 + tid < a.nres) {
+            float t = 0.f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) t += part_l[w * HB + tid];
+            a.part[(long)blockIdx.y * a.nq + r0 + tid] = t;
+        }
+    }
     __syncthreads();
     float* tile = part_l + wave * HB * 33;                            // [j][e'] for this wave
+    // the factor at the write: the similarity's scale, or (distillation) the student's whatever the similarity was
+    const float oscale = (LOSS == LOSS_DISTILL) ? (a.out_logit_scale ? expf(*a.out_logit_scale) : 1.f) : scale;
+    const long* const osel = (LOSS == LOSS_DISTILL) ? a.osel : a.sel;
 #pragma unroll
     for (int t = 0; t < GT; ++t) {
         if (t >= etiles) continue;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) tile[j * 33 + row_of(r, h)] = gacc[t][r] * scale;
+        for (int r = 0; r < 16; ++r) tile[j * 33 + row_of(r, h)] = gacc[t][r] * oscale;
         // lanes: 2 rows per pass (row = pass*2 + h), 32 columns
         for (int pass = 0; pass < 16; ++pass) {
             const int jr = pass * 2 + h;
             if (r0 + jr < a.nres) {
-                const long dst = (MODE == MODE_DQ && a.sel) ? a.sel[r0 + jr] : (long)(r0 + jr);
-                float* o = a.dres + dst * (long)E + e_lo + 32 * t + j;
-                const float v = tile[jr * 33 + j];
+                const long dst = (MODE == MODE_DQ && osel) ? osel[r0 + jr] : (long)(r0 + jr);
+                float* o = a.dres + dst * (long)EV + ev_lo + 32 * t + j;
+                float v = tile[jr * 33 + j];
+                if (LOSS == LOSS_DISTILL && MODE == MODE_DQ && a.sub && blockIdx.y == 0)          // once per row: the first split
+                    v -= coef * oscale * a.sub[(long)(r0 + jr) * EV + ev_lo + 32 * t + j];
                 if (a.splits == 1) *o += v;
                 else atomicAdd(o, v);
             }
@@ -347,7 +406,11 @@ int launch_head(HeadArgs& a, hipStream_t s) {
     });
     const int rb = ce_div_up(a.nres, HB);
     static const int force_nw = getenv("CE_HEAD_WAVES") ? atoi(getenv("CE_HEAD_WAVES")) : 0;
-    const bool eight = a.E % 256 == 0 && a.E <= 768 && force_nw != 4;
+    // eight waves split BOTH widths in eight: a 128-wide value matrix under a 256-wide similarity would get no e-tile.  The
+    // rule holds for FWD too (Eval = the width of the values its log-sum-exp will later weigh): the waves' partial tiles are
+    // added in wave order, so a similarity summed by eight waves differs in its last bits from the same one summed by four, and
+    // exp(x - max) of a row's largest entry is exactly 1 only when the sweep that rebuilds x adds it up as FWD did
+    const bool eight = a.E % 256 == 0 && a.E <= 768 && force_nw != 4 && (LOSS != LOSS_DISTILL || a.Eval % 256 == 0);
     if (eight) hipLaunchKernelGGL((infonce_kernel<MODE, 8, LOSS>), dim3(rb, a.splits), dim3(512), head_lds_bytes(a.E, 8), s, a);
     else hipLaunchKernelGGL((infonce_kernel<MODE, 4, LOSS>), dim3(rb, a.splits), dim3(256), head_lds_bytes(a.E, 4), s, a);
     return 0;
@@ -472,6 +535,169 @@ extern "C" int ce_sigmoid_head_bwd(const float* q, long ldq, const int64_t* sel,
     a.blocks_per_split = ce_div_up(ce_div_up(nq, HB), a.splits);
     a.splits = ce_div_up(ce_div_up(nq, HB), a.blocks_per_split);
     launch_head<MODE_DK, LOSS_SIGMOID>(a, s);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- distillation: cross entropy against a teacher's softmax, on sweeps of the same skeleton --------------------------
+//   S = s <q^_r, k^_c> (student, width Es), T = st <tq^_r, tk^_c> (teacher, width Et, constants), P_t = softmax_c T, P_s = softmax_c S
+//   loss = (1/nq) sum_r (lse_s[r] - sum_c P_t S),   G = (g/nq)(P_s - P_t)
+// With v_r = sum_c P_t[r,c] k^_c ([nq, Es]): sum_c P_t S = s <q^_r, v_r> and dq^_r = (g/nq) s (sum_c P_s k^_c - v_r), so no sweep ever
+// needs a student and a teacher resident block in LDS at once (512 + 768 wide: 165 KB at 32 rows).  A sweep of LOSS_DISTILL
+// has G = c exp(x - lse) with no label term, streams a value matrix that is not the similarity operand through the gradient
+// product (its own width: accumulators and output transpose run over Eval) and writes with a scale of its own.
+
+namespace {
+
+// log-sum-exp from the per-split (max, sum), one thread per query, kept as the pair (max, log sum): one float holds a
+// log-sum-exp near 40 to 2e-6 only, and a softmax rebuilt as exp(x - lse) would be off by that factor in EVERY entry of the
+// row -- up to 2e-6 x sum_c P S ~ 1e-4 in a row term whose value is ~ 1 when both distributions are peaked.  exp((x - max)
+// - log sum) is normalised to fp32 rounding -- provided the sweep rebuilds x bit for bit as FWD saw it (launch_head's wave rule).
+__global__ __launch_bounds__(256) void lse_merge_kernel(const float* __restrict__ part, int splits, int nq, float* __restrict__ lse_out) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= nq) return;
+    float m = -INFINITY;
+    for (int s = 0; s < splits; ++s) m = fmaxf(m, part[((long)s * nq + r) * 2]);
+    float l = 0.f;
+    for (int s = 0; s < splits; ++s) {
+        const float* p = part + ((long)s * nq + r) * 2;
+        l += p[1] * __expf(p[0] - m);
+    }
+    lse_out[2 * r] = m;
+    lse_out[2 * r + 1] = __logf(l);
+}
+
+// term[r] = lse_s[r] - s <q^_r, v_r>, the dot product as the sum of the v sweep's per-split shares in index order
+__global__ __launch_bounds__(256) void distill_row_term_kernel(const float* __restrict__ dotpart, int splits,
+                                                               const float* __restrict__ lse_s,
+                                                               const float* __restrict__ logit_scale, int nq,
+                                                               float* __restrict__ term) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= nq) return;
+    float d = 0.f;
+    for (int s = 0; s < splits; ++s) d += dotpart[(long)s * nq + r];
+    term[r] = (lse_s[2 * r] - expf(*logit_scale) * d) + lse_s[2 * r + 1];
+}
+
+// *out += sum_r <x_r, y_r>: one wave per row
+__global__ __launch_bounds__(256) void rowdot_sum_kernel(const float* __restrict__ x, long ldx, const float* __restrict__ y, long ldy,
+                                                         int n, int E, float* __restrict__ out) {
+    __shared__ float red[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float d = 0.f;
+    for (int r = blockIdx.x * 4 + w; r < n; r += gridDim.x * 4) {
+        const float* xr = x + (long)r * ldx;
+        const float* yr = y + (long)r * ldy;
+        for (int c = lane; c < E; c += 64) d += xr[c] * yr[c];
+    }
+    d = wave_sum(d);
+    if (lane == 0) red[w] = d;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1]) + (red[2] + red[3]));
+}
+
+void set_splits(HeadArgs& a, int cap) {
+    a.splits = pick_splits(a.nres, a.nstr, cap);
+    a.blocks_per_split = ce_div_up(ce_div_up(a.nstr, HB), a.splits);
+    a.splits = ce_div_up(ce_div_up(a.nstr, HB), a.blocks_per_split);
+}
+
+int check_distill(const char* what, const float* q, long ldq, int nq, const float* k, long ldk, int nk, int Es,
+                  const float* logit_scale, const float* tq, long ldtq, const float* tk, long ldtk, int Et,
+                  const float* teacher_logit_scale) {
+    CE_CHECK_ARG(q && k && logit_scale && tq && tk && teacher_logit_scale, "%s: null buffer", what);
+    CE_CHECK_ARG(nq > 0 && nk > 0, "%s: empty problem", what);
+    CE_CHECK_ARG(Es >= 128 && Es % 128 == 0 && Es <= 1024, "%s: Es must be a multiple of 128 in 128..1024 (got %d)", what, Es);
+    CE_CHECK_ARG(Et >= 128 && Et % 128 == 0 && Et <= 1024, "%s: Et must be a multiple of 128 in 128..1024 (got %d)", what, Et);
+    CE_CHECK_ARG(ldq >= Es && ldk >= Es && ldq % 4 == 0 && ldk % 4 == 0, "%s: student leading dimensions must be >= Es and multiples of 4",
+                 what);
+    CE_CHECK_ARG(ldtq >= Et && ldtk >= Et && ldtq % 4 == 0 && ldtk % 4 == 0,
+                 "%s: teacher leading dimensions must be >= Et and multiples of 4", what);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" size_t ce_distill_head_workspace_bytes(int nq) { return ce_infonce_workspace_bytes(nq); }
+
+extern "C" int ce_distill_head_fwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int Es,
+                                   const float* logit_scale, const float* tq, long ldtq, const float* tk, long ldtk, int Et,
+                                   const float* teacher_logit_scale, float* lse_s, float* lse_t, float* v, float* loss,
+                                   void* workspace, void* stream) {
+    if (int rc = check_distill("ce_distill_head_fwd", q, ldq, nq, k, ldk, nk, Es, logit_scale, tq, ldtq, tk, ldtk, Et,
+                               teacher_logit_scale))
+        return rc;
+    CE_CHECK_ARG(lse_s && lse_t && v && loss && workspace, "ce_distill_head_fwd: null output");
+    hipStream_t s = (hipStream_t)stream;
+    HeadArgs a{};
+    a.sel = (const long*)sel; a.nq = nq; a.part = (float*)workspace;
+    // log-sum-exp of the teacher's rows, then of the student's (the partials of one are merged before the other's are written)
+    // (Eval = Es in both: the wave count of the sweeps that will read these statistics)
+    a.res = tq; a.ldres = ldtq; a.nres = nq; a.str = tk; a.ldstr = ldtk; a.nstr = nk; a.E = Et; a.Eval = Es; a.logit_scale = teacher_logit_scale;
+    set_splits(a, CE_INFONCE_MAX_SPLITS);
+    launch_head<MODE_FWD, LOSS_DISTILL>(a, s);
+    CE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lse_merge_kernel, dim3(ce_div_up(nq, 256)), dim3(256), 0, s, (const float*)workspace, a.splits, nq, lse_t);
+    CE_LAUNCH_CHECK();
+    a.res = q; a.ldres = ldq; a.str = k; a.ldstr = ldk; a.E = Es; a.logit_scale = logit_scale;
+    launch_head<MODE_FWD, LOSS_DISTILL>(a, s);
+    CE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lse_merge_kernel, dim3(ce_div_up(nq, 256)), dim3(256), 0, s, (const float*)workspace, a.splits, nq, lse_s);
+    CE_LAUNCH_CHECK();
+    // v[r] += sum_c softmax(T)[r,c] k^_c: the teacher's similarity, the student's keys as values, c = 1, written unscaled
+    a.res = tq; a.ldres = ldtq; a.str = tk; a.ldstr = ldtk; a.E = Et; a.logit_scale = teacher_logit_scale;
+    // the same sweep leaves <q^_r, its share of v_r> per split in the workspace: the loss does not depend on the atomics' order
+    a.lse = lse_t; a.val = k; a.ldval = ldk; a.Eval = Es; a.csign = 1.f; a.dres = v; a.dot = q; a.lddot = ldq;
+    set_splits(a, CE_INFONCE_MAX_SPLITS);
+    launch_head<MODE_DQ, LOSS_DISTILL>(a, s);
+    CE_LAUNCH_CHECK();
+    // the rows' terms, then their sum in index order: no float atomic on the loss
+    float* term = (float*)workspace + (size_t)CE_INFONCE_MAX_SPLITS * nq;
+    hipLaunchKernelGGL(distill_row_term_kernel, dim3(ce_div_up(nq, 256)), dim3(256), 0, s, (const float*)workspace, a.splits,
+                       (const float*)lse_s, logit_scale, nq, term);
+    CE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sigmoid_loss_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)term, nq, nq, loss);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_distill_head_bwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int Es,
+                                   const float* logit_scale, const float* tq, long ldtq, const float* tk, long ldtk, int Et,
+                                   const float* teacher_logit_scale, const float* lse_s, const float* lse_t, const float* v,
+                                   const float* grad, float* dq, float* dk, void* stream) {
+    if (int rc = check_distill("ce_distill_head_bwd", q, ldq, nq, k, ldk, nk, Es, logit_scale, tq, ldtq, tk, ldtk, Et,
+                               teacher_logit_scale))
+        return rc;
+    CE_CHECK_ARG(lse_s && lse_t && v && grad && dq && dk, "ce_distill_head_bwd: null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    HeadArgs a{};
+    a.sel = (const long*)sel; a.nq = nq; a.grad = grad; a.out_logit_scale = logit_scale; a.Eval = Es;
+    // dq[sel[r]] += (g/nq) s (sum_c P_s k^_c - v_r): student similarity, resident = queries; the first split's write takes v off
+    a.res = q; a.ldres = ldq; a.nres = nq; a.str = k; a.ldstr = ldk; a.nstr = nk; a.E = Es; a.logit_scale = logit_scale;
+    a.lse = lse_s; a.val = k; a.ldval = ldk; a.csign = 1.f; a.dres = dq; a.osel = (const long*)sel; a.sub = v;
+    set_splits(a, 1 << 20);
+    launch_head<MODE_DQ, LOSS_DISTILL>(a, s);
+    CE_LAUNCH_CHECK();
+    // dk[c] += (g/nq) s sum_r P_s q^_r: student similarity, resident = keys
+    a.res = k; a.ldres = ldk; a.nres = nk; a.str = q; a.ldstr = ldq; a.nstr = nq; a.val = q; a.ldval = ldq; a.dres = dk;
+    a.osel = nullptr; a.sub = nullptr;
+    set_splits(a, 1 << 20);
+    launch_head<MODE_DK, LOSS_DISTILL>(a, s);
+    CE_LAUNCH_CHECK();
+    // dk[c] -= (g/nq) s sum_r P_t q^_r: the TEACHER's similarity, the student's queries as values, the student's scale at the write
+    a.res = tk; a.ldres = ldtk; a.str = tq; a.ldstr = ldtq; a.E = Et; a.logit_scale = teacher_logit_scale; a.lse = lse_t;
+    a.csign = -1.f;
+    launch_head<MODE_DK, LOSS_DISTILL>(a, s);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_rowdot_sum(const float* x, long ldx, const float* y, long ldy, int n, int E, float* out, void* stream) {
+    CE_CHECK_ARG(x && y && out, "ce_rowdot_sum: null buffer");
+    CE_CHECK_ARG(n > 0 && E > 0 && ldx >= E && ldy >= E, "ce_rowdot_sum: bad shape");
+    int blocks = ce_div_up(n, 4);
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(rowdot_sum_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, n, E, out);
     CE_LAUNCH_CHECK();
     return 0;
 }

@@ -17,9 +17,9 @@ import numpy as np
 import torch
 
 from . import distributed as D
-from .functional import (attach_lengths, fused_contrastive_losses, fused_head_ok, logits_from_features, sigmoid_contrastive_losses,
-                         small_contrastive_losses, small_head_ok, tokens_to_device)
-from .losses import CriterionAlignment, CriterionContrastive
+from .functional import (attach_lengths, distill_losses, fused_contrastive_losses, fused_head_ok, logits_from_features,
+                         sigmoid_contrastive_losses, small_contrastive_losses, small_head_ok, tokens_to_device)
+from .losses import CriterionAlignment, CriterionContrastive, CriterionDistill
 
 
 def _unwrap(model):
@@ -27,9 +27,132 @@ def _unwrap(model):
     return model.module if isinstance(model, D.DistributedDataParallel) else model
 
 
-def _contrastive_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch):
+class Distillation:
+    """Knowledge distillation from a frozen teacher (open_clip's ``--distill-model`` / ``DistillClipLoss``): ``train_step(...,
+    distill=Distillation(teacher))`` adds ``weight`` times the cross entropy of the student's softmax against the teacher's, in
+    both directions, as ``loss_dist_i`` / ``loss_dist_t``.
+
+    ``teacher`` is this package's ``CLIP`` on the student's device; it is put in ``eval()`` with ``requires_grad_(False)`` and
+    encodes under ``torch.no_grad()`` (the stash-free towers), every patch of every image.  ``logit_scale`` (the LOG of the scale,
+    as ``CLIP.logit_scale`` holds it) replaces the teacher's own; with ``teacher=None`` it is required and every step needs
+    ``teacher_features=`` (precomputed features)."""
+
+    def __init__(self, teacher, weight: float = 1.0, logit_scale=None):
+        from .model import CLIP
+        if not float(weight) >= 0:
+            raise ValueError(f"Distillation: weight must be >= 0 (got {weight})")
+        if teacher is None:
+            if logit_scale is None:
+                raise ValueError("Distillation(teacher=None) is for precomputed teacher features and needs the teacher's logit_scale")
+        else:
+            if not isinstance(teacher, CLIP):
+                raise TypeError(f"Distillation: the teacher must be clip_event_amd's CLIP (got {type(teacher).__name__})")
+            if float(getattr(teacher.visual, "patch_dropout", 0.0)) > 0.0:
+                raise ValueError("Distillation: the teacher has patch dropout switched on (set_patch_dropout(0.0)): it must see "
+                                 "every patch")
+            teacher.eval()
+            teacher.requires_grad_(False)
+        self.teacher = teacher
+        self.weight = float(weight)
+        self._logit_scale = None if logit_scale is None else torch.as_tensor(float(logit_scale), dtype=torch.float32)
+
+    def logit_scale(self, device) -> torch.Tensor:
+        ls = self.teacher.logit_scale.detach() if self._logit_scale is None else self._logit_scale
+        return ls.to(device=device, dtype=torch.float32)
+
+    def check_optimizer(self, optimizer):
+        """A teacher the optimiser would update is no teacher: raises when any of its parameters is in ``optimizer``."""
+        if self.teacher is None:
+            return
+        if getattr(optimizer, "model", None) is self.teacher:
+            raise ValueError("Distillation: the optimiser was built on the teacher")
+        mine = {id(p) for p in self.teacher.parameters()}
+        for group in getattr(optimizer, "param_groups", []):
+            if any(id(p) in mine for p in group["params"] if isinstance(p, torch.Tensor)):
+                raise ValueError("Distillation: a parameter of the teacher is in the optimiser's parameter list")
+
+    def check_student(self, model):
+        if self.teacher is None:
+            return
+        if self.teacher is model:
+            raise ValueError("Distillation: the teacher is the student")
+        dev, tdev = next(model.parameters()).device, next(self.teacher.parameters()).device
+        if dev != tdev:
+            raise ValueError(f"Distillation: the teacher is on {tdev}, the student on {dev}")
+
+    def encode(self, image, text, teacher_image=None):
+        """The teacher's (image, text) features of a batch, no gradient, no stash."""
+        t = self.teacher
+        if t is None:
+            raise ValueError("Distillation(teacher=None) holds no teacher: pass teacher_features=(image features, text features)")
+        img = image if teacher_image is None else teacher_image
+        res = int(t.visual.input_resolution)
+        if tuple(img.shape[-2:]) != (res, res):
+            which = "teacher_image" if teacher_image is not None else "image"
+            raise ValueError(f"Distillation: the teacher takes {res} x {res} images and {which} is {tuple(img.shape[-2:])}; "
+                             f"pass teacher_image= at the teacher's resolution")
+        if img.shape[0] != image.shape[0]:
+            raise ValueError(f"Distillation: teacher_image has {img.shape[0]} images, the batch {image.shape[0]}")
+        if t.training:
+            t.eval()
+        with torch.no_grad():
+            tfi, tft = t.encode_both(img, text)
+        return tfi, tft
+
+
+# Logits per direction from which distillation runs on the fused head.  Measured (DESIGN 4h "Numbers"), the fused head is the
+# slower one at every size up to 4096 x 20480 (1.1-1.9 x logits + CriterionDistill): there is no crossover in speed, so the switch
+# is by memory.  At 2^28 logits one fp32 matrix is 1 GiB and the materialised path holds four of them and two gradients of that
+# size, 6 GiB on the stretch where both towers' stashes are alive; from there the fused head, which holds none, takes over.
+# CE_FUSED_HEAD=1 / 0 forces either.
+DISTILL_FUSED_MIN_LOGITS = 1 << 28
+
+
+def _distill_from_features(model, distill, fi, ft, tfi, tft, index_pos, pair):
+    """``weight`` x the two distillation terms from the student's and the teacher's raw features.  ``pair``: the student's
+    gathered (image, text) features when a process group is live (the queries are the local rows; the teacher's features are
+    gathered here, without grad, in one collective), else None.  Logits + ``CriterionDistill`` below ``DISTILL_FUSED_MIN_LOGITS``
+    logits per direction or where the fused head does not take a width, the fused head above; CE_FUSED_HEAD=1 / 0 forces either."""
+    if not model.constrastive_overbatch:
+        raise RuntimeError("distillation needs constrastive_overbatch=True: the per-instance layout has no distribution over the batch")
+    tls = distill.logit_scale(fi.device)
+    if pair is None:
+        fi_all, ft_all, tfi_all, tft_all = fi, ft, tfi, tft
+    else:
+        fi_all, ft_all = pair
+        with torch.no_grad():
+            tfi_all, tft_all = D.gather_feature_pair(tfi.float().contiguous(), tft.float().contiguous())
+    force = os.environ.get("CE_FUSED_HEAD", "")
+    logits = int(fi.shape[0]) * int(ft_all.shape[0])
+    if (force != "0" and (force == "1" or logits >= DISTILL_FUSED_MIN_LOGITS) and fused_head_ok(int(fi.shape[1]))
+            and fused_head_ok(int(tfi.shape[1]))):
+        out = distill_losses(fi, ft, fi_all, ft_all, model.logit_scale, tfi, tft, tfi_all, tft_all, tls, index_pos)
+    else:
+        with torch.no_grad():                                                     # the teacher's side is a constant
+            tlpi, _ = logits_from_features(tfi, tft_all, tls, True, want="image")
+            _, tlpt = logits_from_features(tfi_all, tft, tls, True, want="text")
+        lpi, _ = logits_from_features(fi, ft_all, model.logit_scale, True, want="image")
+        _, lpt = logits_from_features(fi_all, ft, model.logit_scale, True, want="text")
+        out = CriterionDistill()(lpi, lpt, tlpi, tlpt, index_pos=index_pos)
+    return {k: v * distill.weight for k, v in out.items()}
+
+
+def _contrastive_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch, teacher=None):
     """Loss dict of the contrastive criterion from the two towers' (raw) features: all-gather over the ranks when a
-    process group is live, then the fused head (no logits matrix in HBM) or logits + criterion."""
+    process group is live, then the fused head (no logits matrix in HBM) or logits + criterion.  ``teacher`` =
+    (``Distillation``, teacher image features, teacher text features) adds the distillation terms, computed from the features
+    alone; None leaves every launch what it is without it."""
+    if teacher is not None:
+        distill, tfi, tft = teacher
+        pair = D.gather_feature_pair(fi, ft) if (D.active() and global_batch) else None
+        loss_dict = _criterion_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch, pair)
+        loss_dict.update(_distill_from_features(model, distill, fi, ft, tfi, tft, index_pos, pair))
+        return loss_dict
+    return _criterion_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch, None)
+
+
+def _criterion_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch, pair):
+    """``pair``: the gathered (image, text) features when the caller has them already, else None."""
     # fused head: the 'ce' criterion over the batch, SURVEY 8(a) a6.  It exists to keep a big logits matrix out of HBM (config
     # 3 per rank: 512 x 20,480); at B = 256, K = 1 the matrix is 256 KB and the plain path's kernels are the faster ones
     # (same-box A/B: 12.75 / 12.53 vs 12.79 / 12.67 ms/step), so the fused head takes over from 2^17 logits per direction (256 x
@@ -37,7 +160,7 @@ def _contrastive_from_features(model, criterion, fi, ft, labels_per_image, label
     force = os.environ.get("CE_FUSED_HEAD", "")
     dist_global = D.active() and global_batch
     if getattr(criterion, "kind", None) == "sigmoid":
-        return _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_global)
+        return _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_global, None if pair is None else pair[1])
     logits = int(fi.shape[0]) * int(ft.shape[0]) * (D.world_size() if dist_global else 1)
     fused = (force != "0" and (force == "1" or logits >= (1 << 17)) and getattr(criterion, "kind", None) == "ce"
              and model.constrastive_overbatch and fused_head_ok(model.embed_dim))
@@ -46,7 +169,7 @@ def _contrastive_from_features(model, criterion, fi, ft, labels_per_image, label
             and getattr(criterion, "kind", None) == "ce" and model.constrastive_overbatch and index_pos is not None
             and small_head_ok(fi, ft, index_pos)):
         return small_contrastive_losses(fi, ft, model.logit_scale, labels_per_image, labels_per_text, index_pos)
-    fi_all, ft_all = D.gather_feature_pair(fi, ft) if dist_global else (fi, ft)
+    fi_all, ft_all = pair if pair is not None else (D.gather_feature_pair(fi, ft) if dist_global else (fi, ft))
     if fused:
         return fused_contrastive_losses(fi, ft, fi_all, ft_all, model.logit_scale, labels_per_image, labels_per_text, index_pos)
     overbatch = model.constrastive_overbatch
@@ -58,7 +181,7 @@ def _contrastive_from_features(model, criterion, fi, ft, labels_per_image, label
     return criterion(lpi, lpt, labels_per_image, labels_per_text, index_pos=index_pos, constrastive_overbatch=overbatch)
 
 
-def _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_global):
+def _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_global, ft_all=None):
     """``CriterionSigmoid``: the local images against all texts, one direction.  Across ranks only the TEXT features are gathered
     (half of ``gather_feature_pair``'s bytes): the rank's loss is over its own rows, DDP's mean over the ranks makes it the global
     loss, and the reduce-scatter in the gather's backward brings the other ranks' text gradients home.  The fused head (three
@@ -70,7 +193,8 @@ def _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_glob
     bias = getattr(model, "logit_bias", None)
     if bias is None:
         raise RuntimeError("the sigmoid loss needs a logit bias: call model.enable_logit_bias() before building the optimiser")
-    ft_all = D.gather_features(ft) if dist_global else ft
+    if ft_all is None:
+        ft_all = D.gather_features(ft) if dist_global else ft
     if os.environ.get("CE_FUSED_HEAD", "") != "0" and fused_head_ok(model.embed_dim):
         return sigmoid_contrastive_losses(fi, ft_all, model.logit_scale, bias, labels_per_image)
     lpi, _ = logits_from_features(fi, ft_all, model.logit_scale, True, want="image")
@@ -79,7 +203,7 @@ def _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_glob
 
 def contrastive_step_losses(model, criterion: CriterionContrastive, image, text, labels_per_image, labels_per_text,
                             index_pos, global_batch: bool = True, train_arg=None, bboxs=None, bbox_desc_vec=None,
-                            bbox_label_vec=None) -> Dict[str, torch.Tensor]:
+                            bbox_label_vec=None, teacher=None) -> Dict[str, torch.Tensor]:
     """Forward + criterion.  ``global_batch`` (W > 1): logits_per_image = s * I_local @ T_all^T,
     logits_per_text = s * T_local @ I_all^T with labels from ``distributed.global_labels``.  With ``train_arg``
     (model_clip.py:419-488) the two region / argument losses join the dict as ``loss_bbox`` / ``loss_arg``; they
@@ -91,7 +215,8 @@ def contrastive_step_losses(model, criterion: CriterionContrastive, image, text,
     else:
         fi, ft, loss_bbox, loss_arg = model.encode_with_regions(image, text, train_arg, bboxs, bbox_desc_vec, bbox_label_vec)
         extra = {"loss_bbox": loss_bbox, "loss_arg": loss_arg}
-    loss_dict = _contrastive_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch)
+    loss_dict = _contrastive_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch,
+                                           teacher=teacher)
     loss_dict.update(extra)
     return loss_dict
 
@@ -134,7 +259,7 @@ def _cat_tokens(parts):
 
 def merged_step_losses(model, criterion, criterion_ot, image, text, labels_per_image, labels_per_text, index_pos,
                        train_arg=None, bboxs=None, bbox_desc_vec=None, bbox_label_vec=None, object_vec=None,
-                       entitytxt_vec=None, object_num=None, entitytxt_num=None, global_batch: bool = True):
+                       entitytxt_vec=None, object_num=None, entitytxt_num=None, global_batch: bool = True, teacher=None):
     """BASELINE config 4's forward with ONE pass per tower.  The reference (and ``CLIP.forward`` / ``sim_entity`` here) runs
     the image tower twice (batch, object crops: engine.py:57-63) and the text tower up to four times (captions, entity
     mentions, role descriptions, role labels: model_clip.py:430-455, :531-552).  Tower rows are independent of each other,
@@ -142,7 +267,8 @@ def merged_step_losses(model, criterion, criterion_ot, image, text, labels_per_i
     labels]: a 64-image pass fills a quarter of the GPU and a 100-caption pass is ~200 launches of a few microseconds each,
     while the merged passes fill their tiles, and each tower's weight gradients are written once instead of accumulated.
     With ``train_arg`` the image pass keeps every token (the region branch pools the grid of the batch images; the crops'
-    CLS features are row 0 of theirs)."""
+    CLS features are row 0 of theirs).  ``teacher`` (as in ``_contrastive_from_features``) holds the teacher's features of the
+    image and caption rows only: the region and alignment branches are not distilled."""
     from .region import region_losses_from_features, region_plan
     dev = image.device
     B = image.shape[0]
@@ -176,7 +302,8 @@ def merged_step_losses(model, criterion, criterion_ot, image, text, labels_per_i
         obj_f = fi_all[B:, 0, :]
     else:
         fi, grid, obj_f = fi_all[:B], None, fi_all[B:]
-    loss_dict.update(_contrastive_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch))
+    loss_dict.update(_contrastive_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch,
+                                                teacher=teacher))
     ent_f = None
     if want_align:
         ent_f = ft_all[pos:pos + B * n_ent].view(B, n_ent, -1)
@@ -212,7 +339,8 @@ def _sum_losses(loss_dict, check_finite: bool):
 
 def micro_batched_backward(model, criterion, image, text, labels_per_image, labels_per_text, index_pos, micro_batch: int,
                            grad_sync: Optional[D.GradSync] = None, check_finite: bool = False,
-                           global_batch: bool = True) -> Dict[str, torch.Tensor]:
+                           global_batch: bool = True, distill=None, teacher_image=None,
+                           teacher_features=None) -> Dict[str, torch.Tensor]:
     """Forward + backward of the plain contrastive step for a batch whose activation stash does not fit: the stash is
     32-36 x width bytes per row AND block (0.45 GB per ViT-L/14@336 image), and the contrastive loss needs the features of
     the WHOLE batch, so accumulating the gradients of small steps would be a different loss.  Instead:
@@ -227,7 +355,10 @@ def micro_batched_backward(model, criterion, image, text, labels_per_image, labe
 
     The towers treat rows independently, so the cut needs no knowledge of the label layout, and the loss dict is the
     unchunked step's up to what a different tile choice at a smaller M does to the bf16 roundings.  Costs one extra tower
-    forward: 4/3 of the unchunked step's tower FLOPs.  The caller has zeroed the gradients and runs the optimiser."""
+    forward: 4/3 of the unchunked step's tower FLOPs.  The caller has zeroed the gradients and runs the optimiser.
+
+    With ``distill`` the teacher encodes each chunk in pass 1 (``teacher_features`` given: no teacher pass); the head, the
+    distillation terms included, still runs once over the whole batch."""
     B, n = int(image.shape[0]), int(text.shape[0])
     mb = int(micro_batch)
     if mb < 1:
@@ -266,10 +397,18 @@ def micro_batched_backward(model, criterion, image, text, labels_per_image, labe
             for lo, _, img_c, txt_c in chunks:
                 with pinned(lo):
                     feats.append(model.encode_both(img_c, txt_c))
+            teacher = None
+            if distill is not None:
+                if teacher_features is None:
+                    tf = [distill.encode(img_c, txt_c, None if teacher_image is None else teacher_image[lo:hi])
+                          for lo, hi, img_c, txt_c in chunks]
+                    teacher_features = (torch.cat([f[0] for f in tf], dim=0), torch.cat([f[1] for f in tf], dim=0))
+                teacher = (distill, teacher_features[0], teacher_features[1])
         fi = torch.cat([f[0] for f in feats], dim=0).requires_grad_(not locked["visual"])
         ft = torch.cat([f[1] for f in feats], dim=0).requires_grad_(not locked["text"])
         del feats
-        loss_dict = _contrastive_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch)
+        loss_dict = _contrastive_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch,
+                                               teacher=teacher)
         _sum_losses(loss_dict, check_finite).backward()        # fi.grad, ft.grad, logit_scale.grad; no tower node, no exchange
         for lo, hi, img_c, txt_c in (chunks if live else []):
             if len(live) == 2:
@@ -293,7 +432,8 @@ def train_step(model, criterion, optimizer, image, text, labels_per_image, label
                grad_sync: Optional[D.GradSync] = None, criterion_ot: Optional[CriterionAlignment] = None,
                object_vec=None, entitytxt_vec=None, object_num=None, entitytxt_num=None,
                check_finite: bool = False, train_arg=None, bboxs=None, bbox_desc_vec=None,
-               bbox_label_vec=None, text_lengths=None, micro_batch: Optional[int] = None) -> Dict[str, torch.Tensor]:
+               bbox_label_vec=None, text_lengths=None, micro_batch: Optional[int] = None, distill: Optional[Distillation] = None,
+               teacher_image=None, teacher_features=None) -> Dict[str, torch.Tensor]:
     """One iteration of engine.py:48-95.  BASELINE config 4 is this call with ``criterion_ot`` + the object / entity
     tensors (``model.alignment``) and ``train_arg`` + boxes in ONE step, as the reference's forward takes them
     (model_clip.py:419-528, engine.py:57-63).  ``check_finite`` reproduces engine.py:70-81 (all-rank mean of the
@@ -308,7 +448,11 @@ def train_step(model, criterion, optimizer, image, text, labels_per_image, label
 
     ``micro_batch`` (images per chunk; None or >= the number of images: the step above, untouched) runs the plain contrastive
     step for a batch whose activation stash does not fit the card: see ``micro_batched_backward``.  Same loss over the whole
-    batch, one extra tower forward.  Not available with ``train_arg`` / ``criterion_ot``."""
+    batch, one extra tower forward.  Not available with ``train_arg`` / ``criterion_ot``.
+
+    ``distill`` (a ``Distillation``) adds ``loss_dist_i`` / ``loss_dist_t``: the teacher encodes ``teacher_image`` (None: ``image``,
+    which must then have the teacher's resolution) and the captions without grad, or ``teacher_features=(image features, text
+    features)`` are taken as given and no teacher pass runs.  With ``distill=None`` the step is what it is without the argument."""
     wrapped = model
     model = _unwrap(model)
     chunked = micro_batch is not None and int(micro_batch) < int(image.shape[0])
@@ -325,6 +469,16 @@ def train_step(model, criterion, optimizer, image, text, labels_per_image, label
         entitytxt_vec = tokens_to_device(entitytxt_vec, dev)
     if grad_sync is None and wrapped is not model:
         grad_sync = wrapped.grad_sync
+    teacher = None                         # checked, and the teacher run, before anything of the step is touched
+    if distill is not None:
+        distill.check_student(model)
+        distill.check_optimizer(optimizer)
+        if teacher_features is not None:
+            teacher = (distill, teacher_features[0], teacher_features[1])
+        elif not chunked:
+            teacher = (distill,) + tuple(distill.encode(image, text, teacher_image))
+    elif teacher_image is not None or teacher_features is not None:
+        raise ValueError("teacher_image / teacher_features need distill=Distillation(...)")
     if hasattr(optimizer, "zero_grad_first_touch"):
         optimizer.zero_grad_first_touch()      # nothing reads .grad between here and backward(): block weights are overwritten
     else:
@@ -332,17 +486,18 @@ def train_step(model, criterion, optimizer, image, text, labels_per_image, label
     want_align = model.alignment and criterion_ot is not None
     if chunked:
         loss_dict = micro_batched_backward(model, criterion, image, text, labels_per_image, labels_per_text, index_pos,
-                                           int(micro_batch), grad_sync=grad_sync, check_finite=check_finite)
+                                           int(micro_batch), grad_sync=grad_sync, check_finite=check_finite, distill=distill,
+                                           teacher_image=teacher_image, teacher_features=teacher_features)
     elif (want_align or train_arg is not None) and os.environ.get("CE_MERGE_PASSES", "1") != "0":
         # config 4: one pass per tower over [images | object crops] and [captions | entity mentions | role texts]
         loss_dict = merged_step_losses(model, criterion, criterion_ot if want_align else None, image, text, labels_per_image,
                                        labels_per_text, index_pos, train_arg=train_arg, bboxs=bboxs, bbox_desc_vec=bbox_desc_vec,
                                        bbox_label_vec=bbox_label_vec, object_vec=object_vec, entitytxt_vec=entitytxt_vec,
-                                       object_num=object_num, entitytxt_num=entitytxt_num)
+                                       object_num=object_num, entitytxt_num=entitytxt_num, teacher=teacher)
     else:
         loss_dict = contrastive_step_losses(model, criterion, image, text, labels_per_image, labels_per_text, index_pos,
                                             train_arg=train_arg, bboxs=bboxs, bbox_desc_vec=bbox_desc_vec,
-                                            bbox_label_vec=bbox_label_vec)
+                                            bbox_label_vec=bbox_label_vec, teacher=teacher)
         if want_align:
             image_features, text_features = model.sim_entity(object_vec, entitytxt_vec)       # engine.py:57-63
             loss_dict.update(criterion_ot(text_features, image_features, entitytxt_num, object_num))

@@ -804,3 +804,124 @@ class SigmoidHeadFn(torch.autograd.Function):
 def sigmoid_contrastive_losses(fi, ft_all, logit_scale, logit_bias, labels_per_image):
     """``CriterionSigmoid`` over the batch on raw features: the local images against all (gathered) texts, one direction."""
     return {"loss_sig": SigmoidHeadFn.apply(fi, ft_all, logit_scale, logit_bias, labels_per_image, None)}
+
+
+def _teacher_norm(t):
+    """A teacher's features as the distillation head reads them: fp32, L2-normalised, no gradient."""
+    return _l2norm(_f32(t.detach()))[0]
+
+
+def _rowdot_sum(x, y, out):
+    check(lib().ce_rowdot_sum(ptr(x), x.shape[1], ptr(y), y.shape[1], x.shape[0], x.shape[1], ptr(out), stream()), "ce_rowdot_sum")
+
+
+def _distill_fwd(q, sel, nq, k, ls, tq, tk, tls, loss, ws):
+    """One direction's forward on normalised matrices: (lse_s, lse_t, v) for the backward, the loss written into ``loss``."""
+    dev = q.device
+    stats = _empty((2, nq, 2), torch.float32, dev)                                         # lse_s | lse_t, each (max, log sum) per row
+    v = torch.zeros((nq, q.shape[1]), dtype=torch.float32, device=dev)                     # an accumulation target
+    check(lib().ce_distill_head_fwd(ptr(q), q.shape[1], ptr(sel), nq, ptr(k), k.shape[1], k.shape[0], q.shape[1], ptr(ls),
+                                    ptr(tq), tq.shape[1], ptr(tk), tk.shape[1], tq.shape[1], ptr(tls), ptr(stats[0]), ptr(stats[1]),
+                                    ptr(v), ptr(loss), ptr(ws), stream()), "ce_distill_head_fwd")
+    return stats, v
+
+
+def _distill_bwd(q, sel, nq, k, ls, tq, tk, tls, stats, v, g, dq, dk):
+    check(lib().ce_distill_head_bwd(ptr(q), q.shape[1], ptr(sel), nq, ptr(k), k.shape[1], k.shape[0], q.shape[1], ptr(ls),
+                                    ptr(tq), tq.shape[1], ptr(tk), tk.shape[1], tq.shape[1], ptr(tls), ptr(stats[0]), ptr(stats[1]),
+                                    ptr(v), ptr(g), ptr(dq), ptr(dk), stream()), "ce_distill_head_bwd")
+
+
+def _check_teacher(what, s, t):
+    if t.dim() != 2 or t.shape[0] != s.shape[0]:
+        raise RuntimeError(f"distillation: teacher {what} features {tuple(t.shape)} do not match the student's {tuple(s.shape)} row for row")
+
+
+class DistillHeadFn(torch.autograd.Function):
+    """Distillation loss of one direction (open_clip's ``DistillClipLoss.dist_loss``),
+    -(softmax(st tq^ tk^T) * log_softmax(s q^ k^T)).sum(1).mean() over the query rows ``sel`` of ``q`` against all rows of ``k``,
+    without either logits matrix (``ce_distill_head_fwd/bwd``).  ``tq`` / ``tk`` are the teacher's features for the same rows as
+    ``q`` / ``k`` (any width the head takes) and ``teacher_logit_scale`` its log scale: constants.  This is the form for keys
+    gathered across ranks.  Gradients for ``q``, ``k`` and ``logit_scale``; the latter is sum_r <q^_r, dq^_r>
+    (``ce_rowdot_sum`` over the gradient buffer this node owns)."""
+
+    @staticmethod
+    def forward(ctx, q, k, logit_scale, tq, tk, teacher_logit_scale, sel):
+        dev = q.device
+        _check_teacher("query", q, tq)
+        _check_teacher("key", k, tk)
+        q, k = _f32(q), _f32(k)
+        qn, inv_q = _l2norm(q)
+        kn, inv_k = _l2norm(k)
+        tqn, tkn = _teacher_norm(tq), _teacher_norm(tk)
+        sel = _index64(sel, dev)
+        nq = q.shape[0] if sel is None else sel.shape[0]
+        ls, tls = logit_scale.detach().reshape(1), teacher_logit_scale.detach().float().reshape(1).to(dev)
+        loss = _empty((), torch.float32, dev)
+        ws = _empty((lib().ce_distill_head_workspace_bytes(nq),), torch.uint8, dev)
+        stats, v = _distill_fwd(qn, sel, nq, kn, ls, tqn, tkn, tls, loss, ws)
+        ctx.saved = (qn, kn, inv_q, inv_k, ls, tqn, tkn, tls, sel, stats, v)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        qn, kn, inv_q, inv_k, ls, tqn, tkn, tls, sel, stats, v = ctx.saved
+        nq = qn.shape[0] if sel is None else sel.shape[0]
+        g = g.contiguous().float().reshape(1)
+        acc = torch.zeros(qn.numel() + kn.numel() + 4, dtype=torch.float32, device=qn.device)     # dqn | dkn | dscale: one fill
+        dqn, dkn, dls = acc[:qn.numel()].view_as(qn), acc[qn.numel():qn.numel() + kn.numel()].view_as(kn), acc[qn.numel() + kn.numel():]
+        _distill_bwd(qn, sel, nq, kn, ls, tqn, tkn, tls, stats, v, g, dqn, dkn)
+        _rowdot_sum(qn, dqn, dls)
+        return _l2norm_bwd(dqn, qn, inv_q), _l2norm_bwd(dkn, kn, inv_k), dls[0].reshape(()), None, None, None, None
+
+
+class DistillPairFn(torch.autograd.Function):
+    """Both directions of the distillation loss on ONE pair of feature matrices, as ``InfoNCEPairFn``: loss_dist_i over the
+    images against all texts, loss_dist_t over the ``sel`` text rows against all images.  Each matrix is normalised once, both
+    directions add into one gradient buffer per matrix, one ``ce_l2norm_bwd`` each; sum <I^, dI^> over the accumulated image
+    buffer is the ``logit_scale`` gradient of both directions at once (queries of one, keys of the other)."""
+
+    @staticmethod
+    def forward(ctx, fi, ft, logit_scale, tfi, tft, teacher_logit_scale, sel):
+        dev = fi.device
+        _check_teacher("image", fi, tfi)
+        _check_teacher("text", ft, tft)
+        fi, ft = _f32(fi), _f32(ft)
+        In, inv_i = _l2norm(fi)
+        Tn, inv_t = _l2norm(ft)
+        tIn, tTn = _teacher_norm(tfi), _teacher_norm(tft)
+        sel = _index64(sel, dev)
+        nqi = fi.shape[0]
+        nqt = ft.shape[0] if sel is None else sel.shape[0]
+        ls, tls = logit_scale.detach().reshape(1), teacher_logit_scale.detach().float().reshape(1).to(dev)
+        losses = _empty((2,), torch.float32, dev)
+        ws = _empty((lib().ce_distill_head_workspace_bytes(max(nqi, nqt)),), torch.uint8, dev)
+        saved_i = _distill_fwd(In, None, nqi, Tn, ls, tIn, tTn, tls, losses[0:1], ws)
+        saved_t = _distill_fwd(Tn, sel, nqt, In, ls, tTn, tIn, tls, losses[1:2], ws)
+        ctx.saved = (In, Tn, inv_i, inv_t, ls, tIn, tTn, tls, sel, saved_i, saved_t)
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, g_i, g_t):
+        In, Tn, inv_i, inv_t, ls, tIn, tTn, tls, sel, saved_i, saved_t = ctx.saved
+        dev = In.device
+        nqi = In.shape[0]
+        nqt = Tn.shape[0] if sel is None else sel.shape[0]
+        zero = torch.zeros(2, dtype=torch.float32, device=dev)
+        g = torch.stack([zero[0] if g_i is None else g_i.float().reshape(()), zero[1] if g_t is None else g_t.float().reshape(())])
+        acc = torch.zeros(In.numel() + Tn.numel() + 4, dtype=torch.float32, device=dev)         # dIn | dTn | dlogit_scale: one fill
+        dIn, dTn, dls = acc[:In.numel()].view_as(In), acc[In.numel():In.numel() + Tn.numel()].view_as(Tn), acc[In.numel() + Tn.numel():]
+        _distill_bwd(In, None, nqi, Tn, ls, tIn, tTn, tls, *saved_i, g[0:1], dIn, dTn)
+        _distill_bwd(Tn, sel, nqt, In, ls, tTn, tIn, tls, *saved_t, g[1:2], dTn, dIn)
+        _rowdot_sum(In, dIn, dls)
+        return _l2norm_bwd(dIn, In, inv_i), _l2norm_bwd(dTn, Tn, inv_t), dls[0].reshape(()), None, None, None, None
+
+
+def distill_losses(fi, ft, fi_all, ft_all, logit_scale, tfi, tft, tfi_all, tft_all, teacher_logit_scale, index_pos):
+    """The two distillation terms on raw features, the logits never materialised: the local images against all texts and the
+    ``index_pos`` rows of the local texts against all images, student and teacher alike."""
+    if fi_all is fi and ft_all is ft:          # one process: one node for both directions
+        li, lt = DistillPairFn.apply(fi, ft, logit_scale, tfi, tft, teacher_logit_scale, index_pos)
+        return {"loss_dist_i": li, "loss_dist_t": lt}
+    return {"loss_dist_i": DistillHeadFn.apply(fi, ft_all, logit_scale, tfi, tft_all, teacher_logit_scale, None),
+            "loss_dist_t": DistillHeadFn.apply(ft, fi_all, logit_scale, tft, tfi_all, teacher_logit_scale, index_pos)}

@@ -123,6 +123,64 @@ class CriterionSigmoid(nn.Module):
         return {"loss_sig": _ElemLossFn.apply(logits_per_image + logit_bias, onehot, 0) * nk}
 
 
+class _SoftCrossEntropyFn(torch.autograd.Function):
+    """mean over the rows ``sel`` (or all rows) of lse(x_r) - sum_c softmax(t_r)_c x_r,c; ``teacher_logits`` is a constant."""
+
+    @staticmethod
+    def forward(ctx, logits, teacher_logits, sel):
+        if not logits.is_cuda:
+            raise RuntimeError("clip_event_amd losses run on the GPU only (no CPU fallback)")
+        if teacher_logits.shape != logits.shape:
+            raise RuntimeError(f"teacher logits {tuple(teacher_logits.shape)} must match the student's {tuple(logits.shape)}")
+        logits = logits if (logits.dtype == torch.float32 and logits.is_contiguous()) else logits.contiguous().float()
+        teacher = teacher_logits.detach().to(logits.device).contiguous().float()
+        if sel is not None:
+            sel = sel.to(device=logits.device, dtype=torch.int64).contiguous()
+        nrows = logits.shape[0] if sel is None else sel.shape[0]
+        lse = torch.empty(2, nrows, dtype=torch.float32, device=logits.device)
+        loss = torch.zeros((), dtype=torch.float32, device=logits.device)
+        check(lib().ce_soft_xent_fwd(ptr(logits), logits.stride(0), ptr(teacher), teacher.stride(0), ptr(sel), ptr(lse[0]),
+                                     ptr(lse[1]), ptr(loss), nrows, logits.shape[1], stream()), "ce_soft_xent_fwd")
+        ctx.saved = (logits, teacher, sel, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, teacher, sel, lse = ctx.saved
+        nrows = logits.shape[0] if sel is None else sel.shape[0]
+        d = torch.zeros_like(logits) if sel is not None else torch.empty_like(logits)
+        g = g.contiguous().float()
+        check(lib().ce_soft_xent_bwd(ptr(logits), logits.stride(0), ptr(teacher), teacher.stride(0), ptr(sel), ptr(lse[0]),
+                                     ptr(lse[1]), ptr(g), ptr(d), d.stride(0), nrows, logits.shape[1], stream()), "ce_soft_xent_bwd")
+        return d, None, None
+
+
+def soft_cross_entropy(logits, teacher_logits, sel=None):
+    return _SoftCrossEntropyFn.apply(logits, teacher_logits, sel)
+
+
+class CriterionDistill(nn.Module):
+    """The distillation terms of open_clip's ``DistillClipLoss`` on materialised logits: for each direction
+    -(softmax(teacher logits) * log_softmax(logits)).sum(1).mean(), the text direction over the ``index_pos`` rows, times
+    ``weight``.  The teacher's matrices are constants.  This is the general path, for embed dims the fused head
+    (``functional.DistillPairFn``) does not take, and its cross-check on the device; ``engine`` picks between them."""
+
+    kind = "distill"
+
+    def __init__(self, weight: float = 1.0):
+        super().__init__()
+        if not weight >= 0:
+            raise ValueError(f"distillation weight must be >= 0 (got {weight})")
+        self.weight = float(weight)
+
+    def forward(self, logits_per_image, logits_per_text, teacher_logits_per_image, teacher_logits_per_text, index_pos=None):
+        li = soft_cross_entropy(logits_per_image, teacher_logits_per_image)
+        lt = soft_cross_entropy(logits_per_text, teacher_logits_per_text, index_pos)
+        if self.weight != 1.0:
+            li, lt = li * self.weight, lt * self.weight
+        return {"loss_dist_i": li, "loss_dist_t": lt}
+
+
 class CriterionAlignment(nn.Module):
     """model_clip.py:664-715: IPOT optimal-transport distance between entity-text and object
     features (object slot 0 = whole image is dropped), summed over the batch, times 0.01."""

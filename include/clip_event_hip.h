@@ -314,6 +314,14 @@ int ce_xent_fwd(const float* logits, long ld, const int64_t* labels, const int64
                 float* loss, int nrows, int C, void* stream);
 int ce_xent_bwd(const float* logits, long ld, const int64_t* labels, const int64_t* sel, const float* row_lse,
                 const float* grad, float* dlogits, long ldd, int nrows, int C, void* stream);
+/* soft-target cross entropy over the selected rows: *loss += mean_r (lse(x_r) - sum_c softmax(t_r)_c x_r,c), x = logits,
+ * t = teacher_logits (a constant; same shape, own leading dimension); row_lse / row_lse_t [nrows] are kept for the backward,
+ * dlogits[src, c] = grad / nrows (softmax(x)_c - softmax(t)_c) (rows not selected untouched) */
+int ce_soft_xent_fwd(const float* logits, long ld, const float* teacher_logits, long ldt, const int64_t* sel, float* row_lse,
+                     float* row_lse_t, float* loss, int nrows, int C, void* stream);
+int ce_soft_xent_bwd(const float* logits, long ld, const float* teacher_logits, long ldt, const int64_t* sel,
+                     const float* row_lse, const float* row_lse_t, const float* grad, float* dlogits, long ldd, int nrows,
+                     int C, void* stream);
 int ce_dot(const float* a, const float* b, long n, float* out, void* stream);
 /* per-instance logits_per_image (model_clip.py:509-521): lpi[b,k] = exp(*logit_scale) <In[b], Tn[b*K+k]> */
 int ce_instance_logits(const float* In, const float* Tn, const float* logit_scale, float* lpi, int B, int K, int E,
@@ -538,6 +546,32 @@ int ce_sigmoid_head_fwd(const float* q, long ldq, const int64_t* sel, int nq, co
 int ce_sigmoid_head_bwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
                         const float* logit_scale, const float* logit_bias, const int64_t* labels, const float* grad, float* dq,
                         float* dk, float* dlogit_scale, float* dlogit_bias, void* stream);
+
+/* Distillation loss on the same sweep, one direction: cross entropy of the student's softmax against a teacher's, the
+ * logits of neither materialised.  q, k, sel, nq, nk as ce_infonce_fwd (student, width Es, s = exp(*logit_scale)); tq / tk are
+ * the teacher's L2-normalised features with the SAME row layout as q / k (query r = row sel[r] of tq), width Et (may differ
+ * from Es), st = exp(*teacher_logit_scale); the teacher is a constant.
+ *   S = s <q_r, k_c>, T = st <tq_r, tk_c>, loss = (1/nq) sum_r (lse_s[r] - sum_c softmax_c(T)[r,c] S[r,c])
+ *   fwd: lse_s, lse_t [nq][2] (each row's log-sum-exp as the pair (max, log sum): one float would not normalise a peaked softmax
+ *        closely enough) and v [nq, Es] = sum_c softmax_c(T)[r,c] k_c are written for the backward -- v is an accumulation
+ *        target and must be ZERO-FILLED by the caller; *loss is WRITTEN (row terms summed in index order: the same inputs
+ *        give the same bits); workspace = ce_distill_head_workspace_bytes(nq) bytes.
+ *   bwd: G = (*grad / nq)(softmax(S) - softmax(T)); dq[sel[r],:] += s sum_c G k_c, dk[c,:] += s sum_r G q_r (dense, pitch Es,
+ *        zero-filled or holding earlier contributions, as for ce_infonce_bwd).  The logit_scale gradient is not produced
+ *        here: sum G S = sum_r <q_r, dq_r> = sum_c <k_c, dk_c>, so ce_rowdot_sum over a feature matrix and the gradient
+ *        buffer this entry filled gives it -- for a pair of directions accumulated into one buffer, both at once.
+ * Es and Et multiples of 128 in 128..1024.  No allocation, no synchronisation. */
+size_t ce_distill_head_workspace_bytes(int nq);
+int ce_distill_head_fwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int Es,
+                        const float* logit_scale, const float* tq, long ldtq, const float* tk, long ldtk, int Et,
+                        const float* teacher_logit_scale, float* lse_s, float* lse_t, float* v, float* loss, void* workspace,
+                        void* stream);
+int ce_distill_head_bwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int Es,
+                        const float* logit_scale, const float* tq, long ldtq, const float* tk, long ldtk, int Et,
+                        const float* teacher_logit_scale, const float* lse_s, const float* lse_t, const float* v,
+                        const float* grad, float* dq, float* dk, void* stream);
+/* *out += sum_r <x_r, y_r> over n rows of E columns */
+int ce_rowdot_sum(const float* x, long ldx, const float* y, long ldy, int n, int E, float* out, void* stream);
 
 /* Scoring without the [nq, nk] logits matrix (retrieval.hip): best-k keys per query, log-sum-exp and the rank of one target,
  * on the similarity sweep of ce_infonce_fwd.  q [nq,E], keys [nk,E] are used as given (the caller normalises them:

@@ -6,7 +6,9 @@ and the spread (min .. max) of the samples are printed, and one JSON line at the
 
 Shapes (images x texts x embed dim): 256 x 256 x 512 (config 2), 512 x 2560 x 512 (B = 512, K = 5, one process) and
 4096 x 20480 x 512 (config 3's whole batch in one process: an 84 M-element logits matrix that neither head forms).
-``--logits`` adds the logits + criterion path of both losses where its matrix stays below 1 GB."""
+``--logits`` adds the logits + criterion path of both losses where its matrix stays below 1 GB.  ``--distill`` adds the
+distillation row: the fused distillation pair head (``DistillPairFn``, student width 512, teacher width 768) against logits +
+``CriterionDistill`` (four logits matrices) at all three shapes."""
 import argparse
 import json
 import os
@@ -16,8 +18,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from clip_event_amd.functional import InfoNCEPairFn, SigmoidHeadFn, logits_from_features
-from clip_event_amd.losses import CriterionContrastive, CriterionSigmoid
+from clip_event_amd.functional import DistillPairFn, InfoNCEPairFn, SigmoidHeadFn, logits_from_features
+from clip_event_amd.losses import CriterionContrastive, CriterionDistill, CriterionSigmoid
 
 DEV = "cuda:0"
 SHAPES = ((256, 256, 512), (512, 2560, 512), (4096, 20480, 512))
@@ -37,6 +39,8 @@ def main():
     ap.add_argument("--iters", type=int, default=30, help="timed samples per head and shape")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--logits", action="store_true", help="also time logits + criterion")
+    ap.add_argument("--distill", action="store_true", help="also time the distillation head, fused and on logits")
+    ap.add_argument("--teacher-dim", type=int, default=768)
     args = ap.parse_args()
     torch.manual_seed(0)
     results = []
@@ -70,6 +74,23 @@ def main():
                 (ld["loss_i"] + ld["loss_t"]).backward()
 
             heads.update(sigmoid_logits=sigmoid_logits, infonce_logits=infonce_logits)
+        if args.distill:
+            tfi = torch.randn(nq, args.teacher_dim, device=DEV)
+            tft = torch.randn(nk, args.teacher_dim, device=DEV)
+            tls = torch.tensor(4.605, device=DEV)
+            crit_d = CriterionDistill()
+
+            def distill():
+                li, lt = DistillPairFn.apply(fi, ft, ls, tfi, tft, tls, ip)
+                (li + lt).backward()
+
+            def distill_logits():
+                with torch.no_grad():
+                    tlpi, tlpt = logits_from_features(tfi, tft, tls, True)
+                ld = crit_d(*logits_from_features(fi, ft, ls, True), tlpi, tlpt, index_pos=ip)
+                (ld["loss_dist_i"] + ld["loss_dist_t"]).backward()
+
+            heads.update(distill=distill, distill_logits=distill_logits)
         for fn in heads.values():
             for _ in range(args.warmup):
                 fn()
@@ -82,10 +103,13 @@ def main():
         for name, ts in times.items():
             row[name] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
         row["sigmoid_over_infonce_pair"] = row["sigmoid"]["median_ms"] / row["infonce_pair"]["median_ms"]
+        if args.distill:
+            row["distill_over_distill_logits"] = row["distill"]["median_ms"] / row["distill_logits"]["median_ms"]
         results.append(row)
         print(f"{nq} x {nk} x {E}: " + "; ".join(f"{name} {r['median_ms']:.3f} ms ({r['min_ms']:.3f} .. {r['max_ms']:.3f})"
                                                  for name, r in row.items() if isinstance(r, dict))
-              + f"; sigmoid / InfoNCE pair {row['sigmoid_over_infonce_pair']:.2f}", flush=True)
+              + f"; sigmoid / InfoNCE pair {row['sigmoid_over_infonce_pair']:.2f}"
+              + (f"; distill fused / logits {row['distill_over_distill_logits']:.2f}" if args.distill else ""), flush=True)
         del fi, ft
     print(json.dumps({"bench": "head", "iters": args.iters, "results": results}))
 
