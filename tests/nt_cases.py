@@ -107,6 +107,8 @@ def _implied(got, want, bits):
     have been (half an ulp of got is allowed for; below a power of two the true allowance is half of that, so this can only
     understate)."""
     _, e = torch.frexp(got)
+    if bits == 11:
+        e = e.clamp_min(-13)            # fp16 subnormals are 2^-24 apart, whatever their own exponent
     half = torch.ldexp(torch.ones_like(got), e - bits - 1)
     return ((got - want).abs() - half).clamp_min(0.0)
 
