@@ -3,7 +3,9 @@
 Same file layout as ``save_model_on_master`` (engine.py:202-218): ``{'epoch', 'model', 'state_dict', 'perf',
 'optimizer'}`` written with ``torch.save`` as ``<task>_<epoch>.pth``; the ``state_dict`` has the reference's keys
 and shapes, ``optimizer`` is ``torch.optim.Adam``'s format (optim.FusedAdam speaks it) or ``torch.optim.SGD``'s
-(optim.FusedSGD: per-parameter ``momentum_buffer``, an empty state before the first step), so files move both ways.
+(optim.FusedSGD: per-parameter ``momentum_buffer``, an empty state before the first step), so files move both ways; with
+optim.FusedLion it is the layout of the common Lion implementations (timm, lion-pytorch): per-parameter ``exp_avg``, group keys
+``lr`` / ``betas`` / ``weight_decay``, an empty state before the first step.
 Loading follows train.py:101-124 (resume) and also accepts a bare state dict such as the OpenAI ViT-B/32 weights
 (fp16 tensors are widened to the fp32 masters by ``build_model``).  Files are read with ``weights_only=True``:
 nothing in a checkpoint is executed.

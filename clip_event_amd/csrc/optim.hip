@@ -96,6 +96,30 @@ __device__ __forceinline__ void sgd_elem(float& p, float g, float& buf, float co
     p = __builtin_fmaf(-lr, upd, p);
 }
 
+// One element of clip + Lion (Chen et al. 2023): c = b1 m + (1 - b1) g is formed from the OLD momentum, the master moves by exactly
+// lr against c's sign, and only then the momentum becomes b2 m + (1 - b2) g.  As adam_elem / sgd_elem: every kernel form updates
+// through this function -- here every product and sum is an instruction of its own (two products and one sum for c and for m, no
+// multiply-add) -- so that the flat, the tile and the segment kernel give the same bits.  `decay` = lr * weight_decay: always the
+// decoupled form, p <- p - decay p in front of the step, skipped when it is 0 (p - 0 * p is not p for p = -0).  The sign is
+// (c > 0) - (c < 0): 0 for c == 0, and 0 for a NaN c as well (both comparisons are false), so that a NaN gradient leaves the master
+// to the decay alone and shows in the momentum, which becomes NaN.  No bias correction, no step counter: zero momentum is the start.
+__device__ __forceinline__ void lion_elem(float& p, float g, float& m, float coef, float b1, float one_minus_b1, float b2,
+                                          float one_minus_b2, float lr, float decay) {
+#pragma clang fp contract(off)
+    g = g * coef;
+    const float mb1 = m * b1, gb1 = g * one_minus_b1;
+    const float c = mb1 + gb1;
+    const float u = (c > 0.f ? 1.0f : 0.f) - (c < 0.f ? 1.0f : 0.f);
+    if (decay != 0.f) {
+        const float dp = decay * p;
+        p = p - dp;
+    }
+    const float step = lr * u;
+    p = p - step;
+    const float mb2 = m * b2, gb2 = g * one_minus_b2;
+    m = mb2 + gb2;
+}
+
 // One element of the weight average, e <- e + rate (p_new - e) with rate = 1 - decay, in torch's lerp_ form: below a weight of 0.5
 // fma(p_new - e, rate, e), from 0.5 on p_new - (p_new - e) (1 - rate), so that rate 1 gives p_new itself (the branch is uniform
 // over the launch).  p_new is the fp32 master exactly as the rule just wrote it.  As adam_elem / sgd_elem: the subtraction and the
@@ -215,6 +239,48 @@ struct SgdGroupRule {
     }
     __device__ __forceinline__ void elem(float& p, float g, float (&s)[1]) const {
         sgd_elem(p, g, s[0], coef, wd, mu, one_minus_damp, lr, first, nesterov);
+    }
+};
+
+// Lion: one state stream, the streams of SGD with momentum (flat form: 12 B read + 10 B written per parameter).  1 - b1, 1 - b2 and
+// lr * weight_decay are rounded once here, in fp32.
+struct LionRule {
+    static constexpr int NS = 1;                   // the momentum (exp_avg)
+    static constexpr bool GROUPED = false;
+    struct Args {
+        const float* sumsq;
+        float max_norm, lr, b1, b2, wd;
+    };
+    float coef, b1, one_minus_b1, b2, one_minus_b2, lr, decay;
+    __device__ LionRule(const Args& a, int)
+        : coef(clip_coef(a.sumsq, a.max_norm)), b1(a.b1), one_minus_b1(1.0f - a.b1), b2(a.b2), one_minus_b2(1.0f - a.b2), lr(a.lr),
+          decay(a.lr * a.wd) {}
+    __device__ __forceinline__ void elem(float& p, float g, float (&s)[1]) const {
+        lion_elem(p, g, s[0], coef, b1, one_minus_b1, b2, one_minus_b2, lr, decay);
+    }
+};
+
+// lr and weight decay per group; ce_optim_group.decoupled is not read (Lion's decay is always decoupled)
+struct LionGroupRule {
+    static constexpr int NS = 1;
+    static constexpr bool GROUPED = true;
+    struct Args {
+        const float* sumsq;
+        float max_norm, b1, b2;
+        group_table groups;
+    };
+    float coef, b1, one_minus_b1, b2, one_minus_b2, lr, decay;
+    __device__ LionGroupRule(const Args& a, int group)
+        : coef(clip_coef(a.sumsq, a.max_norm)), b1(a.b1), one_minus_b1(1.0f - a.b1), b2(a.b2), one_minus_b2(1.0f - a.b2) {
+        set_group(a, group);
+    }
+    __device__ __forceinline__ void set_group(const Args& a, int group) {
+        const ce_optim_group gr = pick_group(a.groups, group);
+        lr = gr.lr;
+        decay = gr.lr * gr.weight_decay;
+    }
+    __device__ __forceinline__ void elem(float& p, float g, float (&s)[1]) const {
+        lion_elem(p, g, s[0], coef, b1, one_minus_b1, b2, one_minus_b2, lr, decay);
     }
 };
 
@@ -706,6 +772,63 @@ int sgd_step_groups(const char* who, float* p, const float* g, float* buf, void*
     return 0;
 }
 
+// what every Lion entry point asks of its momentum and its hyper-parameters (the grouped forms: of every group's lr / weight decay,
+// checked by lion_groups_check); 0 or -EINVAL with a message
+int lion_check(const char* who, const float* m, float beta1, float beta2) {
+    CE_CHECK_ARG(m, "%s: the momentum buffer m is NULL", who);
+    CE_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f, "%s: invalid beta1 value %g (outside [0, 1))", who, (double)beta1);
+    CE_CHECK_ARG(beta2 >= 0.f && beta2 < 1.f, "%s: invalid beta2 value %g (outside [0, 1))", who, (double)beta2);
+    return 0;
+}
+int lion_scalars_check(const char* who, float lr, float weight_decay) {
+    CE_CHECK_ARG(lr >= 0.f, "%s: invalid learning rate %g", who, (double)lr);
+    CE_CHECK_ARG(weight_decay >= 0.f, "%s: invalid weight_decay value %g", who, (double)weight_decay);
+    return 0;
+}
+
+int lion_step(const char* who, float* p, const float* g, float* m, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+              float beta1, float beta2, float weight_decay, float* ema, float ema_rate, void* stream) {
+    CE_CHECK_ARG(n > 0, "%s: need n>0", who);
+    if (int rc = lion_check(who, m, beta1, beta2)) return rc;
+    if (int rc = lion_scalars_check(who, lr, weight_decay)) return rc;
+    CE_CHECK_ARG(p && g, "%s: null buffer", who);
+    const LionRule::Args a = {sumsq, max_norm, lr, beta1, beta2, weight_decay};
+    launch_flat<LionRule>(p, g, m, nullptr, p_bf16, n, a, stream, ema, ema_rate);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+int lion_step_tiles(const char* who, float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                    int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
+                    float beta1, float beta2, float weight_decay, float* ema, float ema_rate, void* stream) {
+    if (int rc = lion_check(who, m, beta1, beta2)) return rc;
+    if (int rc = lion_scalars_check(who, lr, weight_decay)) return rc;
+    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
+    CE_CHECK_ARG(p && g && p_bf16, "%s: null buffer", who);
+    const LionRule::Args a = {sumsq, max_norm, lr, beta1, beta2, weight_decay};
+    launch_tiles<LionRule>(p, g, m, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream, ema,
+                           ema_rate);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+int lion_step_groups(const char* who, float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                     int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
+                     float max_norm, const ce_optim_group* groups, int ngroups, float beta1, float beta2, float* ema, float ema_rate,
+                     void* stream) {
+    if (int rc = lion_check(who, m, beta1, beta2)) return rc;
+    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
+    CE_CHECK_ARG(p && g && p_bf16, "%s: null buffer", who);
+    LionGroupRule::Args a = {sumsq, max_norm, beta1, beta2, {}};
+    if (int rc = fill_groups(who, a.groups, groups, ngroups, segment_group, true)) return rc;      // (`decoupled` is not read)
+    for (int i = 0; i < ngroups; ++i)
+        if (int rc = lion_scalars_check(who, groups[i].lr, groups[i].weight_decay)) return rc;
+    launch_tiles<LionGroupRule>(p, g, m, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream, ema,
+                                ema_rate);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int ce_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* sumsq,
@@ -806,6 +929,47 @@ extern "C" int ce_sgd_step_groups_ema(float* p, const float* g, float* buf, void
     return sgd_step_groups("ce_sgd_step_groups_ema", p, g, buf, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
                            segment_group, sumsq, max_norm, groups, ngroups, momentum, dampening, nesterov, first_step, ema, ema_rate,
                            stream);
+}
+
+extern "C" int ce_lion_step(float* p, const float* g, float* m, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+                            float beta1, float beta2, float weight_decay, void* stream) {
+    return lion_step("ce_lion_step", p, g, m, p_bf16, n, sumsq, max_norm, lr, beta1, beta2, weight_decay, nullptr, 0.f, stream);
+}
+extern "C" int ce_lion_step_ema(float* p, const float* g, float* m, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+                                float beta1, float beta2, float weight_decay, float* ema, float ema_rate, void* stream) {
+    if (int rc = ema_check("ce_lion_step_ema", ema, ema_rate)) return rc;
+    return lion_step("ce_lion_step_ema", p, g, m, p_bf16, n, sumsq, max_norm, lr, beta1, beta2, weight_decay, ema, ema_rate, stream);
+}
+
+extern "C" int ce_lion_step_tiles(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                                  int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm,
+                                  float lr, float beta1, float beta2, float weight_decay, void* stream) {
+    return lion_step_tiles("ce_lion_step_tiles", p, g, m, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, sumsq,
+                           max_norm, lr, beta1, beta2, weight_decay, nullptr, 0.f, stream);
+}
+extern "C" int ce_lion_step_tiles_ema(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                                      int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm,
+                                      float lr, float beta1, float beta2, float weight_decay, float* ema, float ema_rate,
+                                      void* stream) {
+    if (int rc = ema_check("ce_lion_step_tiles_ema", ema, ema_rate)) return rc;
+    return lion_step_tiles("ce_lion_step_tiles_ema", p, g, m, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                           sumsq, max_norm, lr, beta1, beta2, weight_decay, ema, ema_rate, stream);
+}
+
+extern "C" int ce_lion_step_groups(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                                   int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
+                                   const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float beta1,
+                                   float beta2, void* stream) {
+    return lion_step_groups("ce_lion_step_groups", p, g, m, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                            segment_group, sumsq, max_norm, groups, ngroups, beta1, beta2, nullptr, 0.f, stream);
+}
+extern "C" int ce_lion_step_groups_ema(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                                       int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
+                                       const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float beta1,
+                                       float beta2, float* ema, float ema_rate, void* stream) {
+    if (int rc = ema_check("ce_lion_step_groups_ema", ema, ema_rate)) return rc;
+    return lion_step_groups("ce_lion_step_groups_ema", p, g, m, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                            segment_group, sumsq, max_norm, groups, ngroups, beta1, beta2, ema, ema_rate, stream);
 }
 
 extern "C" int ce_swap_cast_bf16(float* a, float* b, void* a_bf16, long n, void* stream) {

@@ -1,4 +1,4 @@
-"""The optimiser side of the step: fused clip_grad_norm_(.,1) + Adam, or + SGD with momentum, over the
+"""The optimiser side of the step: fused clip_grad_norm_(.,1) + Adam, or + SGD with momentum, or + Lion, over the
 model's flat buffers (reference engine.py:87-95, build_optimizer engine.py:129-151) -- two HIP launches per step, no host
 synchronisation -- and the learning-rate schedules of utils.py:310-416 / build_lr_scheduler engine.py:154-176
 (host arithmetic: one float per step)."""
@@ -634,6 +634,100 @@ class FusedSGD(_FusedFlatOptimizer):
             self._has_buf = True
 
 
+class FusedLion(_FusedFlatOptimizer):
+    """Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms") preceded by the global-norm clip of
+    ``clip_grad_norm_(params, max_norm)``: ``c = b1 m + (1 - b1) g``, ``p <- p (1 - lr weight_decay) - lr sign(c)``, then
+    ``m <- b2 m + (1 - b2) g`` (include/clip_event_hip.h, ``ce_lion_step``, has the arithmetic rounding by rounding).  The weight
+    decay is always decoupled -- the update has magnitude ``lr`` whatever the gradient is, so a decay folded into the gradient
+    would only vote on the sign -- and there is no bias correction and no step counter: zero momentum is the initial state.
+    ``max_norm=None`` disables clipping.  The usual learning rate is a tenth to a third of Adam's, with the weight decay
+    raised by the same factor.
+
+    A real ``torch.optim.Optimizer`` like ``FusedAdam`` / ``FusedSGD``, with everything ``_FusedFlatOptimizer`` provides (tiles,
+    frozen ranges and parameter groups, weight EMA, first-touch zero-fill, the sharded step).  The momentum lives in ONE flat
+    buffer next to the flat parameters -- the streams and bytes of SGD with momentum.  ``state_dict()`` / ``load_state_dict()`` speak the
+    layout of the common Lion implementations (timm, lion-pytorch): per-parameter ``{"exp_avg": tensor}``, group keys ``lr`` /
+    ``betas`` / ``weight_decay``, an empty state before the first step."""
+
+    _flat_op, _tiles_op, _groups_op = "ce_lion_step", "ce_lion_step_tiles", "ce_lion_step_groups"
+    _stock = "a stock Lion (timm.optim.Lion, lion_pytorch.Lion)"
+
+    def __init__(self, model, lr: float = 1e-4, betas=(0.9, 0.99), weight_decay: float = 0.0, max_norm=1.0, groups=None):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        betas = tuple(betas)
+        if len(betas) != 2:
+            raise ValueError(f"Invalid betas: {betas} (need two)")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        for gi, g in enumerate(groups or ()):
+            if isinstance(g, dict) and (g.get("lr", 0.0) < 0.0 or g.get("weight_decay", 0.0) < 0.0):
+                raise ValueError(f"Invalid learning rate or weight_decay value in group {gi}")
+        self.exp_avg = None
+        self._has_state = False            # a step was taken or a momentum loaded: state_dict() has something to say
+        super().__init__(model, max_norm, dict(lr=lr, betas=betas, weight_decay=weight_decay), groups)
+
+    @property
+    def betas(self):
+        return self.param_groups[0]["betas"]
+
+    def _state(self):
+        m = self.model
+        m._ready()
+        flat = m._flat
+        if self.exp_avg is None or self.exp_avg.numel() != flat.numel() or self.exp_avg.device != flat.device:
+            self.exp_avg = torch.zeros_like(flat)
+            self.sumsq = torch.zeros(1, dtype=torch.float32, device=flat.device)
+            self._has_state = False
+
+    def state_buffers(self):
+        """``(exp_avg,)``: the one flat state tensor (what ``distributed.consolidate`` gathers after sharded steps)."""
+        self._state()
+        return (self.exp_avg,)
+
+    def _step_args(self, sumsq):
+        return (self.exp_avg,), (ptr(sumsq), self.max_norm or 0.0, float(self.lr), float(self.betas[0]), float(self.betas[1]),
+                                 float(self.weight_decay))
+
+    def _group_args(self, sumsq):
+        return (self.exp_avg,), (float(self.betas[0]), float(self.betas[1]))
+
+    def _after_step(self, sharded):
+        if sharded:
+            self._moments_stale = True     # the momentum stays sharded
+        self._has_state = True
+
+    def state_dict(self):
+        self._state()
+        self._refuse_sharded_state("Lion momentum is")
+        state = {}
+        if self._has_state:
+            state = {i: {"exp_avg": b.clone()} for i, b in enumerate(self._pieces(self.exp_avg))}
+        return self._state_dict_of(state)
+
+    def load_state_dict(self, sd):
+        self._moments_stale = False          # (every rank loads the same tensors)
+        group = self._matching_group(sd)
+        params = self._params()
+        bufs = {int(k): st["exp_avg"] for k, st in sd["state"].items() if st.get("exp_avg") is not None}
+        if bufs and len(bufs) != len(params):
+            raise ValueError("only %d of %d parameters carry an exp_avg; the fused kernel keeps one flat momentum for all of them"
+                             % (len(bufs), len(params)))
+        self._adopt_group(group)
+        self._state()
+        self.exp_avg.zero_()
+        self._has_state = False
+        if bufs:
+            with torch.no_grad():
+                for i, b in enumerate(self._pieces(self.exp_avg)):
+                    b.copy_(bufs[i].reshape(b.shape))
+            self._has_state = True
+
+
 def _warmup_factor_at(method: str, it: int, warmup_iters: int, warmup_factor: float) -> float:
     """utils.py:393-416: 1 after the warm-up; before it a constant, or a line from warmup_factor to 1."""
     if it >= warmup_iters:
@@ -679,7 +773,7 @@ class WarmupCosineLR(torch.optim.lr_scheduler._LRScheduler):
 
 
 def no_decay_groups(model, weight_decay: float):
-    """The usual fine-tuning split as ``groups`` for ``FusedAdam`` / ``FusedSGD``: gains, biases, every other tensor of one
+    """The usual fine-tuning split as ``groups`` for ``FusedAdam`` / ``FusedSGD`` / ``FusedLion``: gains, biases, every other tensor of one
     dimension or none, ``logit_scale`` and ``logit_bias`` get weight decay 0, the matrices (and embeddings) ``weight_decay``.  Trainable
     parameters only, by name."""
     decay, no_decay = [], []
@@ -691,7 +785,8 @@ def no_decay_groups(model, weight_decay: float):
 
 def build_optimizer(cfg: dict, model, fused: bool = True):
     """engine.py:129-151 (``cfg['optimizer']`` in {'sgd','adam'}); with ``fused`` both return the fused step, which also
-    performs engine.py:89's clip_grad_norm_(.,1).  Frozen parameters: a model that describes its trainable ranges
+    performs engine.py:89's clip_grad_norm_(.,1).  ``'lion'`` (not in the reference) returns ``FusedLion`` with ``cfg['lr']``,
+    ``cfg['weight_decay']`` and ``cfg.get('betas', (0.9, 0.99))``; torch ships no Lion, so ``fused=False`` raises.  Frozen parameters: a model that describes its trainable ranges
     (``trainable_plan``: model.CLIP) keeps the fused step, which then updates those ranges only; any other model gets the stock
     SGD over the trainable ones (the fused step would update the whole flat buffer)."""
     if cfg["optimizer"] == "sgd":
@@ -704,6 +799,12 @@ def build_optimizer(cfg: dict, model, fused: bool = True):
             return FusedAdam(model, lr=cfg["lr"], weight_decay=cfg["weight_decay"], max_norm=1.0)
         return torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=cfg["lr"],
                                 weight_decay=cfg["weight_decay"])
+    if cfg["optimizer"] == "lion":
+        # not one of the reference's: the third optimiser of the CLIP recipes (FusedLion), with the reference's clip in front
+        if not fused:
+            raise NotImplementedError("build_optimizer: torch ships no Lion; 'lion' exists as the fused step only (fused=True), or "
+                                      "build timm.optim.Lion / lion_pytorch.Lion yourself")
+        return FusedLion(model, lr=cfg["lr"], betas=cfg.get("betas", (0.9, 0.99)), weight_decay=cfg["weight_decay"], max_norm=1.0)
     raise RuntimeError("Invalid optimizer '{}'. ".format(cfg["optimizer"]))
 
 

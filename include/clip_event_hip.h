@@ -421,6 +421,39 @@ int ce_sgd_step_groups_ema(float* p, const float* g, float* buf, void* p_bf16, c
                            int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
                            float max_norm, const ce_optim_group* groups, int ngroups, float momentum, float dampening, int nesterov,
                            int first_step, float* ema, float ema_rate, void* stream);
+/* ---- Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms") behind the same clip, in every form above ----
+ * One state stream m (exp_avg; zeros are the initial state: no bias correction, no step counter, no first-step flag), the streams
+ * and bytes of SGD with momentum.  Per element, in fp32, every product and sum rounded on its own (no multiply-add), in this order:
+ *     gc = g * coef                        coef as ce_adam_step: min(1, max_norm / (sqrt(*sumsq) + 1e-6)), 1 when sumsq is NULL
+ *     c  = beta1 * m + (1 - beta1) * gc    two products, one sum
+ *     u  = (c > 0) - (c < 0)               the sign; 0 for c == 0, and 0 for a NaN c (both comparisons are false: the master then
+ *                                          moves by the decay alone, and m becomes NaN)
+ *     p  = p - (lr * weight_decay) * p     decoupled decay, always; skipped, bit for bit, when lr * weight_decay == 0
+ *     p  = p - lr * u                      the master moves by exactly lr
+ *     m  = beta2 * m + (1 - beta2) * gc    from the OLD m, after c was formed
+ * 1 - beta1, 1 - beta2 and lr * weight_decay are rounded once to fp32.  All forms give the same bits; p_bf16, jobs, segments,
+ * segment_group and groups are those of the Adam / SGD forms.  In the grouped form lr and weight_decay come from the group and
+ * ce_optim_group.decoupled is IGNORED (Lion's decay is decoupled whatever it says); one group gives ce_lion_step_tiles' bits.
+ * -EINVAL, each with a message of its own, for n <= 0 (flat), m == NULL, beta1 or beta2 outside [0, 1), lr < 0 or weight_decay < 0
+ * (of any group), and for what the SGD form refuses: empty tables, ngroups outside 1..8, groups == NULL, p / g / p_bf16 NULL; the
+ * _ema forms (as above: ema += ema_rate * (p_new - ema) in the same traversal) also for ema == NULL and ema_rate outside (0, 1]. */
+int ce_lion_step(float* p, const float* g, float* m, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+                 float beta1, float beta2, float weight_decay, void* stream);
+int ce_lion_step_tiles(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                       int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
+                       float beta1, float beta2, float weight_decay, void* stream);
+int ce_lion_step_groups(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                        int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
+                        float max_norm, const ce_optim_group* groups, int ngroups, float beta1, float beta2, void* stream);
+int ce_lion_step_ema(float* p, const float* g, float* m, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+                     float beta1, float beta2, float weight_decay, float* ema, float ema_rate, void* stream);
+int ce_lion_step_tiles_ema(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                           int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
+                           float beta1, float beta2, float weight_decay, float* ema, float ema_rate, void* stream);
+int ce_lion_step_groups_ema(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                            int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
+                            float max_norm, const ce_optim_group* groups, int ngroups, float beta1, float beta2, float* ema,
+                            float ema_rate, void* stream);
 /* a[i] <-> b[i] for i < n, and a_bf16[i] = bf16(new a[i]) (ce_cast_bf16's rounding): the masters and their average change places
  * and the bf16 mirror follows, in one pass.  a, b 16-byte aligned, a_bf16 8-byte aligned, a != b.  Calling it twice restores both. */
 int ce_swap_cast_bf16(float* a, float* b, void* a_bf16, long n, void* stream);

@@ -2,7 +2,8 @@
 """Micro-benchmarks of the HBM-bound kernels at the step's shapes with COLD operands: every call works on the next of
 NSETS buffer sets (together larger than the 256 MiB Infinity Cache), as in the step, where a kernel's inputs were written
 tens of kernels earlier.  Prints us per call and GB/s on the algorithmic bytes.   python tools/bench_hbm.py [ln adam sgd attn]
-adam_ema / sgd_ema: the tiled update with the weight average fused in, beside the same update without it and beside "update, then
+lion: clip + Lion, flat (22 B per parameter) and tiled (24 B), each beside the SGD-with-momentum form that moves the same bytes.
+adam_ema / sgd_ema / lion_ema: the tiled update with the weight average fused in, beside the same update without it and beside "update, then
 ``ema.lerp_(masters, rate)``" -- what the fusion replaces -- in alternation in one process."""
 import os
 import sys
@@ -154,6 +155,52 @@ def bench_sgd():
               flush=True)
 
 
+def bench_lion(rounds=2):
+    """clip + Lion beside clip + SGD with momentum 0.9, which moves exactly the same bytes: the flat kernels on buffers of their own
+    (12 B read + 10 B written per parameter) and the tiled forms over the model's layout (+ 2 B of W^T), each pair in alternation
+    (same box, same minute), ``rounds`` times."""
+    n = 151_277_312
+    p = torch.randn(n, device=DEV) * 0.02
+    g = torch.randn(n, device=DEV) * 1e-3
+    buf = torch.zeros(n, device=DEV)
+    p16 = torch.empty(n, device=DEV, dtype=torch.bfloat16)
+    ss = torch.zeros(1, device=DEV)
+
+    def sgd():
+        check(lib().ce_sgd_step(ptr(p), ptr(g), ptr(buf), ptr(p16), c_long(n), ptr(ss), c_float(1.0), c_float(1e-6), c_float(0.9),
+                                c_float(0.0), c_float(0.0), c_int(0), c_int(0), stream()), "sgd")
+
+    def lion():
+        check(lib().ce_lion_step(ptr(p), ptr(g), ptr(buf), ptr(p16), c_long(n), ptr(ss), c_float(1.0), c_float(1e-6), c_float(0.9),
+                                 c_float(0.99), c_float(0.0), stream()), "lion")
+
+    for r in range(rounds):
+        t_sgd = timeit([sgd], iters=10, warm=2)
+        print(f"sgd     round {r} n={n}: {t_sgd * 1e6:7.1f} us  {n * 22 / t_sgd / 1e9:7.0f} GB/s", flush=True)
+        dt = timeit([lion], iters=10, warm=2)
+        print(f"lion    round {r} n={n}: {dt * 1e6:7.1f} us  {n * 22 / dt / 1e9:7.0f} GB/s   ({dt / t_sgd:.3f} of the SGD line above; same bytes)",
+              flush=True)
+    del p, g, buf, p16
+    t = _tiled_model()
+    m, seg, (tj, tn_, tt) = t["m"], t["seg"], t["m"]._tjobs_bwd
+    n = sum(q.numel() for q in m.parameters())
+    head = (ptr(m._flat), ptr(m._flat_grad), ptr(t["a"]), ptr(m._flat16), ptr(tj), c_int(tn_), c_int(tt), ptr(seg), c_int(seg.shape[0]),
+            ptr(t["ss"]), c_float(1.0), c_float(1e-6))
+
+    def sgd_tiles():
+        check(lib().ce_sgd_step_tiles(*head, c_float(0.9), c_float(0.0), c_float(0.0), c_int(0), c_int(0), stream()), "sgd tiles")
+
+    def lion_tiles():
+        check(lib().ce_lion_step_tiles(*head, c_float(0.9), c_float(0.99), c_float(0.0), stream()), "lion tiles")
+
+    for r in range(rounds):
+        t_sgd = timeit([sgd_tiles], iters=10, warm=2)
+        print(f"sgd tiles  round {r} n={n}: {t_sgd * 1e6:7.1f} us  {n * 24 / t_sgd / 1e9:7.0f} GB/s", flush=True)
+        dt = timeit([lion_tiles], iters=10, warm=2)
+        print(f"lion tiles round {r} n={n}: {dt * 1e6:7.1f} us  {n * 24 / dt / 1e9:7.0f} GB/s   ({dt / t_sgd:.3f} of the SGD line above; same bytes)",
+              flush=True)
+
+
 def bench_ema(kinds, rounds=3):
     """The step's tiled update over the ViT-B/32 layout (same parameter count as ``adam`` / ``sgd``) in three forms, measured in
     alternation (same box, same minute), ``rounds`` times: without the average (Adam 32 B, SGD 24 B per parameter); with the
@@ -166,9 +213,10 @@ def bench_ema(kinds, rounds=3):
     rate = 1e-4
     tables = (ptr(m._flat16), ptr(tj), c_int(tn_), c_int(tt), ptr(seg), c_int(seg.shape[0]), ptr(t["ss"]), c_float(1.0), c_float(1e-6))
     tails = {"adam": (c_float(0.9), c_float(0.999), c_float(1e-8), c_float(0.0), c_int(3)),
-             "sgd": (c_float(0.9), c_float(0.0), c_float(0.0), c_int(0), c_int(0))}
-    state = {"adam": (ptr(t["a"]), ptr(t["b"])), "sgd": (ptr(t["a"]),)}
-    base_bytes = {"adam": 32, "sgd": 24}
+             "sgd": (c_float(0.9), c_float(0.0), c_float(0.0), c_int(0), c_int(0)),
+             "lion": (c_float(0.9), c_float(0.99), c_float(0.0))}
+    state = {"adam": (ptr(t["a"]), ptr(t["b"])), "sgd": (ptr(t["a"]),), "lion": (ptr(t["a"]),)}
+    base_bytes = {"adam": 32, "sgd": 24, "lion": 24}
 
     def step(kind, fused):
         name = f"ce_{kind}_step_tiles" + ("_ema" if fused else "")
@@ -216,7 +264,9 @@ if __name__ == "__main__":
         bench_adam()
     if "sgd" in which:
         bench_sgd()
-    if "adam_ema" in which or "sgd_ema" in which:
-        bench_ema([k for k in ("adam", "sgd") if k + "_ema" in which])
+    if "lion" in which:
+        bench_lion()
+    if "adam_ema" in which or "sgd_ema" in which or "lion_ema" in which:
+        bench_ema([k for k in ("adam", "sgd", "lion") if k + "_ema" in which])
     if "attn" in which:
         bench_attn()
