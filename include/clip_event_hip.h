@@ -301,6 +301,28 @@ size_t ce_preprocess_table_bytes(int n_out, int n_px, int kmax);
 int ce_preprocess(const ce_preproc_desc* descs_device, int n_out, int n_px, int kmax, int max_rows, void* table,
                   void* tmp, float* out, const float* mean, const float* std, void* stream);
 
+/* ---- training augmentation (preprocess.hip) ---- */
+/* What follows the crop + resize of one OUTPUT, in torchvision's order: RandomHorizontalFlip, ColorJitter (an op list in
+ * its drawn order), RandomGrayscale.  The arithmetic is Pillow's (Blend.c, Convert.c), bit for bit. */
+enum { CE_AUG_BRIGHTNESS = 0, CE_AUG_CONTRAST = 1, CE_AUG_SATURATION = 2, CE_AUG_HUE = 3 };
+typedef struct {
+    int flip;          /* 0/1: mirror left-right */
+    int grey;          /* 0/1: replace the three channels by the luma, after the ops */
+    int n_ops;         /* 0..4 */
+    int op[4];         /* CE_AUG_*; contrast at most once */
+    float factor[4];   /* >= 0: the enhancement factor (1 = unchanged); for hue the integer shift 0..255 of the 8-bit H */
+} ce_augment_desc;
+/* table, per-output luma sums, 8-bit n x n x 3 images and the pass-1 scratch (tmp_bytes = sum of rows*n*3) in one block */
+size_t ce_augment_workspace_bytes(int n_out, int n_px, int kmax, long tmp_bytes);
+/* out[o] (f32 [3,n,n]) = Normalize(ToTensor(grey(ops(flip(Resize(region_o -> n x n, BICUBIC)))))).  descs: as for
+ * ce_preprocess with ow = oh = n_px and left = top = 0 (RandomResizedCrop: the region is the crop box; it may be smaller
+ * than n_px).  augs_device / augs_host: the same n_out records on the device and on the host (the host copy is checked
+ * and decides whether the contrast reduction is launched at all).  The contrast mean is an integer sum per output, so the
+ * result does not depend on the launch shape; the sums are zeroed by the library's own kernels.  n_px <= 2896. */
+int ce_augment(const ce_preproc_desc* descs_device, const ce_augment_desc* augs_device, const ce_augment_desc* augs_host,
+               int n_out, int n_px, int kmax, int max_rows, void* workspace, float* out, const float* mean, const float* std,
+               void* stream);
+
 /* ---- contrastive head (head.hip) ---- */
 int ce_l2norm_fwd(const float* f, long ldf, float* y, long ldy, float* inv_norm, int n, int E, void* stream);
 int ce_l2norm_bwd(const float* dy, long lddy, const float* y, long ldy, const float* inv_norm, float* df, long lddf,

@@ -25,7 +25,12 @@ on logits + ``losses.CriterionDistill``, CE_FUSED_HEAD=1 for the fused distillat
 
 ``--ema DECAY`` keeps an exponential moving average of the weights in the fused step (``optimizer.enable_ema``; ``--ema-warmup``:
 the ramped decay of ``optim.ema_rate``); the checkpoint carries it, the resumed run restores it, and the end prints
-``inference.retrieval_metrics`` on the fixed batch for the raw and for the averaged weights (``optimizer.averaged()``)."""
+``inference.retrieval_metrics`` on the fixed batch for the raw and for the averaged weights (``optimizer.averaged()``).
+
+``--augment`` replaces the evaluation transform by open_clip's training transform on the device (``preprocess.Augment``:
+``RandomResizedCrop(scale=(0.9, 1.0))``; ``--aug-scale``, ``--aug-hflip``, ``--aug-color-jitter B C S H``, ``--aug-color-jitter-prob``,
+``--aug-gray-scale-prob`` are its ``--aug-cfg`` fields) with ``draw`` = the step, so that the run resumed at step 20 sees the crops the
+first run would have seen there."""
 import argparse
 import os
 import sys
@@ -39,20 +44,20 @@ from clip_event_amd import checkpoint, clip, distributed as D, inference, synthe
 from clip_event_amd.engine import Distillation, train_step as engine_train_step
 from clip_event_amd.losses import CriterionContrastive, CriterionSigmoid
 from clip_event_amd.optim import FusedAdam, FusedLion, FusedSGD, build_lr_scheduler, build_optimizer, no_decay_groups
-from clip_event_amd.preprocess import preprocess
+from clip_event_amd.preprocess import Augment, preprocess
 
 CAPTIONS = list(S.ASCII_CAPTIONS)
 
 
-def batch(rng, B, K, dev):
+def batch(rng, B, K, dev, aug=None, draw=0):
     sizes = [(int(rng.integers(240, 640)), int(rng.integers(240, 640))) for _ in range(B)]
     imgs = [torch.from_numpy(rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)).to(dev) for (w, h) in sizes]
-    image = preprocess(imgs)                                                    # clip.py:62-69 on the GPU
+    image = preprocess(imgs) if aug is None else aug(imgs, draw=draw)           # clip.py:62-69 / the training transform, on the GPU
     texts = [CAPTIONS[int(rng.integers(len(CAPTIONS)))] + f" number {int(rng.integers(1000))}" for _ in range(B * K)]
     text = clip.tokenize(texts)                                                 # clip.py:168-201: stays on the HOST, as the reference's loader
                                                                                 # yields it -- train_step copies it and keeps the caption lengths
     yi, yt, ip = D.global_labels(B, 1, K - 1, True, device=dev)                 # dataset_voa.py:605-664
-    return image, text, yi, yt, ip
+    return (image, text, yi, yt, ip), imgs
 
 
 def main():
@@ -76,7 +81,19 @@ def main():
                     help="distil from a frozen teacher of this geometry (engine.Distillation)")
     ap.add_argument("--distill-weight", type=float, default=1.0, metavar="W", help="with --distill-arch: weight of the two terms")
     ap.add_argument("--distill-checkpoint", default=None, metavar="PATH", help="with --distill-arch: the teacher's checkpoint")
+    ap.add_argument("--augment", action="store_true", help="open_clip's training transform on the device (preprocess.Augment), draw = step")
+    ap.add_argument("--aug-scale", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --augment: RandomResizedCrop scale (0.9 1.0)")
+    ap.add_argument("--aug-hflip", type=float, default=None, metavar="P", help="with --augment: probability of a horizontal flip (0)")
+    ap.add_argument("--aug-color-jitter", type=float, nargs=4, default=None, metavar=("B", "C", "S", "H"),
+                    help="with --augment: ColorJitter(brightness, contrast, saturation, hue)")
+    ap.add_argument("--aug-color-jitter-prob", type=float, default=None, metavar="P", help="with --aug-color-jitter: its probability (0.8)")
+    ap.add_argument("--aug-gray-scale-prob", type=float, default=None, metavar="P", help="with --augment: RandomGrayscale probability (0)")
     args = ap.parse_args()
+    aug_cfg = {k: v for k, v in (("scale", args.aug_scale), ("hflip", args.aug_hflip), ("color_jitter", args.aug_color_jitter),
+                                 ("color_jitter_prob", args.aug_color_jitter_prob), ("gray_scale_prob", args.aug_gray_scale_prob))
+               if v is not None}
+    if aug_cfg and not args.augment:
+        ap.error("--aug-* options go with --augment")
     if args.distill_arch is None and (args.distill_checkpoint is not None or args.distill_weight != 1.0):
         ap.error("--distill-weight / --distill-checkpoint go with --distill-arch")
     if args.logit_bias is not None and args.loss != "sigmoid":
@@ -138,9 +155,12 @@ def main():
     if args.ema is not None:
         optimizer.enable_ema(args.ema, warmup=args.ema_warmup)
     scheduler = build_lr_scheduler(cfg, optimizer, 0)                           # engine.py:154-176
-    data = batch(rng, B, K, dev)                                                # one fixed batch: the loss must fall
+    aug = Augment(model.visual.input_resolution, seed=0, **aug_cfg) if args.augment else None
+    data, decoded = batch(rng, B, K, dev, aug)                                  # one fixed batch: the loss must fall
     losses = []
     for it in range(20):
+        if aug is not None:
+            data = (aug(decoded, draw=it),) + data[1:]                          # the same images, cropped (jittered) anew every step
         ld = train_step(model, criterion, optimizer, *data, check_finite=True, micro_batch=mb)
         scheduler.step()
         losses.append(float(sum(v.detach() for v in ld.values())))
@@ -150,7 +170,7 @@ def main():
     # wrong side -- and has 20 steps at lr 1e-5 to pull the positives up; so must Lion's, which at a tenth of Adam's rate moves
     # every weight by at most 1e-6 per step where Adam's first steps move it by 1e-5: measured 6.72 -> 5.81)
     slow = (args.lock_image_tower or args.lock_text_tower or args.patch_dropout or args.loss == "sigmoid" or args.distill_arch
-            or args.optimizer == "lion")
+            or args.optimizer == "lion" or args.augment)
     assert losses[-1] < (0.5 if not slow else 1.0) * losses[0]
     with tempfile.TemporaryDirectory() as d:
         path = checkpoint.save_model_on_master(model, d, cfg["task"], 20, 0.0, optimizer)      # engine.py:202-218
@@ -168,20 +188,28 @@ def main():
             optimizer2.load_ema_state_dict(ema)                                               # decay, warm-up, update count, average
             assert optimizer2.ema_updates == optimizer.ema_updates == 20
         scheduler2 = build_lr_scheduler(cfg, optimizer2, begin_epoch)
+    if aug is not None:
+        # the draws are a hash of (seed, rank, draw, sample): a resumed run needs the settings and the step, nothing else
+        aug.draw = 20
+        aug2 = Augment(model2.visual.input_resolution, seed=0, **aug_cfg)
+        aug2.load_state_dict(aug.state_dict())
+        data = (aug2(decoded),) + data[1:]
+        assert aug2.draw == 21 and torch.equal(data[0], aug(decoded, draw=20)) and not torch.equal(data[0], aug(decoded, draw=19))
+        print("resumed run draws the crops of step 20 again")
     assert begin_epoch == 20 and abs(optimizer2.param_groups[0]["lr"] - optimizer.param_groups[0]["lr"]) < 1e-12
     a = train_step(model, criterion, optimizer, *data, micro_batch=mb)
     b = train_step(model2, criterion, optimizer2, *data, micro_batch=mb)
     la, lb = float(sum(v.detach() for v in a.values())), float(sum(v.detach() for v in b.values()))
     print(f"resumed run continues: loss {la:.5f} vs {lb:.5f}")
     assert abs(la - lb) < 1e-3 * max(1.0, abs(la))
-    new = batch(rng, B, K, dev)                                                 # a fresh ragged batch goes through too
+    new, _ = batch(rng, B, K, dev, aug, 21)                                     # a fresh ragged batch goes through too
     ld = train_step(model2, criterion, optimizer2, *new, micro_batch=mb)
     scheduler2.step()
     assert all(torch.isfinite(v) for v in ld.values())
     # a longer stretch of fresh batches with no host synchronisation in the loop: host-side caption lengths, the run-ahead
     # limit of engine.train_step, the asynchronous poll of the fp16-stream clamp counters (every 16 optimiser steps)
     import time
-    batches = [batch(rng, 32, K, dev) for _ in range(8)]
+    batches = [batch(rng, 32, K, dev, aug, 22 + i)[0] for i in range(8)]
     for it in range(4):                                                         # new batch size: workspaces are allocated here
         train_step(model2, criterion, optimizer2, *batches[it], micro_batch=mb)
     torch.cuda.synchronize()
