@@ -39,11 +39,13 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "head_sweep.hpp"
 #include "../../include/clip_event_hip.h"
+
+using namespace head_sweep;
 
 namespace {
 
-constexpr int HB = 32;          // rows per resident / streamed block
 enum { MODE_FWD = 0, MODE_DQ = 1, MODE_DK = 2 };
 enum { LOSS_SOFTMAX = 0, LOSS_SIGMOID = 1, LOSS_DISTILL = 2 };
 
@@ -71,8 +73,6 @@ struct HeadArgs {
     const float* dot; long lddot;                 // DQ: part[split][r] = <dot[sel[r]], this split's share of output row r> (nullable)
     float csign;                                  // c = csign * (grad ? *grad / nq : 1)
 };
-
-__device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // 32x32 C/D row of reg r
 
 // log(1 + e) for 0 <= e <= 1, accurate where e is tiny (with the usual bias near -10 a negative pair's term is ~ 4.5e-5 and
 // log(1.f + e) alone keeps four of its digits): u = fl(1 + e) carries the rounding of the sum, and log(u) * e / (u - 1) takes it
@@ -107,15 +107,7 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
     const float scale = (LOSS == LOSS_DISTILL) ? expf(*a.logit_scale) : __expf(*a.logit_scale);
 
     // ---- resident block -> LDS (gathered through sel when the residents are queries) ----
-    for (int idx = tid; idx < HB * (E / 4); idx += 64 * NW) {
-        const int r = idx / (E / 4), c = (idx - r * (E / 4)) * 4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (r0 + r < a.nres) {
-            const long src = (MODE != MODE_DK && a.sel) ? a.sel[r0 + r] : (long)(r0 + r);
-            v = *reinterpret_cast<const f32x4*>(a.res + src * a.ldres + c);
-        }
-        *reinterpret_cast<f32x4*>(res_l + r * pitch + c) = v;
-    }
+    load_residents<NW>(a.res, a.ldres, a.nres, MODE != MODE_DK ? a.sel : nullptr, E, res_l, r0, tid);
     // per-lane facts about resident row j
     const bool jvalid = r0 + j < a.nres;
     long jsrc = 0, jlabel = -1;
@@ -358,13 +350,8 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
 __global__ __launch_bounds__(256) void infonce_merge_kernel(HeadArgs a, float* __restrict__ lse_out, float* __restrict__ loss) {
     const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= a.nq) return;
-    float m = -INFINITY;
-    for (int s = 0; s < a.splits; ++s) m = fmaxf(m, a.part[((long)s * a.nq + r) * 2]);
-    float l = 0.f;
-    for (int s = 0; s < a.splits; ++s) {
-        const float* p = a.part + ((long)s * a.nq + r) * 2;
-        l += p[1] * __expf(p[0] - m);
-    }
+    float m, l;
+    merge_max_sum(a.part + 2L * r, 2L * a.nq, a.splits, m, l);
     const float lse = m + __logf(l);
     const long src = a.sel ? a.sel[r] : (long)r;
     const long y = a.labels[src];
@@ -393,44 +380,46 @@ __global__ __launch_bounds__(256) void sigmoid_loss_sum_kernel(const float* __re
     if (threadIdx.x == 0) *loss = red[0] / (float)nq;
 }
 
-size_t head_lds_bytes(int E, int nw) { return (size_t)(HB * (E + 4) + nw * HB * 33 + 2 * HB) * 4; }
+size_t head_lds_bytes(int E, int nw) { return lds_bytes(E, nw) + 2 * HB * 4; }      // + qinfo
 
+struct Side {      // one matrix of a sweep: [n, E] fp32 rows, ld floats apart
+    const float* p; long ld; int n;
+};
+constexpr int NO_CAP = 1 << 20;          // splits of a sweep whose partials need no workspace
+
+// One sweep of the skeleton: `res` resident, `str` streamed, both E wide, the streamed blocks split under `cap`.
+// The wave count follows head_sweep::eight_waves -- for FWD too, with Eval = the width of the values its log-sum-exp will later
+// weigh: exp(x - max) of a row's largest entry is exactly 1 only when the sweep that rebuilds x adds it up as FWD did.
 template <int MODE, int LOSS = LOSS_SOFTMAX>
-int launch_head(HeadArgs& a, hipStream_t s) {
+int sweep(HeadArgs& a, Side res, Side str, int E, int cap, hipStream_t s) {
     static std::once_flag flag;
     std::call_once(flag, [] {
         hipFuncSetAttribute(reinterpret_cast<const void*>(infonce_kernel<MODE, 4, LOSS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)head_lds_bytes(1024, 4));
         hipFuncSetAttribute(reinterpret_cast<const void*>(infonce_kernel<MODE, 8, LOSS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)head_lds_bytes(768, 8));      // E = 1024 with eight partial tiles exceeds 160 KiB
+                            (int)head_lds_bytes(768, 8));
     });
-    const int rb = ce_div_up(a.nres, HB);
+    a.res = res.p; a.ldres = res.ld; a.nres = res.n;
+    a.str = str.p; a.ldstr = str.ld; a.nstr = str.n;
+    a.E = E;
+    const Splits sp = split_choice(res.n, str.n, 0, cap);
+    a.splits = sp.splits;
+    a.blocks_per_split = sp.blocks_per_split;
+    const int rb = ce_div_up(res.n, HB);
     static const int force_nw = getenv("CE_HEAD_WAVES") ? atoi(getenv("CE_HEAD_WAVES")) : 0;
-    // eight waves split BOTH widths in eight: a 128-wide value matrix under a 256-wide similarity would get no e-tile.  The
-    // rule holds for FWD too (Eval = the width of the values its log-sum-exp will later weigh): the waves' partial tiles are
-    // added in wave order, so a similarity summed by eight waves differs in its last bits from the same one summed by four, and
-    // exp(x - max) of a row's largest entry is exactly 1 only when the sweep that rebuilds x adds it up as FWD did
-    const bool eight = a.E % 256 == 0 && a.E <= 768 && force_nw != 4 && (LOSS != LOSS_DISTILL || a.Eval % 256 == 0);
-    if (eight) hipLaunchKernelGGL((infonce_kernel<MODE, 8, LOSS>), dim3(rb, a.splits), dim3(512), head_lds_bytes(a.E, 8), s, a);
-    else hipLaunchKernelGGL((infonce_kernel<MODE, 4, LOSS>), dim3(rb, a.splits), dim3(256), head_lds_bytes(a.E, 4), s, a);
+    if (eight_waves(E, LOSS == LOSS_DISTILL ? a.Eval : E) && force_nw != 4)
+        hipLaunchKernelGGL((infonce_kernel<MODE, 8, LOSS>), dim3(rb, a.splits), dim3(512), head_lds_bytes(E, 8), s, a);
+    else hipLaunchKernelGGL((infonce_kernel<MODE, 4, LOSS>), dim3(rb, a.splits), dim3(256), head_lds_bytes(E, 4), s, a);
+    CE_LAUNCH_CHECK();
     return 0;
-}
-
-int pick_splits(int nres, int nstr, int cap) {
-    const int rb = ce_div_up(nres, HB), sblocks = ce_div_up(nstr, HB);
-    int splits = ce_div_up(512, rb);            // about two workgroups per CU
-    if (splits > sblocks) splits = sblocks;
-    if (splits > cap) splits = cap;
-    if (splits < 1) splits = 1;
-    return splits;
 }
 
 int check_common(const char* what, const float* q, long ldq, int nq, const float* k, long ldk, int nk, int E,
                  const float* logit_scale, const int64_t* labels) {
-    CE_CHECK_ARG(q && k && logit_scale && labels, "%s: null buffer", what);
+    if (int rc = check_features(what, "E", q, ldq, E)) return rc;
+    if (int rc = check_features(what, "E", k, ldk, E)) return rc;
+    CE_CHECK_ARG(logit_scale && labels, "%s: null buffer", what);
     CE_CHECK_ARG(nq > 0 && nk > 0, "%s: empty problem", what);
-    CE_CHECK_ARG(E >= 128 && E % 128 == 0 && E <= 1024, "%s: E must be a multiple of 128 in 128..1024 (got %d)", what, E);
-    CE_CHECK_ARG(ldq >= E && ldk >= E && ldq % 4 == 0 && ldk % 4 == 0, "%s: leading dimensions must be >= E and multiples of 4", what);
     CE_CHECK_ARG(nk < (1 << 24), "%s: more than 2^24 keys", what);
     return 0;
 }
@@ -444,16 +433,13 @@ extern "C" int ce_infonce_fwd(const float* q, long ldq, const int64_t* sel, int 
                               void* stream) {
     if (int rc = check_common("ce_infonce_fwd", q, ldq, nq, k, ldk, nk, E, logit_scale, labels)) return rc;
     CE_CHECK_ARG(lse && loss && workspace, "ce_infonce_fwd: null output");
-    HeadArgs a{};
-    a.res = q; a.ldres = ldq; a.nres = nq; a.str = k; a.ldstr = ldk; a.nstr = nk;
-    a.sel = (const long*)sel; a.labels = (const long*)labels; a.logit_scale = logit_scale;
-    a.part = (float*)workspace; a.E = E; a.nq = nq;
-    a.splits = pick_splits(nq, nk, CE_INFONCE_MAX_SPLITS);
-    a.blocks_per_split = ce_div_up(ce_div_up(nk, HB), a.splits);
-    a.splits = ce_div_up(ce_div_up(nk, HB), a.blocks_per_split);
     hipStream_t s = (hipStream_t)stream;
-    launch_head<MODE_FWD>(a, s);
-    CE_LAUNCH_CHECK();
+    const Side Q{q, ldq, nq}, K{k, ldk, nk};
+    HeadArgs a{};
+    a.sel = (const long*)sel; a.labels = (const long*)labels; a.logit_scale = logit_scale; a.nq = nq;
+    // per-split (max, sum) of every query, then the merge that also picks the labelled logit
+    a.part = (float*)workspace;
+    if (int rc = sweep<MODE_FWD>(a, Q, K, E, CE_INFONCE_MAX_SPLITS, s)) return rc;
     hipLaunchKernelGGL(infonce_merge_kernel, dim3(ce_div_up(nq, 4)), dim3(256), 0, s, a, lse, loss);
     CE_LAUNCH_CHECK();
     return 0;
@@ -465,31 +451,23 @@ extern "C" int ce_infonce_bwd(const float* q, long ldq, const int64_t* sel, int 
     if (int rc = check_common("ce_infonce_bwd", q, ldq, nq, k, ldk, nk, E, logit_scale, labels)) return rc;
     CE_CHECK_ARG(lse && grad && dq && dk && dlogit_scale, "ce_infonce_bwd: null buffer");
     hipStream_t s = (hipStream_t)stream;
+    const Side Q{q, ldq, nq}, K{k, ldk, nk};
     HeadArgs a{};
     a.sel = (const long*)sel; a.labels = (const long*)labels; a.logit_scale = logit_scale; a.lse = lse; a.grad = grad;
-    a.E = E; a.nq = nq; a.dls = dlogit_scale;
+    a.nq = nq; a.dls = dlogit_scale;
     // dq: resident = queries, streamed = keys
-    a.res = q; a.ldres = ldq; a.nres = nq; a.str = k; a.ldstr = ldk; a.nstr = nk; a.dres = dq;
-    a.splits = pick_splits(nq, nk, 1 << 20);
-    a.blocks_per_split = ce_div_up(ce_div_up(nk, HB), a.splits);
-    a.splits = ce_div_up(ce_div_up(nk, HB), a.blocks_per_split);
-    launch_head<MODE_DQ>(a, s);
-    CE_LAUNCH_CHECK();
+    a.dres = dq;
+    if (int rc = sweep<MODE_DQ>(a, Q, K, E, NO_CAP, s)) return rc;
     // dk: resident = keys, streamed = queries
-    a.res = k; a.ldres = ldk; a.nres = nk; a.str = q; a.ldstr = ldq; a.nstr = nq; a.dres = dk;
-    a.splits = pick_splits(nk, nq, 1 << 20);
-    a.blocks_per_split = ce_div_up(ce_div_up(nq, HB), a.splits);
-    a.splits = ce_div_up(ce_div_up(nq, HB), a.blocks_per_split);
-    launch_head<MODE_DK>(a, s);
-    CE_LAUNCH_CHECK();
-    return 0;
+    a.dres = dk;
+    return sweep<MODE_DK>(a, K, Q, E, NO_CAP, s);
 }
 
 // ---- sigmoid pairwise loss (SigLIP) on the same sweep ----------------------------------------------------------------
 
 extern "C" size_t ce_sigmoid_head_workspace_bytes(int nq, int nk) {
     if (nq <= 0 || nk <= 0) return 0;
-    return (size_t)ce_div_up(nq, HB) * pick_splits(nq, nk, CE_INFONCE_MAX_SPLITS) * sizeof(float);
+    return (size_t)ce_div_up(nq, HB) * split_bound(nq, nk, 0, CE_INFONCE_MAX_SPLITS) * sizeof(float);
 }
 
 extern "C" int ce_sigmoid_head_fwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
@@ -497,16 +475,13 @@ extern "C" int ce_sigmoid_head_fwd(const float* q, long ldq, const int64_t* sel,
                                    void* workspace, void* stream) {
     if (int rc = check_common("ce_sigmoid_head_fwd", q, ldq, nq, k, ldk, nk, E, logit_scale, labels)) return rc;
     CE_CHECK_ARG(logit_bias && loss && workspace, "ce_sigmoid_head_fwd: null buffer");
-    HeadArgs a{};
-    a.res = q; a.ldres = ldq; a.nres = nq; a.str = k; a.ldstr = ldk; a.nstr = nk;
-    a.sel = (const long*)sel; a.labels = (const long*)labels; a.logit_scale = logit_scale; a.logit_bias = logit_bias;
-    a.loss_part = (float*)workspace; a.E = E; a.nq = nq;
-    a.splits = pick_splits(nq, nk, CE_INFONCE_MAX_SPLITS);
-    a.blocks_per_split = ce_div_up(ce_div_up(nk, HB), a.splits);
-    a.splits = ce_div_up(ce_div_up(nk, HB), a.blocks_per_split);          // never more than the workspace was sized for
     hipStream_t s = (hipStream_t)stream;
-    launch_head<MODE_FWD, LOSS_SIGMOID>(a, s);
-    CE_LAUNCH_CHECK();
+    const Side Q{q, ldq, nq}, K{k, ldk, nk};
+    HeadArgs a{};
+    a.sel = (const long*)sel; a.labels = (const long*)labels; a.logit_scale = logit_scale; a.logit_bias = logit_bias; a.nq = nq;
+    // one loss partial per workgroup (never more splits than the workspace was sized for), then their sum in index order
+    a.loss_part = (float*)workspace;
+    if (int rc = sweep<MODE_FWD, LOSS_SIGMOID>(a, Q, K, E, CE_INFONCE_MAX_SPLITS, s)) return rc;
     hipLaunchKernelGGL(sigmoid_loss_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)workspace, ce_div_up(nq, HB) * a.splits, nq,
                        loss);
     CE_LAUNCH_CHECK();
@@ -519,24 +494,16 @@ extern "C" int ce_sigmoid_head_bwd(const float* q, long ldq, const int64_t* sel,
     if (int rc = check_common("ce_sigmoid_head_bwd", q, ldq, nq, k, ldk, nk, E, logit_scale, labels)) return rc;
     CE_CHECK_ARG(logit_bias && grad && dq && dk && dlogit_scale && dlogit_bias, "ce_sigmoid_head_bwd: null buffer");
     hipStream_t s = (hipStream_t)stream;
+    const Side Q{q, ldq, nq}, K{k, ldk, nk};
     HeadArgs a{};
     a.sel = (const long*)sel; a.labels = (const long*)labels; a.logit_scale = logit_scale; a.logit_bias = logit_bias; a.grad = grad;
-    a.E = E; a.nq = nq; a.dls = dlogit_scale; a.dbias = dlogit_bias;
+    a.nq = nq; a.dls = dlogit_scale; a.dbias = dlogit_bias;
     // dq: resident = queries, streamed = keys (also the scale and bias gradients)
-    a.res = q; a.ldres = ldq; a.nres = nq; a.str = k; a.ldstr = ldk; a.nstr = nk; a.dres = dq;
-    a.splits = pick_splits(nq, nk, 1 << 20);
-    a.blocks_per_split = ce_div_up(ce_div_up(nk, HB), a.splits);
-    a.splits = ce_div_up(ce_div_up(nk, HB), a.blocks_per_split);
-    launch_head<MODE_DQ, LOSS_SIGMOID>(a, s);
-    CE_LAUNCH_CHECK();
+    a.dres = dq;
+    if (int rc = sweep<MODE_DQ, LOSS_SIGMOID>(a, Q, K, E, NO_CAP, s)) return rc;
     // dk: resident = keys, streamed = queries
-    a.res = k; a.ldres = ldk; a.nres = nk; a.str = q; a.ldstr = ldq; a.nstr = nq; a.dres = dk;
-    a.splits = pick_splits(nk, nq, 1 << 20);
-    a.blocks_per_split = ce_div_up(ce_div_up(nq, HB), a.splits);
-    a.splits = ce_div_up(ce_div_up(nq, HB), a.blocks_per_split);
-    launch_head<MODE_DK, LOSS_SIGMOID>(a, s);
-    CE_LAUNCH_CHECK();
-    return 0;
+    a.dres = dk;
+    return sweep<MODE_DK, LOSS_SIGMOID>(a, K, Q, E, NO_CAP, s);
 }
 
 // ---- distillation: cross entropy against a teacher's softmax, on sweeps of the same skeleton --------------------------
@@ -552,17 +519,12 @@ namespace {
 // log-sum-exp from the per-split (max, sum), one thread per query, kept as the pair (max, log sum): one float holds a
 // log-sum-exp near 40 to 2e-6 only, and a softmax rebuilt as exp(x - lse) would be off by that factor in EVERY entry of the
 // row -- up to 2e-6 x sum_c P S ~ 1e-4 in a row term whose value is ~ 1 when both distributions are peaked.  exp((x - max)
-// - log sum) is normalised to fp32 rounding -- provided the sweep rebuilds x bit for bit as FWD saw it (launch_head's wave rule).
+// - log sum) is normalised to fp32 rounding -- provided the sweep rebuilds x bit for bit as FWD saw it (sweep()'s wave rule).
 __global__ __launch_bounds__(256) void lse_merge_kernel(const float* __restrict__ part, int splits, int nq, float* __restrict__ lse_out) {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= nq) return;
-    float m = -INFINITY;
-    for (int s = 0; s < splits; ++s) m = fmaxf(m, part[((long)s * nq + r) * 2]);
-    float l = 0.f;
-    for (int s = 0; s < splits; ++s) {
-        const float* p = part + ((long)s * nq + r) * 2;
-        l += p[1] * __expf(p[0] - m);
-    }
+    float m, l;
+    merge_max_sum(part + 2L * r, 2L * nq, splits, m, l);
     lse_out[2 * r] = m;
     lse_out[2 * r + 1] = __logf(l);
 }
@@ -596,23 +558,15 @@ __global__ __launch_bounds__(256) void rowdot_sum_kernel(const float* __restrict
     if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1]) + (red[2] + red[3]));
 }
 
-void set_splits(HeadArgs& a, int cap) {
-    a.splits = pick_splits(a.nres, a.nstr, cap);
-    a.blocks_per_split = ce_div_up(ce_div_up(a.nstr, HB), a.splits);
-    a.splits = ce_div_up(ce_div_up(a.nstr, HB), a.blocks_per_split);
-}
-
 int check_distill(const char* what, const float* q, long ldq, int nq, const float* k, long ldk, int nk, int Es,
                   const float* logit_scale, const float* tq, long ldtq, const float* tk, long ldtk, int Et,
                   const float* teacher_logit_scale) {
-    CE_CHECK_ARG(q && k && logit_scale && tq && tk && teacher_logit_scale, "%s: null buffer", what);
+    if (int rc = check_features(what, "Es", q, ldq, Es)) return rc;
+    if (int rc = check_features(what, "Es", k, ldk, Es)) return rc;
+    if (int rc = check_features(what, "Et", tq, ldtq, Et)) return rc;
+    if (int rc = check_features(what, "Et", tk, ldtk, Et)) return rc;
+    CE_CHECK_ARG(logit_scale && teacher_logit_scale, "%s: null buffer", what);
     CE_CHECK_ARG(nq > 0 && nk > 0, "%s: empty problem", what);
-    CE_CHECK_ARG(Es >= 128 && Es % 128 == 0 && Es <= 1024, "%s: Es must be a multiple of 128 in 128..1024 (got %d)", what, Es);
-    CE_CHECK_ARG(Et >= 128 && Et % 128 == 0 && Et <= 1024, "%s: Et must be a multiple of 128 in 128..1024 (got %d)", what, Et);
-    CE_CHECK_ARG(ldq >= Es && ldk >= Es && ldq % 4 == 0 && ldk % 4 == 0, "%s: student leading dimensions must be >= Es and multiples of 4",
-                 what);
-    CE_CHECK_ARG(ldtq >= Et && ldtk >= Et && ldtq % 4 == 0 && ldtk % 4 == 0,
-                 "%s: teacher leading dimensions must be >= Et and multiples of 4", what);
     return 0;
 }
 
@@ -629,28 +583,25 @@ extern "C" int ce_distill_head_fwd(const float* q, long ldq, const int64_t* sel,
         return rc;
     CE_CHECK_ARG(lse_s && lse_t && v && loss && workspace, "ce_distill_head_fwd: null output");
     hipStream_t s = (hipStream_t)stream;
+    const Side Q{q, ldq, nq}, K{k, ldk, nk}, TQ{tq, ldtq, nq}, TK{tk, ldtk, nk};
     HeadArgs a{};
     a.sel = (const long*)sel; a.nq = nq; a.part = (float*)workspace;
     // log-sum-exp of the teacher's rows, then of the student's (the partials of one are merged before the other's are written)
     // (Eval = Es in both: the wave count of the sweeps that will read these statistics)
-    a.res = tq; a.ldres = ldtq; a.nres = nq; a.str = tk; a.ldstr = ldtk; a.nstr = nk; a.E = Et; a.Eval = Es; a.logit_scale = teacher_logit_scale;
-    set_splits(a, CE_INFONCE_MAX_SPLITS);
-    launch_head<MODE_FWD, LOSS_DISTILL>(a, s);
-    CE_LAUNCH_CHECK();
+    a.Eval = Es;
+    a.logit_scale = teacher_logit_scale;
+    if (int rc = sweep<MODE_FWD, LOSS_DISTILL>(a, TQ, TK, Et, CE_INFONCE_MAX_SPLITS, s)) return rc;
     hipLaunchKernelGGL(lse_merge_kernel, dim3(ce_div_up(nq, 256)), dim3(256), 0, s, (const float*)workspace, a.splits, nq, lse_t);
     CE_LAUNCH_CHECK();
-    a.res = q; a.ldres = ldq; a.str = k; a.ldstr = ldk; a.E = Es; a.logit_scale = logit_scale;
-    launch_head<MODE_FWD, LOSS_DISTILL>(a, s);
-    CE_LAUNCH_CHECK();
+    a.logit_scale = logit_scale;
+    if (int rc = sweep<MODE_FWD, LOSS_DISTILL>(a, Q, K, Es, CE_INFONCE_MAX_SPLITS, s)) return rc;
     hipLaunchKernelGGL(lse_merge_kernel, dim3(ce_div_up(nq, 256)), dim3(256), 0, s, (const float*)workspace, a.splits, nq, lse_s);
     CE_LAUNCH_CHECK();
     // v[r] += sum_c softmax(T)[r,c] k^_c: the teacher's similarity, the student's keys as values, c = 1, written unscaled
-    a.res = tq; a.ldres = ldtq; a.str = tk; a.ldstr = ldtk; a.E = Et; a.logit_scale = teacher_logit_scale;
+    a.logit_scale = teacher_logit_scale;
     // the same sweep leaves <q^_r, its share of v_r> per split in the workspace: the loss does not depend on the atomics' order
-    a.lse = lse_t; a.val = k; a.ldval = ldk; a.Eval = Es; a.csign = 1.f; a.dres = v; a.dot = q; a.lddot = ldq;
-    set_splits(a, CE_INFONCE_MAX_SPLITS);
-    launch_head<MODE_DQ, LOSS_DISTILL>(a, s);
-    CE_LAUNCH_CHECK();
+    a.lse = lse_t; a.val = k; a.ldval = ldk; a.csign = 1.f; a.dres = v; a.dot = q; a.lddot = ldq;
+    if (int rc = sweep<MODE_DQ, LOSS_DISTILL>(a, TQ, TK, Et, CE_INFONCE_MAX_SPLITS, s)) return rc;
     // the rows' terms, then their sum in index order: no float atomic on the loss
     float* term = (float*)workspace + (size_t)CE_INFONCE_MAX_SPLITS * nq;
     hipLaunchKernelGGL(distill_row_term_kernel, dim3(ce_div_up(nq, 256)), dim3(256), 0, s, (const float*)workspace, a.splits,
@@ -670,26 +621,21 @@ extern "C" int ce_distill_head_bwd(const float* q, long ldq, const int64_t* sel,
         return rc;
     CE_CHECK_ARG(lse_s && lse_t && v && grad && dq && dk, "ce_distill_head_bwd: null buffer");
     hipStream_t s = (hipStream_t)stream;
+    const Side Q{q, ldq, nq}, K{k, ldk, nk}, TQ{tq, ldtq, nq}, TK{tk, ldtk, nk};
     HeadArgs a{};
     a.sel = (const long*)sel; a.nq = nq; a.grad = grad; a.out_logit_scale = logit_scale; a.Eval = Es;
     // dq[sel[r]] += (g/nq) s (sum_c P_s k^_c - v_r): student similarity, resident = queries; the first split's write takes v off
-    a.res = q; a.ldres = ldq; a.nres = nq; a.str = k; a.ldstr = ldk; a.nstr = nk; a.E = Es; a.logit_scale = logit_scale;
+    a.logit_scale = logit_scale;
     a.lse = lse_s; a.val = k; a.ldval = ldk; a.csign = 1.f; a.dres = dq; a.osel = (const long*)sel; a.sub = v;
-    set_splits(a, 1 << 20);
-    launch_head<MODE_DQ, LOSS_DISTILL>(a, s);
-    CE_LAUNCH_CHECK();
+    if (int rc = sweep<MODE_DQ, LOSS_DISTILL>(a, Q, K, Es, NO_CAP, s)) return rc;
     // dk[c] += (g/nq) s sum_r P_s q^_r: student similarity, resident = keys
-    a.res = k; a.ldres = ldk; a.nres = nk; a.str = q; a.ldstr = ldq; a.nstr = nq; a.val = q; a.ldval = ldq; a.dres = dk;
+    a.val = q; a.ldval = ldq; a.dres = dk;
     a.osel = nullptr; a.sub = nullptr;
-    set_splits(a, 1 << 20);
-    launch_head<MODE_DK, LOSS_DISTILL>(a, s);
-    CE_LAUNCH_CHECK();
+    if (int rc = sweep<MODE_DK, LOSS_DISTILL>(a, K, Q, Es, NO_CAP, s)) return rc;
     // dk[c] -= (g/nq) s sum_r P_t q^_r: the TEACHER's similarity, the student's queries as values, the student's scale at the write
-    a.res = tk; a.ldres = ldtk; a.str = tq; a.ldstr = ldtq; a.E = Et; a.logit_scale = teacher_logit_scale; a.lse = lse_t;
+    a.logit_scale = teacher_logit_scale; a.lse = lse_t;
     a.csign = -1.f;
-    launch_head<MODE_DK, LOSS_DISTILL>(a, s);
-    CE_LAUNCH_CHECK();
-    return 0;
+    return sweep<MODE_DK, LOSS_DISTILL>(a, TK, TQ, Et, NO_CAP, s);
 }
 
 extern "C" int ce_rowdot_sum(const float* x, long ldx, const float* y, long ldy, int n, int E, float* out, void* stream) {

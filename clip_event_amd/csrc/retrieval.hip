@@ -25,11 +25,12 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "head_sweep.hpp"
 #include "../../include/clip_event_hip.h"
 
-namespace {
+using namespace head_sweep;
 
-constexpr int HB = 32;          // rows per resident / streamed block
+namespace {
 
 struct TopkArgs {
     const float* q; long ldq; int nq;              // resident matrix: queries
@@ -42,8 +43,6 @@ struct TopkArgs {
     float* p_val; int* p_idx;                      // [splits][nq][KB] partial top-k
     int E, splits, blocks_per_split;
 };
-
-__device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // 32x32 C/D row of reg r
 
 // (yv, yi) comes before (xv, xi): score descending, then index ascending
 __device__ __forceinline__ bool before(float yv, int yi, float xv, int xi) { return yv > xv || (yv == xv && yi < xi); }
@@ -91,17 +90,6 @@ __device__ __forceinline__ void sim_tile(const float* arow, bool ivalid, const f
     }
 }
 
-template <int NW>
-__device__ __forceinline__ void load_residents(const TopkArgs& a, float* res_l, int r0, int tid) {
-    const int E = a.E, pitch = E + 4;
-    for (int idx = tid; idx < HB * (E / 4); idx += 64 * NW) {
-        const int r = idx / (E / 4), c = (idx - r * (E / 4)) * 4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (r0 + r < a.nq) v = *reinterpret_cast<const f32x4*>(a.q + (long)(r0 + r) * a.ldq + c);
-        *reinterpret_cast<f32x4*>(res_l + r * pitch + c) = v;
-    }
-}
-
 // pre-pass: tscore[r] = score(r, target[r]) from sim_tile, the target rows gathered as the streamed block (diagonal)
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void target_score_kernel(TopkArgs a) {
@@ -114,7 +102,7 @@ __global__ __launch_bounds__(64 * NW) void target_score_kernel(TopkArgs a) {
     const int j = lane & 31, h = lane >> 5;
     const int r0 = blockIdx.x * HB;
     const float scale = a.logit_scale ? __expf(*a.logit_scale) : 1.f;
-    load_residents<NW>(a, res_l, r0, tid);
+    load_residents<NW>(a.q, a.ldq, a.nq, nullptr, E, res_l, r0, tid);
     const bool jvalid = r0 + j < a.nq;
     const long tgt = jvalid ? a.target[r0 + j] : -1;
     const bool tvalid = tgt >= 0 && tgt < a.nk;                          // anything else is never dereferenced
@@ -139,7 +127,7 @@ __global__ __launch_bounds__(64 * NW) void topk_sweep_kernel(TopkArgs a) {
     const int j = lane & 31, h = lane >> 5;
     const int r0 = blockIdx.x * HB;
     const float scale = a.logit_scale ? __expf(*a.logit_scale) : 1.f;
-    load_residents<NW>(a, res_l, r0, tid);
+    load_residents<NW>(a.q, a.ldq, a.nq, nullptr, E, res_l, r0, tid);
     const bool jvalid = r0 + j < a.nq;
     const long tgt64 = (a.target && jvalid) ? a.target[r0 + j] : -1;
     const bool tvalid = tgt64 >= 0 && tgt64 < a.nk;
@@ -278,13 +266,8 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(TopkArgs a, int KB, int
     }
     if (lane == 0) {
         if (lse) {
-            float m = -INFINITY;
-            for (int s = 0; s < a.splits; ++s) m = fmaxf(m, a.p_ms[((long)s * a.nq + r) * 2]);
-            float l = 0.f;
-            for (int s = 0; s < a.splits; ++s) {
-                const float* p = a.p_ms + ((long)s * a.nq + r) * 2;
-                l += p[1] * __expf(p[0] - m);
-            }
+            float m, l;
+            merge_max_sum(a.p_ms + 2L * r, 2L * a.nq, a.splits, m, l);
             lse[r] = m + __logf(l);
         }
         if (rank) {
@@ -299,24 +282,13 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(TopkArgs a, int KB, int
     }
 }
 
-size_t sweep_lds_bytes(int E, int nw) { return (size_t)(HB * (E + 4) + nw * HB * 33) * 4; }
 size_t merge_lds_bytes(int nw, int kb) { return (size_t)(HB * 2 * nw * (2 * kb + 3) + 2 * HB * kb) * 4; }
 size_t topk_lds_bytes(int E, int nw, int kb) {
-    const size_t s = sweep_lds_bytes(E, nw), m = merge_lds_bytes(nw, kb);
+    const size_t s = lds_bytes(E, nw), m = merge_lds_bytes(nw, kb);
     return s > m ? s : m;
 }
 
 int bucket_of(int k) { return k == 1 ? 1 : (k <= 8 ? 8 : 16); }
-bool eight_waves(int E) { return E % 256 == 0 && E <= 768; }      // E = 1024 with eight partial tiles exceeds 160 KiB of LDS
-
-// splits of the key range: about two workgroups per CU when the queries alone do not fill the chip
-int resolve_splits(int nq, int nk, int splits) {
-    const int rb = ce_div_up(nq, HB), sblocks = ce_div_up(nk, HB);
-    if (splits == 0) splits = ce_div_up(512, rb);
-    if (splits > CE_INFONCE_MAX_SPLITS) splits = CE_INFONCE_MAX_SPLITS;
-    if (splits > sblocks) splits = sblocks;
-    return splits < 1 ? 1 : splits;
-}
 
 // rows of per-split partials the workspace holds.  splits = 0: a bound on nq * (the launcher's choice) that grows with nq
 // (the choice itself falls as nq grows): nq * ceil(512 / rb) <= 32 rb (512 / rb + 1)
@@ -355,23 +327,22 @@ extern "C" int ce_score_topk(const float* q, long ldq, int nq, const float* keys
                              int64_t* top_idx, float* lse, int64_t* rank, void* workspace, void* stream) {
     CE_CHECK_ARG(nq > 0 && nk > 0, "ce_score_topk: empty problem (nq = %d, nk = %d)", nq, nk);
     CE_CHECK_ARG(k >= 1 && k <= CE_TOPK_MAX, "ce_score_topk: k must be in 1..%d (got %d)", CE_TOPK_MAX, k);
-    CE_CHECK_ARG(E >= 128 && E % 128 == 0 && E <= 1024, "ce_score_topk: E must be a multiple of 128 in 128..1024 (got %d)", E);
     CE_CHECK_ARG(splits >= 0 && splits <= CE_INFONCE_MAX_SPLITS, "ce_score_topk: splits must be 0 or 1..%d (got %d)",
                  CE_INFONCE_MAX_SPLITS, splits);
-    CE_CHECK_ARG(q && keys, "ce_score_topk: null input");
+    if (int rc = check_features("ce_score_topk", "E", q, ldq, E)) return rc;
+    if (int rc = check_features("ce_score_topk", "E", keys, ldk, E)) return rc;
     CE_CHECK_ARG(top_val && top_idx && workspace, "ce_score_topk: null output");
     CE_CHECK_ARG(!rank || target, "ce_score_topk: rank needs target");
-    CE_CHECK_ARG(ldq >= E && ldk >= E && ldq % 4 == 0 && ldk % 4 == 0,
-                 "ce_score_topk: leading dimensions must be >= E and multiples of 4");
     const int kb = bucket_of(k);
     const long rows = partial_rows(nq, nk, splits);
     TopkArgs a{};
     a.q = q; a.ldq = ldq; a.nq = nq; a.keys = keys; a.ldk = ldk; a.nk = nk; a.E = E;
     a.logit_scale = logit_scale;
     a.target = rank ? (const long*)target : nullptr;          // without rank nobody reads the count
-    a.splits = resolve_splits(nq, nk, splits);
-    a.blocks_per_split = ce_div_up(ce_div_up(nk, HB), a.splits);
-    a.splits = ce_div_up(ce_div_up(nk, HB), a.blocks_per_split);
+    // splits of the key range: the caller's, or about two workgroups per CU when the queries alone do not fill the chip
+    const Splits sp = split_choice(nq, nk, splits, CE_INFONCE_MAX_SPLITS);
+    a.splits = sp.splits;
+    a.blocks_per_split = sp.blocks_per_split;
     a.tscore = (float*)workspace;
     a.p_ms = a.tscore + nq;
     a.p_cnt = (int*)(a.p_ms + 2 * rows);
@@ -379,8 +350,8 @@ extern "C" int ce_score_topk(const float* q, long ldq, int nq, const float* keys
     a.p_idx = (int*)(a.p_val + rows * kb);
     static std::once_flag flag;
     std::call_once(flag, [] {
-        allow_lds(target_score_kernel<4>, sweep_lds_bytes(1024, 4));
-        allow_lds(target_score_kernel<8>, sweep_lds_bytes(768, 8));
+        allow_lds(target_score_kernel<4>, lds_bytes(1024, 4));
+        allow_lds(target_score_kernel<8>, lds_bytes(768, 8));
         allow_lds(topk_sweep_kernel<4, 1>, topk_lds_bytes(1024, 4, 1));
         allow_lds(topk_sweep_kernel<4, 8>, topk_lds_bytes(1024, 4, 8));
         allow_lds(topk_sweep_kernel<4, 16>, topk_lds_bytes(1024, 4, 16));
@@ -389,10 +360,10 @@ extern "C" int ce_score_topk(const float* q, long ldq, int nq, const float* keys
         allow_lds(topk_sweep_kernel<8, 16>, topk_lds_bytes(768, 8, 16));
     });
     hipStream_t s = (hipStream_t)stream;
-    const bool eight = eight_waves(E);
+    const bool eight = eight_waves(E, E);
     if (a.target) {
-        if (eight) hipLaunchKernelGGL(target_score_kernel<8>, dim3(ce_div_up(nq, HB)), dim3(512), sweep_lds_bytes(E, 8), s, a);
-        else hipLaunchKernelGGL(target_score_kernel<4>, dim3(ce_div_up(nq, HB)), dim3(256), sweep_lds_bytes(E, 4), s, a);
+        if (eight) hipLaunchKernelGGL(target_score_kernel<8>, dim3(ce_div_up(nq, HB)), dim3(512), lds_bytes(E, 8), s, a);
+        else hipLaunchKernelGGL(target_score_kernel<4>, dim3(ce_div_up(nq, HB)), dim3(256), lds_bytes(E, 4), s, a);
         CE_LAUNCH_CHECK();
     }
     if (eight) launch_sweep_k<8>(a, kb, s);

@@ -100,12 +100,42 @@ class Distillation:
         return tfi, tft
 
 
+# Logits per direction from which the 'ce' criterion over the batch runs on the fused head, SURVEY 8(a) a6.  The fused head
+# exists to keep a big logits matrix out of HBM (config 3 per rank: 512 x 20,480); at B = 256, K = 1 the matrix is 256 KB and the
+# plain path's kernels are the faster ones (same-box A/B: 12.75 / 12.53 vs 12.79 / 12.67 ms/step), so the fused head takes over
+# from 2^17 logits per direction (256 x 1280 and 512 x 512: fused ahead by 0.1-0.2 ms).  CE_FUSED_HEAD=1 / 0 forces either.
+CE_FUSED_MIN_LOGITS = 1 << 17
+
 # Logits per direction from which distillation runs on the fused head.  Measured (DESIGN 4h "Numbers"), the fused head is the
 # slower one at every size up to 4096 x 20480 (1.1-1.9 x logits + CriterionDistill): there is no crossover in speed, so the switch
 # is by memory.  At 2^28 logits one fp32 matrix is 1 GiB and the materialised path holds four of them and two gradients of that
 # size, 6 GiB on the stretch where both towers' stashes are alive; from there the fused head, which holds none, takes over.
 # CE_FUSED_HEAD=1 / 0 forces either.
 DISTILL_FUSED_MIN_LOGITS = 1 << 28
+
+
+def head_route(kind, *, rows, keys, width, teacher_width=None, dist_global=False, overbatch=True, has_index_pos=True,
+               small_ok=False, fused_env="", small_env="1") -> str:
+    """Which head a loss runs on: "small" (the three-launch head), "fused" (no logits matrix) or "logits" (logits + criterion).
+    Pure: everything it looks at is an argument.  ``kind``: the criterion's ("ce", "sigmoid", "bce", "kl", ...) or "distill";
+    ``rows`` x ``keys``: local query rows and all key rows of one direction (the logits the direction would materialise);
+    ``width`` / ``teacher_width``: the feature widths; ``dist_global``: the keys are gathered across ranks; ``small_ok``:
+    ``small_head_ok`` of the shapes; ``fused_env`` / ``small_env``: the values of CE_FUSED_HEAD ("" unset) and CE_SMALL_HEAD."""
+    logits = rows * keys
+    if kind == "sigmoid":              # the fused head at every size the kernels take: the three-launch small head is 'ce'-only
+        return "fused" if fused_env != "0" and fused_head_ok(width) else "logits"
+    if kind == "distill":
+        fused = (fused_env != "0" and (fused_env == "1" or logits >= DISTILL_FUSED_MIN_LOGITS) and fused_head_ok(width)
+                 and fused_head_ok(teacher_width))
+        return "fused" if fused else "logits"
+    if kind != "ce" or not overbatch:
+        return "logits"
+    if fused_env != "0" and (fused_env == "1" or logits >= CE_FUSED_MIN_LOGITS) and fused_head_ok(width):
+        return "fused"
+    # below that size, in one process: the three-launch head (CE_SMALL_HEAD=0 or CE_FUSED_HEAD=0: the general logits + criterion path)
+    if not dist_global and fused_env == "" and small_env != "0" and has_index_pos and small_ok:
+        return "small"
+    return "logits"
 
 
 def _distill_from_features(model, distill, fi, ft, tfi, tft, index_pos, pair):
@@ -122,10 +152,8 @@ def _distill_from_features(model, distill, fi, ft, tfi, tft, index_pos, pair):
         fi_all, ft_all = pair
         with torch.no_grad():
             tfi_all, tft_all = D.gather_feature_pair(tfi.float().contiguous(), tft.float().contiguous())
-    force = os.environ.get("CE_FUSED_HEAD", "")
-    logits = int(fi.shape[0]) * int(ft_all.shape[0])
-    if (force != "0" and (force == "1" or logits >= DISTILL_FUSED_MIN_LOGITS) and fused_head_ok(int(fi.shape[1]))
-            and fused_head_ok(int(tfi.shape[1]))):
+    if head_route("distill", rows=int(fi.shape[0]), keys=int(ft_all.shape[0]), width=int(fi.shape[1]),
+                  teacher_width=int(tfi.shape[1]), fused_env=os.environ.get("CE_FUSED_HEAD", "")) == "fused":
         out = distill_losses(fi, ft, fi_all, ft_all, model.logit_scale, tfi, tft, tfi_all, tft_all, tls, index_pos)
     else:
         with torch.no_grad():                                                     # the teacher's side is a constant
@@ -153,24 +181,18 @@ def _contrastive_from_features(model, criterion, fi, ft, labels_per_image, label
 
 def _criterion_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, global_batch, pair):
     """``pair``: the gathered (image, text) features when the caller has them already, else None."""
-    # fused head: the 'ce' criterion over the batch, SURVEY 8(a) a6.  It exists to keep a big logits matrix out of HBM (config
-    # 3 per rank: 512 x 20,480); at B = 256, K = 1 the matrix is 256 KB and the plain path's kernels are the faster ones
-    # (same-box A/B: 12.75 / 12.53 vs 12.79 / 12.67 ms/step), so the fused head takes over from 2^17 logits per direction (256 x
-    # 1280 and 512 x 512: fused ahead by 0.1-0.2 ms).  CE_FUSED_HEAD=1 / 0 forces either.
-    force = os.environ.get("CE_FUSED_HEAD", "")
     dist_global = D.active() and global_batch
     if getattr(criterion, "kind", None) == "sigmoid":
         return _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_global, None if pair is None else pair[1])
-    logits = int(fi.shape[0]) * int(ft.shape[0]) * (D.world_size() if dist_global else 1)
-    fused = (force != "0" and (force == "1" or logits >= (1 << 17)) and getattr(criterion, "kind", None) == "ce"
-             and model.constrastive_overbatch and fused_head_ok(model.embed_dim))
-    # below that size, in one process: the three-launch head (CE_SMALL_HEAD=0 or CE_FUSED_HEAD=0: the general logits + criterion path)
-    if (not dist_global and not fused and force == "" and os.environ.get("CE_SMALL_HEAD", "1") != "0"
-            and getattr(criterion, "kind", None) == "ce" and model.constrastive_overbatch and index_pos is not None
-            and small_head_ok(fi, ft, index_pos)):
+    route = head_route(getattr(criterion, "kind", None), rows=int(fi.shape[0]),
+                       keys=int(ft.shape[0]) * (D.world_size() if dist_global else 1), width=model.embed_dim,
+                       dist_global=dist_global, overbatch=model.constrastive_overbatch, has_index_pos=index_pos is not None,
+                       small_ok=small_head_ok(fi, ft, index_pos), fused_env=os.environ.get("CE_FUSED_HEAD", ""),
+                       small_env=os.environ.get("CE_SMALL_HEAD", "1"))
+    if route == "small":
         return small_contrastive_losses(fi, ft, model.logit_scale, labels_per_image, labels_per_text, index_pos)
     fi_all, ft_all = pair if pair is not None else (D.gather_feature_pair(fi, ft) if dist_global else (fi, ft))
-    if fused:
+    if route == "fused":
         return fused_contrastive_losses(fi, ft, fi_all, ft_all, model.logit_scale, labels_per_image, labels_per_text, index_pos)
     overbatch = model.constrastive_overbatch
     if dist_global:
@@ -195,7 +217,8 @@ def _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_glob
         raise RuntimeError("the sigmoid loss needs a logit bias: call model.enable_logit_bias() before building the optimiser")
     if ft_all is None:
         ft_all = D.gather_features(ft) if dist_global else ft
-    if os.environ.get("CE_FUSED_HEAD", "") != "0" and fused_head_ok(model.embed_dim):
+    if head_route("sigmoid", rows=int(fi.shape[0]), keys=int(ft_all.shape[0]), width=model.embed_dim,
+                  fused_env=os.environ.get("CE_FUSED_HEAD", "")) == "fused":
         return sigmoid_contrastive_losses(fi, ft_all, model.logit_scale, bias, labels_per_image)
     lpi, _ = logits_from_features(fi, ft_all, model.logit_scale, True, want="image")
     return criterion(lpi, None, labels_per_image, constrastive_overbatch=True, logit_bias=bias)

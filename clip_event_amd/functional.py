@@ -620,92 +620,95 @@ def logits_from_features(image_features, text_features, logit_scale, overbatch: 
     return LogitsFn.apply(image_features, text_features, logit_scale, bool(overbatch), want)
 
 
+# ---- the fused loss heads: one autograd node per loss, one or two directions over a pair of feature matrices ---------------
+# A node takes two raw feature matrices a, b.  Direction 0 scores query rows of a (the rows ``sel``, or all) against every row of
+# b; direction 1, when asked for, rows of b against every row of a (one process: the keys of one direction are the queries of the
+# other).  Each matrix is normalised once however many directions read it, every backward call adds into one gradient buffer per
+# matrix, and one ``ce_l2norm_bwd`` per matrix follows.  A node returns one loss per direction (a bare tensor when there is one).
+# The helpers below are that frame; what a loss calls in its forward and backward stays written out in its node.
+
+def _head_normalise(a, b):
+    """((a^, b^), (1 / |a|, 1 / |b|)): both matrices fp32 and L2-normalised row by row."""
+    a, b = _f32(a), _f32(b)
+    an, inv_a = _l2norm(a)
+    bn, inv_b = _l2norm(b)
+    return (an, bn), (inv_a, inv_b)
+
+
+def _head_directions(mats, *given):
+    """The directions of a node as its library calls read them, [(iq, nq, labels, sel)]: direction t takes its queries from
+    ``mats[iq]`` (iq = t) and its keys from ``mats[1 - iq]``; ``given`` holds one (labels, sel) per direction."""
+    dev = mats[0].device
+    dirs = []
+    for iq, (labels, sel) in enumerate(given):
+        sel = _index64(sel, dev)
+        dirs.append((iq, mats[iq].shape[0] if sel is None else sel.shape[0], _index64(labels, dev), sel))
+    return dirs
+
+
+def _head_upstream(gs, dev):
+    """The upstream gradients of a node's losses as one fp32 tensor [directions] (a loss nobody used: 0)."""
+    if len(gs) == 1:
+        return gs[0].contiguous().float().reshape(1)
+    zero = torch.zeros(len(gs), dtype=torch.float32, device=dev)
+    return torch.stack([zero[t] if g is None else g.float().reshape(()) for t, g in enumerate(gs)])
+
+
+def _head_grad_buffers(mats):
+    """((da^, db^), four scalar slots): the accumulation targets of a backward, zeroed in ONE fill."""
+    na, nb = mats[0].numel(), mats[1].numel()
+    acc = torch.zeros(na + nb + 4, dtype=torch.float32, device=mats[0].device)
+    return (acc[:na].view_as(mats[0]), acc[na:na + nb].view_as(mats[1])), acc[na + nb:]
+
+
+def _head_result(losses):
+    return losses[0] if losses.shape[0] == 1 else (losses[0], losses[1])
+
+
 class InfoNCEFn(torch.autograd.Function):
-    """mean_r CE(s q^_r . k^_c, label_r) over the query rows ``sel`` (index_pos) of ``q`` against all rows of ``k`` --
+    """mean_r CE(s q^_r . k^_c, label_r) over the query rows ``sel_ab`` (index_pos) of ``a`` against all rows of ``b`` --
     model_clip.py:496-521 + :633-662 for one direction -- without the [nq, nk] logits matrix (``ce_infonce_fwd/bwd``:
-    similarity tiles on the fp32 matrix instruction, online log-sum-exp, backward from the saved log-sum-exp)."""
+    similarity tiles on the fp32 matrix instruction, online log-sum-exp, backward from the saved log-sum-exp).  With
+    ``labels_ba`` also the other direction on the same pair of matrices, the rows ``sel_ba`` of ``b`` against all rows of ``a``:
+    the same kernels and arithmetic as two nodes, 14 launches instead of 26 on the stretch between the towers' forward and
+    backward, where nothing else can run.  Across ranks, where queries and keys are different tensors: one direction per node."""
 
     @staticmethod
-    def forward(ctx, q, k, logit_scale, labels, sel):
-        dev = q.device
-        q, k = _f32(q), _f32(k)
-        E = q.shape[1]
-        qn, inv_q = _l2norm(q)
-        kn, inv_k = _l2norm(k)
-        labels, sel = _index64(labels, dev), _index64(sel, dev)
-        nq = q.shape[0] if sel is None else sel.shape[0]
+    def forward(ctx, a, b, logit_scale, labels_ab, sel_ab, labels_ba=None, sel_ba=None):
+        cl, s = lib(), stream()
+        dev = a.device
+        mats, invs = _head_normalise(a, b)
+        E = mats[0].shape[1]
+        dirs = _head_directions(mats, (labels_ab, sel_ab), *([] if labels_ba is None else [(labels_ba, sel_ba)]))
         ls = logit_scale.detach().reshape(1)
-        lse = _empty((nq,), torch.float32, dev)
-        loss = torch.zeros((), dtype=torch.float32, device=dev)
-        ws = _infonce_workspace(nq, dev)
-        check(lib().ce_infonce_fwd(ptr(qn), E, ptr(sel), nq, ptr(kn), E, k.shape[0], E, ptr(ls), ptr(labels), ptr(lse), ptr(loss),
-                                   ptr(ws), stream()), "ce_infonce_fwd")
-        ctx.saved = (qn, kn, inv_q, inv_k, ls, labels, sel, lse)
-        return loss
+        losses = torch.zeros(len(dirs), dtype=torch.float32, device=dev)                   # the merge kernel adds the rows' terms
+        ws = _infonce_workspace(max(nq for _, nq, _, _ in dirs), dev)
+        lses = []
+        for t, (iq, nq, labels, sel) in enumerate(dirs):
+            q, k = mats[iq], mats[1 - iq]
+            lses.append(_empty((nq,), torch.float32, dev))
+            check(cl.ce_infonce_fwd(ptr(q), E, ptr(sel), nq, ptr(k), E, k.shape[0], E, ptr(ls), ptr(labels), ptr(lses[t]),
+                                    ptr(losses[t:t + 1]), ptr(ws), s), "ce_infonce_fwd")
+        ctx.saved = (mats, invs, ls, dirs, lses)
+        return _head_result(losses)
 
     @staticmethod
-    def backward(ctx, g):
-        qn, kn, inv_q, inv_k, ls, labels, sel, lse = ctx.saved
-        E = qn.shape[1]
-        nq = qn.shape[0] if sel is None else sel.shape[0]
-        g = g.contiguous().float().reshape(1)
-        dqn, dkn = torch.zeros_like(qn), torch.zeros_like(kn)
-        dls = torch.zeros(1, dtype=torch.float32, device=qn.device)
-        check(lib().ce_infonce_bwd(ptr(qn), E, ptr(sel), nq, ptr(kn), E, kn.shape[0], E, ptr(ls), ptr(labels), ptr(lse), ptr(g),
-                                   ptr(dqn), ptr(dkn), ptr(dls), stream()), "ce_infonce_bwd")
-        return _l2norm_bwd(dqn, qn, inv_q), _l2norm_bwd(dkn, kn, inv_k), dls.reshape(()), None, None
+    def backward(ctx, *gs):
+        cl, s = lib(), stream()
+        mats, invs, ls, dirs, lses = ctx.saved
+        E = mats[0].shape[1]
+        g = _head_upstream(gs, mats[0].device)
+        grads, scalars = _head_grad_buffers(mats)                                           # da^ | db^ | dlogit_scale
+        for t, (iq, nq, labels, sel) in enumerate(dirs):
+            q, k = mats[iq], mats[1 - iq]
+            check(cl.ce_infonce_bwd(ptr(q), E, ptr(sel), nq, ptr(k), E, k.shape[0], E, ptr(ls), ptr(labels), ptr(lses[t]),
+                                    ptr(g[t:t + 1]), ptr(grads[iq]), ptr(grads[1 - iq]), ptr(scalars[0:1]), s), "ce_infonce_bwd")
+        return (_l2norm_bwd(grads[0], mats[0], invs[0]), _l2norm_bwd(grads[1], mats[1], invs[1]), scalars[0].reshape(()),
+                None, None, None, None)
 
 
 def fused_head_ok(embed_dim: int) -> bool:
     return embed_dim % 128 == 0 and 128 <= embed_dim <= 1024
-
-
-class InfoNCEPairFn(torch.autograd.Function):
-    """Both directions of the batch criterion on ONE pair of feature matrices (single process: the keys of one direction are
-    the queries of the other): loss_i = CE(s I^ T^T, labels_i), loss_t = CE over the ``sel`` rows of s T^ I^T.  Same kernels
-    and the same arithmetic as two ``InfoNCEFn`` nodes, but each matrix is normalised once, both backward directions
-    accumulate into one pair of gradient buffers (``ce_infonce_bwd`` adds), and one ``ce_l2norm_bwd`` per matrix follows:
-    14 launches instead of 26 on the stretch between the towers' forward and backward, where nothing else can run."""
-
-    @staticmethod
-    def forward(ctx, fi, ft, logit_scale, labels_i, labels_t, sel):
-        cl, s = lib(), stream()
-        dev = fi.device
-        fi, ft = _f32(fi), _f32(ft)
-        E = fi.shape[1]
-        In, inv_i = _l2norm(fi)
-        Tn, inv_t = _l2norm(ft)
-        labels_i, labels_t, sel = _index64(labels_i, dev), _index64(labels_t, dev), _index64(sel, dev)
-        nqi = fi.shape[0]
-        nqt = ft.shape[0] if sel is None else sel.shape[0]
-        ls = logit_scale.detach().reshape(1)
-        lse_i, lse_t = _empty((nqi,), torch.float32, dev), _empty((nqt,), torch.float32, dev)
-        losses = torch.zeros(2, dtype=torch.float32, device=dev)
-        ws = _infonce_workspace(max(nqi, nqt), dev)
-        check(cl.ce_infonce_fwd(ptr(In), E, None, nqi, ptr(Tn), E, ft.shape[0], E, ptr(ls), ptr(labels_i), ptr(lse_i),
-                                ptr(losses[0:1]), ptr(ws), s), "ce_infonce_fwd(image)")
-        check(cl.ce_infonce_fwd(ptr(Tn), E, ptr(sel), nqt, ptr(In), E, fi.shape[0], E, ptr(ls), ptr(labels_t), ptr(lse_t),
-                                ptr(losses[1:2]), ptr(ws), s), "ce_infonce_fwd(text)")
-        ctx.saved = (In, Tn, inv_i, inv_t, ls, labels_i, labels_t, sel, lse_i, lse_t)
-        return losses[0], losses[1]
-
-    @staticmethod
-    def backward(ctx, g_i, g_t):
-        cl, s = lib(), stream()
-        In, Tn, inv_i, inv_t, ls, labels_i, labels_t, sel, lse_i, lse_t = ctx.saved
-        dev = In.device
-        E = In.shape[1]
-        nqi = In.shape[0]
-        nqt = Tn.shape[0] if sel is None else sel.shape[0]
-        zero = torch.zeros(2, dtype=torch.float32, device=dev)
-        g = torch.stack([zero[0] if g_i is None else g_i.float().reshape(()), zero[1] if g_t is None else g_t.float().reshape(())])
-        acc = torch.zeros(In.numel() + Tn.numel() + 4, dtype=torch.float32, device=dev)         # dIn | dTn | dlogit_scale: one fill
-        dIn, dTn, dls = acc[:In.numel()].view_as(In), acc[In.numel():In.numel() + Tn.numel()].view_as(Tn), acc[In.numel() + Tn.numel():]
-        check(cl.ce_infonce_bwd(ptr(In), E, None, nqi, ptr(Tn), E, Tn.shape[0], E, ptr(ls), ptr(labels_i), ptr(lse_i), ptr(g[0:1]),
-                                ptr(dIn), ptr(dTn), ptr(dls), s), "ce_infonce_bwd(image)")
-        check(cl.ce_infonce_bwd(ptr(Tn), E, ptr(sel), nqt, ptr(In), E, In.shape[0], E, ptr(ls), ptr(labels_t), ptr(lse_t), ptr(g[1:2]),
-                                ptr(dTn), ptr(dIn), ptr(dls), s), "ce_infonce_bwd(text)")
-        return _l2norm_bwd(dIn, In, inv_i), _l2norm_bwd(dTn, Tn, inv_t), dls[0].reshape(()), None, None, None
 
 
 def small_head_ok(fi, ft, index_pos) -> bool:
@@ -759,7 +762,7 @@ def fused_contrastive_losses(fi, ft, fi_all, ft_all, logit_scale, labels_per_ima
     """``CriterionContrastive('ce')`` over the batch on raw features: loss_i = CE(s I^ T_all^T, labels_per_image),
     loss_t = CE over the ``index_pos`` rows of s T^ I_all^T (model_clip.py:633-662), the logits never materialised."""
     if fi_all is fi and ft_all is ft:          # one process: one node for both directions
-        loss_i, loss_t = InfoNCEPairFn.apply(fi, ft, logit_scale, labels_per_image, labels_per_text, index_pos)
+        loss_i, loss_t = InfoNCEFn.apply(fi, ft, logit_scale, labels_per_image, None, labels_per_text, index_pos)
         return {"loss_i": loss_i, "loss_t": loss_t}
     return {"loss_i": InfoNCEFn.apply(fi, ft_all, logit_scale, labels_per_image, None),
             "loss_t": InfoNCEFn.apply(ft, fi_all, logit_scale, labels_per_text, index_pos)}
@@ -767,38 +770,42 @@ def fused_contrastive_losses(fi, ft, fi_all, ft_all, logit_scale, labels_per_ima
 
 class SigmoidHeadFn(torch.autograd.Function):
     """The sigmoid pairwise loss of SigLIP, -(1/nq) sum_r sum_c log sigma(z (s q^_r . k^_c + b)) with z = +1 where c is the label
-    of query r and -1 elsewhere, over the query rows ``sel`` of ``q`` against all rows of ``k`` -- without the [nq, nk] logits
-    matrix (``ce_sigmoid_head_fwd/bwd``: three sweeps, nothing saved but the normalised features).  Returns the scalar loss;
-    gradients for both raw feature matrices, ``logit_scale`` and ``logit_bias``."""
+    of query r and -1 elsewhere, over the query rows ``sel_ab`` of ``a`` against all rows of ``b`` -- without the [nq, nk] logits
+    matrix (``ce_sigmoid_head_fwd/bwd``: three sweeps, nothing saved but the normalised features); with ``labels_ba`` also over the
+    rows ``sel_ba`` of ``b`` against all rows of ``a``.  Gradients for both raw feature matrices, ``logit_scale`` and
+    ``logit_bias``."""
 
     @staticmethod
-    def forward(ctx, q, k, logit_scale, logit_bias, labels, sel):
-        dev = q.device
-        q, k = _f32(q), _f32(k)
-        E = q.shape[1]
-        qn, inv_q = _l2norm(q)
-        kn, inv_k = _l2norm(k)
-        labels, sel = _index64(labels, dev), _index64(sel, dev)
-        nq = q.shape[0] if sel is None else sel.shape[0]
+    def forward(ctx, a, b, logit_scale, logit_bias, labels_ab, sel_ab, labels_ba=None, sel_ba=None):
+        cl, s = lib(), stream()
+        dev = a.device
+        mats, invs = _head_normalise(a, b)
+        E = mats[0].shape[1]
+        dirs = _head_directions(mats, (labels_ab, sel_ab), *([] if labels_ba is None else [(labels_ba, sel_ba)]))
         ls, lb = logit_scale.detach().reshape(1), logit_bias.detach().float().reshape(1)
-        loss = _empty((), torch.float32, dev)
-        ws = _empty((lib().ce_sigmoid_head_workspace_bytes(nq, k.shape[0]),), torch.uint8, dev)
-        check(lib().ce_sigmoid_head_fwd(ptr(qn), E, ptr(sel), nq, ptr(kn), E, k.shape[0], E, ptr(ls), ptr(lb), ptr(labels), ptr(loss),
-                                        ptr(ws), stream()), "ce_sigmoid_head_fwd")
-        ctx.saved = (qn, kn, inv_q, inv_k, ls, lb, labels, sel)
-        return loss
+        losses = _empty((len(dirs),), torch.float32, dev)
+        for t, (iq, nq, labels, sel) in enumerate(dirs):
+            q, k = mats[iq], mats[1 - iq]
+            ws = _empty((cl.ce_sigmoid_head_workspace_bytes(nq, k.shape[0]),), torch.uint8, dev)
+            check(cl.ce_sigmoid_head_fwd(ptr(q), E, ptr(sel), nq, ptr(k), E, k.shape[0], E, ptr(ls), ptr(lb), ptr(labels),
+                                         ptr(losses[t:t + 1]), ptr(ws), s), "ce_sigmoid_head_fwd")
+        ctx.saved = (mats, invs, ls, lb, dirs)
+        return _head_result(losses)
 
     @staticmethod
-    def backward(ctx, g):
-        qn, kn, inv_q, inv_k, ls, lb, labels, sel = ctx.saved
-        E = qn.shape[1]
-        nq = qn.shape[0] if sel is None else sel.shape[0]
-        g = g.contiguous().float().reshape(1)
-        acc = torch.zeros(qn.numel() + kn.numel() + 4, dtype=torch.float32, device=qn.device)     # dqn | dkn | dscale, dbias: one fill
-        dqn, dkn, ds = acc[:qn.numel()].view_as(qn), acc[qn.numel():qn.numel() + kn.numel()].view_as(kn), acc[qn.numel() + kn.numel():]
-        check(lib().ce_sigmoid_head_bwd(ptr(qn), E, ptr(sel), nq, ptr(kn), E, kn.shape[0], E, ptr(ls), ptr(lb), ptr(labels), ptr(g),
-                                        ptr(dqn), ptr(dkn), ptr(ds[0:1]), ptr(ds[1:2]), stream()), "ce_sigmoid_head_bwd")
-        return _l2norm_bwd(dqn, qn, inv_q), _l2norm_bwd(dkn, kn, inv_k), ds[0].reshape(()), ds[1].reshape(()), None, None
+    def backward(ctx, *gs):
+        cl, s = lib(), stream()
+        mats, invs, ls, lb, dirs = ctx.saved
+        E = mats[0].shape[1]
+        g = _head_upstream(gs, mats[0].device)
+        grads, scalars = _head_grad_buffers(mats)                                           # da^ | db^ | dscale, dbias
+        for t, (iq, nq, labels, sel) in enumerate(dirs):
+            q, k = mats[iq], mats[1 - iq]
+            check(cl.ce_sigmoid_head_bwd(ptr(q), E, ptr(sel), nq, ptr(k), E, k.shape[0], E, ptr(ls), ptr(lb), ptr(labels),
+                                         ptr(g[t:t + 1]), ptr(grads[iq]), ptr(grads[1 - iq]), ptr(scalars[0:1]), ptr(scalars[1:2]), s),
+                  "ce_sigmoid_head_bwd")
+        return (_l2norm_bwd(grads[0], mats[0], invs[0]), _l2norm_bwd(grads[1], mats[1], invs[1]), scalars[0].reshape(()),
+                scalars[1].reshape(()), None, None, None, None)
 
 
 def sigmoid_contrastive_losses(fi, ft_all, logit_scale, logit_bias, labels_per_image):
@@ -815,113 +822,68 @@ def _rowdot_sum(x, y, out):
     check(lib().ce_rowdot_sum(ptr(x), x.shape[1], ptr(y), y.shape[1], x.shape[0], x.shape[1], ptr(out), stream()), "ce_rowdot_sum")
 
 
-def _distill_fwd(q, sel, nq, k, ls, tq, tk, tls, loss, ws):
-    """One direction's forward on normalised matrices: (lse_s, lse_t, v) for the backward, the loss written into ``loss``."""
-    dev = q.device
-    stats = _empty((2, nq, 2), torch.float32, dev)                                         # lse_s | lse_t, each (max, log sum) per row
-    v = torch.zeros((nq, q.shape[1]), dtype=torch.float32, device=dev)                     # an accumulation target
-    check(lib().ce_distill_head_fwd(ptr(q), q.shape[1], ptr(sel), nq, ptr(k), k.shape[1], k.shape[0], q.shape[1], ptr(ls),
-                                    ptr(tq), tq.shape[1], ptr(tk), tk.shape[1], tq.shape[1], ptr(tls), ptr(stats[0]), ptr(stats[1]),
-                                    ptr(v), ptr(loss), ptr(ws), stream()), "ce_distill_head_fwd")
-    return stats, v
-
-
-def _distill_bwd(q, sel, nq, k, ls, tq, tk, tls, stats, v, g, dq, dk):
-    check(lib().ce_distill_head_bwd(ptr(q), q.shape[1], ptr(sel), nq, ptr(k), k.shape[1], k.shape[0], q.shape[1], ptr(ls),
-                                    ptr(tq), tq.shape[1], ptr(tk), tk.shape[1], tq.shape[1], ptr(tls), ptr(stats[0]), ptr(stats[1]),
-                                    ptr(v), ptr(g), ptr(dq), ptr(dk), stream()), "ce_distill_head_bwd")
-
-
 def _check_teacher(what, s, t):
     if t.dim() != 2 or t.shape[0] != s.shape[0]:
         raise RuntimeError(f"distillation: teacher {what} features {tuple(t.shape)} do not match the student's {tuple(s.shape)} row for row")
 
 
 class DistillHeadFn(torch.autograd.Function):
-    """Distillation loss of one direction (open_clip's ``DistillClipLoss.dist_loss``),
-    -(softmax(st tq^ tk^T) * log_softmax(s q^ k^T)).sum(1).mean() over the query rows ``sel`` of ``q`` against all rows of ``k``,
-    without either logits matrix (``ce_distill_head_fwd/bwd``).  ``tq`` / ``tk`` are the teacher's features for the same rows as
-    ``q`` / ``k`` (any width the head takes) and ``teacher_logit_scale`` its log scale: constants.  This is the form for keys
-    gathered across ranks.  Gradients for ``q``, ``k`` and ``logit_scale``; the latter is sum_r <q^_r, dq^_r>
-    (``ce_rowdot_sum`` over the gradient buffer this node owns)."""
+    """Distillation loss (open_clip's ``DistillClipLoss.dist_loss``),
+    -(softmax(st ta^ tb^T) * log_softmax(s a^ b^T)).sum(1).mean() over the query rows ``sel_ab`` of ``a`` against all rows of ``b``,
+    without either logits matrix (``ce_distill_head_fwd/bwd``).  ``ta`` / ``tb`` are the teacher's features for the same rows as
+    ``a`` / ``b`` (any width the head takes) and ``teacher_logit_scale`` its log scale: constants.  ``both``: also the other
+    direction on the same matrices, the rows ``sel_ba`` of ``b`` against all rows of ``a`` (one process); one direction is the form
+    for keys gathered across ranks.  Gradients for ``a``, ``b`` and ``logit_scale``; the latter is sum_r <a^_r, da^_r>
+    (``ce_rowdot_sum`` over the accumulated gradient buffer this node owns: the queries of one direction, the keys of the other)."""
 
     @staticmethod
-    def forward(ctx, q, k, logit_scale, tq, tk, teacher_logit_scale, sel):
-        dev = q.device
-        _check_teacher("query", q, tq)
-        _check_teacher("key", k, tk)
-        q, k = _f32(q), _f32(k)
-        qn, inv_q = _l2norm(q)
-        kn, inv_k = _l2norm(k)
-        tqn, tkn = _teacher_norm(tq), _teacher_norm(tk)
-        sel = _index64(sel, dev)
-        nq = q.shape[0] if sel is None else sel.shape[0]
+    def forward(ctx, a, b, logit_scale, ta, tb, teacher_logit_scale, sel_ab, both=False, sel_ba=None):
+        cl, s = lib(), stream()
+        dev = a.device
+        _check_teacher("first", a, ta)
+        _check_teacher("second", b, tb)
+        mats, invs = _head_normalise(a, b)
+        tmats = (_teacher_norm(ta), _teacher_norm(tb))
+        Es, Et = mats[0].shape[1], tmats[0].shape[1]
+        dirs = _head_directions(mats, (None, sel_ab), *([(None, sel_ba)] if both else []))
         ls, tls = logit_scale.detach().reshape(1), teacher_logit_scale.detach().float().reshape(1).to(dev)
-        loss = _empty((), torch.float32, dev)
-        ws = _empty((lib().ce_distill_head_workspace_bytes(nq),), torch.uint8, dev)
-        stats, v = _distill_fwd(qn, sel, nq, kn, ls, tqn, tkn, tls, loss, ws)
-        ctx.saved = (qn, kn, inv_q, inv_k, ls, tqn, tkn, tls, sel, stats, v)
-        return loss
+        losses = _empty((len(dirs),), torch.float32, dev)
+        ws = _empty((cl.ce_distill_head_workspace_bytes(max(nq for _, nq, _, _ in dirs)),), torch.uint8, dev)
+        kept = []
+        for t, (iq, nq, _, sel) in enumerate(dirs):
+            q, k, tq, tk = mats[iq], mats[1 - iq], tmats[iq], tmats[1 - iq]
+            stats = _empty((2, nq, 2), torch.float32, dev)                                 # lse_s | lse_t, each (max, log sum) per row
+            v = torch.zeros((nq, Es), dtype=torch.float32, device=dev)                     # an accumulation target
+            check(cl.ce_distill_head_fwd(ptr(q), Es, ptr(sel), nq, ptr(k), Es, k.shape[0], Es, ptr(ls), ptr(tq), Et, ptr(tk), Et, Et,
+                                         ptr(tls), ptr(stats[0]), ptr(stats[1]), ptr(v), ptr(losses[t:t + 1]), ptr(ws), s),
+                  "ce_distill_head_fwd")
+            kept.append((stats, v))
+        ctx.saved = (mats, invs, tmats, ls, tls, dirs, kept)
+        return _head_result(losses)
 
     @staticmethod
-    def backward(ctx, g):
-        qn, kn, inv_q, inv_k, ls, tqn, tkn, tls, sel, stats, v = ctx.saved
-        nq = qn.shape[0] if sel is None else sel.shape[0]
-        g = g.contiguous().float().reshape(1)
-        acc = torch.zeros(qn.numel() + kn.numel() + 4, dtype=torch.float32, device=qn.device)     # dqn | dkn | dscale: one fill
-        dqn, dkn, dls = acc[:qn.numel()].view_as(qn), acc[qn.numel():qn.numel() + kn.numel()].view_as(kn), acc[qn.numel() + kn.numel():]
-        _distill_bwd(qn, sel, nq, kn, ls, tqn, tkn, tls, stats, v, g, dqn, dkn)
-        _rowdot_sum(qn, dqn, dls)
-        return _l2norm_bwd(dqn, qn, inv_q), _l2norm_bwd(dkn, kn, inv_k), dls[0].reshape(()), None, None, None, None
-
-
-class DistillPairFn(torch.autograd.Function):
-    """Both directions of the distillation loss on ONE pair of feature matrices, as ``InfoNCEPairFn``: loss_dist_i over the
-    images against all texts, loss_dist_t over the ``sel`` text rows against all images.  Each matrix is normalised once, both
-    directions add into one gradient buffer per matrix, one ``ce_l2norm_bwd`` each; sum <I^, dI^> over the accumulated image
-    buffer is the ``logit_scale`` gradient of both directions at once (queries of one, keys of the other)."""
-
-    @staticmethod
-    def forward(ctx, fi, ft, logit_scale, tfi, tft, teacher_logit_scale, sel):
-        dev = fi.device
-        _check_teacher("image", fi, tfi)
-        _check_teacher("text", ft, tft)
-        fi, ft = _f32(fi), _f32(ft)
-        In, inv_i = _l2norm(fi)
-        Tn, inv_t = _l2norm(ft)
-        tIn, tTn = _teacher_norm(tfi), _teacher_norm(tft)
-        sel = _index64(sel, dev)
-        nqi = fi.shape[0]
-        nqt = ft.shape[0] if sel is None else sel.shape[0]
-        ls, tls = logit_scale.detach().reshape(1), teacher_logit_scale.detach().float().reshape(1).to(dev)
-        losses = _empty((2,), torch.float32, dev)
-        ws = _empty((lib().ce_distill_head_workspace_bytes(max(nqi, nqt)),), torch.uint8, dev)
-        saved_i = _distill_fwd(In, None, nqi, Tn, ls, tIn, tTn, tls, losses[0:1], ws)
-        saved_t = _distill_fwd(Tn, sel, nqt, In, ls, tTn, tIn, tls, losses[1:2], ws)
-        ctx.saved = (In, Tn, inv_i, inv_t, ls, tIn, tTn, tls, sel, saved_i, saved_t)
-        return losses[0], losses[1]
-
-    @staticmethod
-    def backward(ctx, g_i, g_t):
-        In, Tn, inv_i, inv_t, ls, tIn, tTn, tls, sel, saved_i, saved_t = ctx.saved
-        dev = In.device
-        nqi = In.shape[0]
-        nqt = Tn.shape[0] if sel is None else sel.shape[0]
-        zero = torch.zeros(2, dtype=torch.float32, device=dev)
-        g = torch.stack([zero[0] if g_i is None else g_i.float().reshape(()), zero[1] if g_t is None else g_t.float().reshape(())])
-        acc = torch.zeros(In.numel() + Tn.numel() + 4, dtype=torch.float32, device=dev)         # dIn | dTn | dlogit_scale: one fill
-        dIn, dTn, dls = acc[:In.numel()].view_as(In), acc[In.numel():In.numel() + Tn.numel()].view_as(Tn), acc[In.numel() + Tn.numel():]
-        _distill_bwd(In, None, nqi, Tn, ls, tIn, tTn, tls, *saved_i, g[0:1], dIn, dTn)
-        _distill_bwd(Tn, sel, nqt, In, ls, tTn, tIn, tls, *saved_t, g[1:2], dTn, dIn)
-        _rowdot_sum(In, dIn, dls)
-        return _l2norm_bwd(dIn, In, inv_i), _l2norm_bwd(dTn, Tn, inv_t), dls[0].reshape(()), None, None, None, None
+    def backward(ctx, *gs):
+        cl, s = lib(), stream()
+        mats, invs, tmats, ls, tls, dirs, kept = ctx.saved
+        Es, Et = mats[0].shape[1], tmats[0].shape[1]
+        g = _head_upstream(gs, mats[0].device)
+        grads, scalars = _head_grad_buffers(mats)                                           # da^ | db^ | dlogit_scale
+        for t, (iq, nq, _, sel) in enumerate(dirs):
+            q, k, tq, tk = mats[iq], mats[1 - iq], tmats[iq], tmats[1 - iq]
+            stats, v = kept[t]
+            check(cl.ce_distill_head_bwd(ptr(q), Es, ptr(sel), nq, ptr(k), Es, k.shape[0], Es, ptr(ls), ptr(tq), Et, ptr(tk), Et, Et,
+                                         ptr(tls), ptr(stats[0]), ptr(stats[1]), ptr(v), ptr(g[t:t + 1]), ptr(grads[iq]),
+                                         ptr(grads[1 - iq]), s), "ce_distill_head_bwd")
+        _rowdot_sum(mats[0], grads[0], scalars)
+        return (_l2norm_bwd(grads[0], mats[0], invs[0]), _l2norm_bwd(grads[1], mats[1], invs[1]), scalars[0].reshape(()),
+                None, None, None, None, None, None)
 
 
 def distill_losses(fi, ft, fi_all, ft_all, logit_scale, tfi, tft, tfi_all, tft_all, teacher_logit_scale, index_pos):
     """The two distillation terms on raw features, the logits never materialised: the local images against all texts and the
     ``index_pos`` rows of the local texts against all images, student and teacher alike."""
     if fi_all is fi and ft_all is ft:          # one process: one node for both directions
-        li, lt = DistillPairFn.apply(fi, ft, logit_scale, tfi, tft, teacher_logit_scale, index_pos)
+        li, lt = DistillHeadFn.apply(fi, ft, logit_scale, tfi, tft, teacher_logit_scale, None, True, index_pos)
         return {"loss_dist_i": li, "loss_dist_t": lt}
     return {"loss_dist_i": DistillHeadFn.apply(fi, ft_all, logit_scale, tfi, tft_all, teacher_logit_scale, None),
             "loss_dist_t": DistillHeadFn.apply(ft, fi_all, logit_scale, tft, tfi_all, teacher_logit_scale, index_pos)}

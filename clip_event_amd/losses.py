@@ -163,7 +163,7 @@ class CriterionDistill(nn.Module):
     """The distillation terms of open_clip's ``DistillClipLoss`` on materialised logits: for each direction
     -(softmax(teacher logits) * log_softmax(logits)).sum(1).mean(), the text direction over the ``index_pos`` rows, times
     ``weight``.  The teacher's matrices are constants.  This is the general path, for embed dims the fused head
-    (``functional.DistillPairFn``) does not take, and its cross-check on the device; ``engine`` picks between them."""
+    (``functional.DistillHeadFn``) does not take, and its cross-check on the device; ``engine`` picks between them."""
 
     kind = "distill"
 

@@ -62,7 +62,7 @@ def _distill(weight=1.0, seed=77):
 
 @pytest.mark.parametrize("K", [1, 3])
 def test_fused_distillation_equals_logits_plus_criterion_path(K, monkeypatch):
-    """``train_step`` through ``DistillPairFn`` and through logits + ``CriterionDistill`` (CE_FUSED_HEAD=0): the same losses (1e-5)
+    """``train_step`` through ``DistillHeadFn`` and through logits + ``CriterionDistill`` (CE_FUSED_HEAD=0): the same losses (1e-5)
     and flat gradients (rel-L2 5e-3: the towers' backward rounds the feature gradient to bf16 first), the scale gradient, which no
     tower touches, to 2e-5 -- test_sigmoid_gpu.py's bounds -- and the losses equal the fp64 reference on the models' own features."""
     from clip_event_amd import engine

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """The loss heads alone, forward + backward, on synthetic features: the fused sigmoid pairwise head (``SigmoidHeadFn``: one
-direction, three sweeps) against the fused InfoNCE pair head (``InfoNCEPairFn``: both directions, six sweeps and two merges) at
+direction, three sweeps) against the fused InfoNCE head with both directions (``InfoNCEFn``: six sweeps and two merges) at
 the same shape in the same process, alternating, each sample one HIP-event interval around one forward + backward; the median
 and the spread (min .. max) of the samples are printed, and one JSON line at the end.
 
 Shapes (images x texts x embed dim): 256 x 256 x 512 (config 2), 512 x 2560 x 512 (B = 512, K = 5, one process) and
 4096 x 20480 x 512 (config 3's whole batch in one process: an 84 M-element logits matrix that neither head forms).
 ``--logits`` adds the logits + criterion path of both losses where its matrix stays below 1 GB.  ``--distill`` adds the
-distillation row: the fused distillation pair head (``DistillPairFn``, student width 512, teacher width 768) against logits +
-``CriterionDistill`` (four logits matrices) at all three shapes."""
+distillation row: the fused distillation head with both directions (``DistillHeadFn``, student width 512, teacher width 768)
+against logits + ``CriterionDistill`` (four logits matrices) at all three shapes.  ``--topk`` adds ``ops.score_topk`` (k = 10, with
+a target: pre-pass, sweep and merge, forward only) on the normalised features at the same shapes."""
 import argparse
 import json
 import os
@@ -18,7 +19,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from clip_event_amd.functional import DistillPairFn, InfoNCEPairFn, SigmoidHeadFn, logits_from_features
+from clip_event_amd import ops
+from clip_event_amd.functional import DistillHeadFn, InfoNCEFn, SigmoidHeadFn, logits_from_features
 from clip_event_amd.losses import CriterionContrastive, CriterionDistill, CriterionSigmoid
 
 DEV = "cuda:0"
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--logits", action="store_true", help="also time logits + criterion")
     ap.add_argument("--distill", action="store_true", help="also time the distillation head, fused and on logits")
+    ap.add_argument("--topk", action="store_true", help="also time ops.score_topk (k = 10, with a target)")
     ap.add_argument("--teacher-dim", type=int, default=768)
     args = ap.parse_args()
     torch.manual_seed(0)
@@ -58,7 +61,7 @@ def main():
             SigmoidHeadFn.apply(fi, ft, ls, lb, yi, None).backward()
 
         def infonce():
-            li, lt = InfoNCEPairFn.apply(fi, ft, ls, yi, yt, ip)
+            li, lt = InfoNCEFn.apply(fi, ft, ls, yi, None, yt, ip)
             (li + lt).backward()
 
         heads = {"sigmoid": sigmoid, "infonce_pair": infonce}
@@ -81,7 +84,7 @@ def main():
             crit_d = CriterionDistill()
 
             def distill():
-                li, lt = DistillPairFn.apply(fi, ft, ls, tfi, tft, tls, ip)
+                li, lt = DistillHeadFn.apply(fi, ft, ls, tfi, tft, tls, None, True, ip)
                 (li + lt).backward()
 
             def distill_logits():
@@ -91,6 +94,15 @@ def main():
                 (ld["loss_dist_i"] + ld["loss_dist_t"]).backward()
 
             heads.update(distill=distill, distill_logits=distill_logits)
+        if args.topk:
+            with torch.no_grad():
+                qn, kn = torch.nn.functional.normalize(fi.detach(), dim=1), torch.nn.functional.normalize(ft.detach(), dim=1)
+            lsd = ls.detach().reshape(1)
+
+            def topk():
+                ops.score_topk(qn, kn, 10, logit_scale=lsd, target=yi)
+
+            heads.update(topk=topk)
         for fn in heads.values():
             for _ in range(args.warmup):
                 fn()
