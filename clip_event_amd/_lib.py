@@ -40,6 +40,29 @@ class TransposeJob(ctypes.Structure):
                 ("tile_start", ctypes.c_int), ("pad_", ctypes.c_int)]
 
 
+class LoraJob(ctypes.Structure):
+    """``ce_lora_job`` of include/clip_event_hip.h."""
+    _fields_ = ([(n, c_void_p) for n in ("w0", "w16", "wt", "a", "b", "gw", "ga", "gb")] +
+                [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("rank", ctypes.c_int), ("scale", ctypes.c_float),
+                 ("tile_start", ctypes.c_int), ("strip_start", ctypes.c_int), ("ws_start", ctypes.c_long)])
+
+
+def lora_job_table(specs):
+    """``(host array, tiles, strips)`` of ``ce_lora_job``s from ``specs`` = [(w0, w16, wt, a, b, gw, ga, gb, rows, cols, rank, scale)]
+    (addresses as integers, ``wt`` may be 0 / None) with the running ``tile_start`` / ``strip_start`` / ``ws_start`` filled in."""
+    jobs = (LoraJob * len(specs))()
+    tiles = strips = ws = 0
+    for job, (w0, w16, wt, a, b, gw, ga, gb, rows, cols, rank, scale) in zip(jobs, specs):
+        job.w0, job.w16, job.wt, job.a, job.b, job.gw, job.ga, job.gb = w0, w16, wt or None, a, b, gw, ga, gb
+        job.rows, job.cols, job.rank, job.scale = rows, cols, rank, scale
+        job.tile_start, job.strip_start, job.ws_start = tiles, strips, ws
+        n = (rows + 63) // 64
+        tiles += n * ((cols + 63) // 64)
+        strips += n
+        ws += n * rank * cols
+    return jobs, tiles, strips
+
+
 class NTPlan(ctypes.Structure):
     """``ce_nt_plan`` of include/clip_event_hip.h; ``kernel`` indexes ``NT_KERNELS``."""
     _fields_ = [(name, ctypes.c_int) for name in ("kernel", "tm", "ts", "tall_panels", "tiles_m", "tiles_n", "tile_chunk",

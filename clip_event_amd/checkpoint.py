@@ -13,6 +13,10 @@ nothing in a checkpoint is executed.
 An optimiser with a weight average (``optimizer.enable_ema``) adds one entry, ``'ema'``: ``optimizer.ema_state_dict()`` with
 its tensors on the CPU, read back by ``load_ema``.  Without one the file has exactly the reference's five keys.  A checkpoint
 OF the averaged weights in the reference's layout is ``with optimizer.averaged(): save_model_on_master(...)``.
+
+A model with low-rank adapters (``CLIP.enable_lora``) adds one entry, ``'lora'``: ``model.lora_config()``; its ``state_dict``
+then holds the adapters beside the base weights, and ``load_checkpoint`` rebuilds base model, adapters and their values from
+the two.  ``model.lora_state_dict()`` alone is the few-MB per-task file; ``model.merge_lora()`` gives a plain model again.
 """
 from __future__ import annotations
 
@@ -39,6 +43,9 @@ def checkpoint_dict(model, optimizer, task: str, epoch: int, best_perf: float) -
     if getattr(optimizer, "ema_enabled", False):
         ema = optimizer.ema_state_dict()
         ckpt["ema"] = {**ema, "shadow": {k: v.detach().cpu() for k, v in ema["shadow"].items()}}
+    lora = model.lora_config() if hasattr(model, "lora_config") else None
+    if lora is not None:
+        ckpt["lora"] = lora
     return ckpt
 
 
@@ -69,7 +76,8 @@ def load_checkpoint(path: str, device=None, is_train: bool = True) -> Tuple[Any,
         best_perf = blob.get("perf", 0.0)
     else:
         state_dict, opt_state, begin_epoch, best_perf = blob, None, 0, 0.0
-    model = build_model(dict(state_dict))
+    # low-rank adapters: the base model from the other keys, enable_lora(**config), then the adapters (model.build_model)
+    model = build_model(dict(state_dict), lora=blob.get("lora") if isinstance(blob, dict) else None)
     if device is not None:
         model = model.to(device)
     return model, opt_state, begin_epoch, best_perf

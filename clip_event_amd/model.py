@@ -193,6 +193,10 @@ _GEMM_SUFFIXES = ("attn.in_proj_weight", "attn.out_proj.weight", "mlp.c_fc.weigh
 TOWERS = ("visual", "text")
 _INPUT_SIDE = {"visual": ("visual.ln_pre.", "visual.conv1.", "visual.positional_embedding", "visual.class_embedding"),
                "text": ("token_embedding.", "positional_embedding")}
+# low-rank adapters (CLIP.enable_lora): the block matrices that can carry them, and the matrix behind each name
+LORA_TARGETS = ("in_proj", "out_proj", "c_fc", "c_proj")
+_LORA_WEIGHT = dict(zip(LORA_TARGETS, _GEMM_SUFFIXES))
+_LORA_SUFFIXES = ("lora_A", "lora_B")
 SEGMENT, CHUNK = 2048, 1 << 16       # longest range of one workgroup: the optimiser's segment kernel, the table-driven gradient norm
 
 
@@ -332,7 +336,7 @@ class CLIP(nn.Module):
     _RUNTIME = ("_flat", "_flat_grad", "_flat16", "_offsets", "_ranges", "_layer_end", "_pmap", "_pool", "_trigger",
                 "_versions", "_w16", "_w16t", "_kp", "_kp_real", "_conv_pad", "_conv_gpad", "_cast_list", "_tjobs",
                 "_tjobs_bwd", "_adam_tiles_ok", "_wt_fresh", "_wt_event", "_aux_stream", "_mirror_fresh", "_mirror_versions", "_vdesc", "_tdesc", "_vblocks", "_tblocks",
-                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch", "_lease_batch", "_plist", "_plans", "_patch_pin", "_patch_off")
+                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch", "_lease_batch", "_plist", "_plans", "_patch_pin", "_patch_off", "_lora_tab")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -376,12 +380,234 @@ class CLIP(nn.Module):
             self.__setstate__(state)
         return self.logit_bias
 
+    # ---- low-rank adapters (LoRA), merged-operand form: DESIGN.md 4l ------------------------------------------------------------
+    def _drop_layout(self):
+        """Forget the flat layout (a parameter was added or removed): ``_prepare()`` lays the parameters out anew on the next
+        forward; until then they stay views of the old buffer."""
+        for k in ("_plist", "_plans"):
+            self.__dict__.pop(k, None)
+        if self._flat is not None:
+            state = self.__getstate__()
+            self.__dict__.clear()
+            self.__setstate__(state)
+
+    def _lora_holder(self, w0_name: str):
+        """``(module, name of the A parameter, name of the B parameter)`` for the adapted matrix ``w0_name``."""
+        mod_path, leaf = w0_name.rsplit(".", 1)
+        mod = self.get_submodule(mod_path)
+        return (mod, "in_proj_lora_A", "in_proj_lora_B") if leaf == "in_proj_weight" else (mod, "lora_A", "lora_B")
+
+    def enable_lora(self, rank: int = 8, alpha: float = 16.0, targets=LORA_TARGETS, towers=TOWERS, layers=None,
+                    freeze_base: bool = True, seed: int = 0):
+        """Give the block matrices named by ``targets`` (of ``in_proj`` / ``out_proj`` / ``c_fc`` / ``c_proj``) in ``towers``
+        low-rank adapters: ``W = W0 + (alpha / rank) B A`` with ``A [rank, in]`` and ``B [out, rank]`` registered as
+        ``...attn.in_proj_lora_A/_B``, ``...attn.out_proj.lora_A/_B``, ``...mlp.c_fc.lora_A/_B``, ``...mlp.c_proj.lora_A/_B`` (fp32
+        parameters in their block's range of the flat layout).  ``layers=n``: the top ``n`` blocks of each tower only.  Init as
+        loralib / PEFT: ``A`` is ``kaiming_uniform_(a=sqrt(5))`` drawn from a ``torch.Generator`` seeded with ``seed``, ``B`` is 0,
+        so the model computes what it computed before.  Every adapted ``W0`` is frozen (always), and with ``freeze_base`` every
+        other parameter that is no adapter too; unfreeze what else should train (``logit_scale``, LayerNorms, ...) afterwards.
+
+        The towers do not change: ``refresh_operands`` writes ``bf16(W0 + s B A)`` into the operand copies (``ce_lora_merge``) and
+        ``finish_lora_grads`` turns the towers' weight gradient of ``W0`` into the gradients of ``A`` and ``B``.  Opt-in: call it
+        before the optimiser is built.  A second call raises."""
+        if getattr(self, "_lora", None) is not None:
+            raise RuntimeError("enable_lora: the model has adapters already (merge_lora() folds them in and removes them)")
+        if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= 64:
+            raise ValueError(f"enable_lora: rank must be an integer in 1..64 (got {rank!r})")
+        alpha = float(alpha)
+        if not (math.isfinite(alpha) and alpha > 0.0):
+            raise ValueError(f"enable_lora: alpha must be positive and finite (got {alpha})")
+        targets = (targets,) if isinstance(targets, str) else tuple(targets)
+        towers = (towers,) if isinstance(towers, str) else tuple(towers)
+        if not targets or any(t not in LORA_TARGETS for t in targets) or len(set(targets)) != len(targets):
+            raise ValueError(f"enable_lora: targets must be distinct names out of {LORA_TARGETS} (got {targets})")
+        if not towers or any(t not in TOWERS for t in towers) or len(set(towers)) != len(towers):
+            raise ValueError(f"enable_lora: towers must be distinct names out of {TOWERS} (got {towers})")
+        if layers is not None and (isinstance(layers, bool) or not isinstance(layers, int) or layers < 1):
+            raise ValueError(f"enable_lora: layers must be None or a positive integer (got {layers!r})")
+        dev = self.logit_scale.device
+        gen = torch.Generator().manual_seed(int(seed))
+        saved = {n: p.requires_grad for n, p in self.named_parameters()}
+        entries = []
+        for tower in TOWERS:
+            if tower not in towers:
+                continue
+            tr, prefix = (self.visual.transformer, "visual.transformer.") if tower == "visual" else (self.transformer, "transformer.")
+            first = 0 if layers is None else max(0, tr.layers - layers)
+            for blk in range(first, tr.layers):
+                for t in LORA_TARGETS:
+                    if t not in targets:
+                        continue
+                    w0_name = f"{prefix}resblocks.{blk}.{_LORA_WEIGHT[t]}"
+                    mod, a_attr, b_attr = self._lora_holder(w0_name)
+                    w0 = getattr(mod, w0_name.rsplit(".", 1)[1])
+                    out_f, in_f = w0.shape
+                    if out_f % 8 or in_f % 8:
+                        raise ValueError(f"enable_lora: {w0_name} is {out_f} x {in_f}; adapted matrices need multiples of 8")
+                    bound = 1.0 / math.sqrt(in_f)         # kaiming_uniform_(a = sqrt(5)): gain sqrt(1/3), bound sqrt(3) gain / sqrt(fan_in)
+                    a = torch.empty(rank, in_f, dtype=torch.float32).uniform_(-bound, bound, generator=gen)
+                    mod.register_parameter(a_attr, nn.Parameter(a.to(dev)))
+                    mod.register_parameter(b_attr, nn.Parameter(torch.zeros(out_f, rank, dtype=torch.float32, device=dev)))
+                    stem = w0_name.rsplit(".", 1)[0]
+                    entries.append((w0_name, f"{stem}.{a_attr}", f"{stem}.{b_attr}"))
+        adapters = {n for e in entries for n in e[1:]}
+        frozen_w0 = {e[0] for e in entries}
+        for n, p in self.named_parameters():
+            if n in frozen_w0 or (freeze_base and n not in adapters):
+                p.requires_grad_(False)
+        self._lora = {"config": {"rank": rank, "alpha": alpha, "targets": list(targets), "towers": list(towers), "layers": layers,
+                                 "freeze_base": bool(freeze_base), "seed": int(seed)},
+                      "entries": entries, "saved_flags": saved}
+        self._drop_layout()
+        return self
+
+    def lora_config(self):
+        """``enable_lora``'s arguments as a plain dict (lists for the tuples), or None without adapters."""
+        lora = getattr(self, "_lora", None)
+        return None if lora is None else {k: (list(v) if isinstance(v, list) else v) for k, v in lora["config"].items()}
+
+    def lora_parameter_names(self):
+        """The adapters' parameter names, ``A`` before ``B`` for every adapted matrix, in table order."""
+        lora = getattr(self, "_lora", None)
+        return [] if lora is None else [n for e in lora["entries"] for n in e[1:]]
+
+    def _lora_adapter_of(self):
+        """adapter name -> the adapted matrix it belongs to (empty without adapters)."""
+        lora = getattr(self, "_lora", None)
+        return {} if lora is None else {n: e[0] for e in lora["entries"] for n in e[1:]}
+
+    def lora_scale(self) -> float:
+        """``alpha / rank`` rounded once to fp32."""
+        cfg = self._lora["config"]
+        return float(np.float32(cfg["alpha"] / cfg["rank"]))
+
+    def _check_lora_frozen(self):
+        lora = getattr(self, "_lora", None)
+        if lora is None:
+            return
+        idx = lora.get("w0_index")
+        if idx is None:
+            names = [n for n, _ in self.named_parameters()]
+            idx = lora["w0_index"] = [(names.index(e[0]), e[0]) for e in lora["entries"]]
+        flags = self._flags()
+        for i, n in idx:
+            if flags[i]:
+                raise RuntimeError(f"{n} carries adapters and has requires_grad=True: an adapted matrix stays frozen (its weight "
+                                   "gradient is the adapters' input); merge_lora() first to train it directly")
+
+    def _build_lora_table(self):
+        """The ``ce_lora_job`` table of the adapters over the current flat layout: ``(host array, device copy, njobs, tiles, strips,
+        workspace bytes)``, or None without adapters."""
+        lora = getattr(self, "_lora", None)
+        if lora is None:
+            return None
+        scale = self.lora_scale()
+        rank = lora["config"]["rank"]
+        specs = []
+        for w, a, b in lora["entries"]:
+            rows, cols = self._pmap[w].shape
+            specs.append((self._pmap[w].data_ptr(), self._w16[w].data_ptr(), self._w16t[w].data_ptr(), self._pmap[a].data_ptr(),
+                          self._pmap[b].data_ptr(), self._gview(w).data_ptr(), self._gview(a).data_ptr(), self._gview(b).data_ptr(),
+                          rows, cols, rank, scale))
+        host, tiles, strips = L.lora_job_table(specs)
+        dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self._flat.device)
+        ws = int(lib().ce_lora_grad_workspace_bytes(host, len(specs)))
+        if ws == 0:
+            raise RuntimeError(f"ce_lora_grad_workspace_bytes refused the adapter table: {lib().ce_last_error().decode()}")
+        return host, dev, len(specs), tiles, strips, ws
+
+    def _operand_versions(self):
+        """Versions of every master an operand copy is made from: the cast list and, with adapters, ``A`` and ``B``."""
+        return tuple(self._pmap[n]._version for n in self._cast_list) + tuple(self._pmap[n]._version for n in self.lora_parameter_names())
+
+    def _lora_merge(self, write_master: bool):
+        host, dev, n, tiles, _, _ = self._lora_tab
+        check(lib().ce_lora_merge(host, ptr(dev), n, tiles, int(write_master), stream()), "ce_lora_merge")
+
+    def finish_lora_grads(self):
+        """Turn the weight gradients of the adapted matrices into the adapters' gradients (``ce_lora_grad``, on the current stream):
+        ``A.grad = s B^T dW``, ``B.grad = s dW A^T``, stored.  After ``backward()`` -- and after the gradient exchange of a
+        data-parallel step -- and before anything reads ``A.grad`` / ``B.grad``: the fused optimisers call it in ``step()``, a loop
+        with a stock optimiser calls it itself.  No-op without adapters; calling it again gives the same values."""
+        if getattr(self, "_lora", None) is None or self._flat is None or not self._flat_ok():
+            return
+        self._check_lora_frozen()
+        host, dev, n, _, strips, ws_bytes = self._lora_tab
+        ws = self._pool.take("lora", ws_bytes, self._flat.device)
+        check(lib().ce_lora_grad(host, ptr(dev), n, strips, ptr(ws), ws_bytes, stream()), "ce_lora_grad")
+        self._pool.give("lora", ws)          # only this method takes the tag, always on the stream the step runs on
+        base = self._flat_grad.data_ptr()
+        for name in self.lora_parameter_names():
+            p = self._pmap[name]
+            if p.requires_grad and (p.grad is None or p.grad.data_ptr() != base + self._offsets[name] * 4):
+                p.grad = self._gview(name)
+
+    def lora_state_dict(self):
+        """``{"config": lora_config(), "state": {adapter name: tensor}}`` (copies): the whole of a task's checkpoint."""
+        if getattr(self, "_lora", None) is None:
+            raise RuntimeError("lora_state_dict: the model has no adapters (enable_lora first)")
+        pm = dict(self.named_parameters())
+        return {"config": self.lora_config(), "state": {n: pm[n].detach().clone() for n in self.lora_parameter_names()}}
+
+    def load_lora_state_dict(self, sd):
+        """Load ``lora_state_dict()``'s format; a model without adapters gets them from ``sd["config"]`` first.  Names and shapes
+        must match the model's."""
+        if getattr(self, "_lora", None) is None:
+            self.enable_lora(**sd["config"])
+        state = sd["state"]
+        pm = dict(self.named_parameters())
+        names = self.lora_parameter_names()
+        missing, extra = sorted(set(names) - set(state)), sorted(set(state) - set(names))
+        if missing or extra:
+            raise ValueError(f"adapter state does not match the model: missing {missing[:3]}, unexpected {extra[:3]}")
+        for n in names:
+            if tuple(state[n].shape) != tuple(pm[n].shape):
+                raise ValueError(f"adapter state does not match the model: {n} is {tuple(state[n].shape)}, expected {tuple(pm[n].shape)}")
+        with torch.no_grad():
+            for n in names:
+                pm[n].copy_(state[n])        # in place: the version moves, the next forward merges again
+
+    def merge_lora(self):
+        """Fold the adapters into the masters (``W0 <- fmaf(s, B A, W0)`` in fp32; on the GPU ``ce_lora_merge`` with
+        ``write_master``), remove them and give every parameter the ``requires_grad`` flag it had before ``enable_lora``:
+        afterwards the model is a plain one again and ``state_dict()`` has exactly the reference's keys."""
+        lora = getattr(self, "_lora", None)
+        if lora is None:
+            raise RuntimeError("merge_lora: the model has no adapters")
+        if self.positional_embedding.device.type == "cuda":
+            self._check_lora_frozen()
+            if not self._flat_ok():
+                self._prepare()
+            self.wait_transposes()
+            self._lora_merge(write_master=True)
+        else:
+            s = self.lora_scale()
+            pm = dict(self.named_parameters())
+            with torch.no_grad():
+                for w, a, b in lora["entries"]:
+                    pm[w].add_(pm[b] @ pm[a], alpha=s)
+        for w, _, _ in lora["entries"]:
+            mod, a_attr, b_attr = self._lora_holder(w)
+            del mod._parameters[a_attr], mod._parameters[b_attr]
+        self._lora = None
+        for n, p in self.named_parameters():
+            p.requires_grad_(lora["saved_flags"].get(n, True))
+        self._drop_layout()
+        return self
+
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """``nn.Module.load_state_dict``; a state dict without ``logit_bias`` (a reference checkpoint) loaded into a model that has
         the bias leaves the current bias value in place."""
         if getattr(self, "logit_bias", None) is not None and "logit_bias" not in state_dict:
             state_dict = dict(state_dict)
             state_dict["logit_bias"] = self.logit_bias.detach().clone()
+        lora = getattr(self, "_lora", None)
+        if lora is not None and not any(n in state_dict for n in self.lora_parameter_names()):
+            # a plain state dict (the base model's) loaded under adapters: the adapters keep their values
+            state_dict = dict(state_dict)
+            pm = dict(self.named_parameters())
+            for n in self.lora_parameter_names():
+                state_dict[n] = pm[n].detach().clone()
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
     def initialize_parameters(self):
@@ -512,6 +738,12 @@ class CLIP(nn.Module):
             for n, p in todo:
                 p.grad = self._gview(n)
         else:
+            adapters = self._lora_adapter_of()
+            if any(p.grad is None and n in adapters for n, p in todo):
+                # an adapter whose gradient was dropped (zero_grad(set_to_none=True)): the weight gradient of its frozen matrix, which
+                # finish_lora_grads reads, starts from zero with it
+                for w in {adapters[n] for n, p in todo if p.grad is None and n in adapters}:
+                    self._gview(w).zero_()
             for n, p in todo:
                 view = self._gview(n)
                 if p.grad is None:
@@ -589,9 +821,11 @@ class CLIP(nn.Module):
         pending = getattr(self, "_first_touch", None)
         if not pending:
             return
+        adapted = set(self._lora_adapter_of().values())
         for n, p in self._pmap.items():
-            # (a frozen weight's gradient is in no table of the optimiser: nothing consumes it, nothing to settle)
-            if p.requires_grad and self._is_block_weight(n) and (("visual" in pending and n.startswith("visual.")) or
+            # (a frozen weight's gradient is in no table of the optimiser: nothing consumes it, nothing to settle -- unless it
+            #  carries adapters: finish_lora_grads reads it)
+            if (p.requires_grad or n in adapted) and self._is_block_weight(n) and (("visual" in pending and n.startswith("visual.")) or
                                                                  ("text" in pending and not n.startswith("visual."))):
                 self._gview(n).zero_()
         self._first_touch = set()
@@ -794,6 +1028,7 @@ class CLIP(nn.Module):
         self._tdesc = desc("transformer.", self.transformer, self.context_length, True)
         self._w8 = None
         self._fp8_fresh = False
+        self._lora_tab = self._build_lora_table()
 
     def _job_table(self, names, groups=None):
         """``(device table, njobs, tiles)``: one ``ce_transpose_job`` per name (bf16 operand copy -> its W^T copy); ``groups``
@@ -864,7 +1099,7 @@ class CLIP(nn.Module):
     def refresh_operands(self, force: bool = False):
         """Re-cast the bf16 GEMM operands from the fp32 masters when a master changed
         (in-place optimiser update, ``load_state_dict``)."""
-        vers = tuple(self._pmap[n]._version for n in self._cast_list)
+        vers = self._operand_versions()
         self._vdesc.fp8 = self._tdesc.fp8 = int(self.fp8)
         self._vdesc.stream16 = self._tdesc.stream16 = 1 if self.stream16 else 0
         if not force and vers == self._versions:
@@ -879,6 +1114,11 @@ class CLIP(nn.Module):
             self.wait_transposes()        # an earlier asynchronous rebuild may still be reading the mirror
             # masters changed outside the fused optimiser: rebuild the whole bf16 mirror (one launch)
             check(cl.ce_cast_bf16(ptr(self._flat), ptr(self._flat16), self._flat.numel(), s), "ce_cast_bf16")
+        if self._lora_tab is not None:
+            # adapters: the operand copies of every adapted matrix become bf16(W0 + s B A), the row-major mirror and W^T alike --
+            # behind whoever wrote the mirror, in front of everything that reads it (the transposes below, _refresh_fp8)
+            self.wait_transposes()
+            self._lora_merge(write_master=False)
         tj, tn_, tt = self._tjobs
         check(cl.ce_multi_transpose_bf16(ptr(tj), tn_, tt, s), "ce_multi_transpose_bf16")
         tj, tn_, tt = self._tjobs_bwd
@@ -920,7 +1160,7 @@ class CLIP(nn.Module):
         self._versions = None
         self._mirror_fresh = mirror_fresh
         self._wt_fresh = bool(mirror_fresh and wt_fresh)
-        self._mirror_versions = tuple(self._pmap[n]._version for n in self._cast_list) if mirror_fresh else None
+        self._mirror_versions = self._operand_versions() if mirror_fresh else None
 
     def _ready(self):
         if not self._flat_ok():
@@ -930,6 +1170,7 @@ class CLIP(nn.Module):
             # launches go to the CURRENT device's stream: running a model that lives on another GPU would fault
             raise RuntimeError(f"the model lives on {dev} but the current device is cuda:{torch.cuda.current_device()}: "
                                "call torch.cuda.set_device() first (one process per GPU)")
+        self._check_lora_frozen()
         self.refresh_operands()
 
     # ---- encoders -------------------------------------------------------------------------
@@ -1143,9 +1384,22 @@ class CLIP(nn.Module):
         return image_features, text_features
 
 
-def build_model(state_dict: dict) -> CLIP:
+def build_model(state_dict: dict, lora: Optional[dict] = None) -> CLIP:
     """model_clip.py:578-617 (ViT branch): hyper-parameters inferred from tensor shapes, strict load,
-    returned in train mode."""
+    returned in train mode.  A state dict with adapter keys (``CLIP.enable_lora``) needs ``lora`` = the adapters' config
+    (``lora_config()``; the ``'lora'`` entry of a checkpoint): the base model is built from the other keys, then
+    ``enable_lora(**lora)``, then the adapters are loaded."""
+    adapter_keys = [k for k in state_dict if k.endswith(_LORA_SUFFIXES)]
+    if adapter_keys and lora is None:
+        raise ValueError(f"the state dict holds low-rank adapters ({adapter_keys[0]}, ...) but no adapter config was given: pass "
+                         "lora=<lora_config()> (checkpoint.load_checkpoint reads it from the checkpoint's 'lora' entry)")
+    if lora is not None:
+        base = {k: v for k, v in state_dict.items() if k not in set(adapter_keys)}
+        model = build_model(base)
+        model.enable_lora(**lora)
+        if adapter_keys:
+            model.load_lora_state_dict({"config": lora, "state": {k: state_dict[k] for k in adapter_keys}})
+        return model
     if "visual.proj" not in state_dict:
         raise NotImplementedError("ModifiedResNet checkpoints are out of scope (ViT towers only)")
     vision_width = state_dict["visual.conv1.weight"].shape[0]

@@ -332,7 +332,9 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         m = self.model
         self._follow_flags()            # a parameter frozen or unfrozen since the last step
         m._settle_first_touch()         # a tower that saw no backward since zero_grad_first_touch
-        m.wait_transposes()             # the update rewrites the bf16 mirror an asynchronous W^T rebuild may still be reading
+        if hasattr(m, "finish_lora_grads"):
+            m.finish_lora_grads()       # adapters: their gradients from the weight gradients of the frozen matrices (no-op without)
+        m.wait_transposes()            # the update rewrites the bf16 mirror an asynchronous W^T rebuild may still be reading
         n = m._flat.numel()
         s = stream()
         self.step_count += 1

@@ -480,6 +480,42 @@ int ce_lion_step_groups_ema(float* p, const float* g, float* m, void* p_bf16, co
  * and the bf16 mirror follows, in one pass.  a, b 16-byte aligned, a_bf16 8-byte aligned, a != b.  Calling it twice restores both. */
 int ce_swap_cast_bf16(float* a, float* b, void* a_bf16, long n, void* stream);
 
+/* ---- low-rank adapters in the merged-operand form (lora.hip) ----
+ * An adapted matrix W0 [rows = out, cols = in] (fp32 master, frozen) has two fp32 parameters A [rank, cols] and B [rows, rank];
+ * the towers run on bf16(W0 + scale * B A) and hand back the full fp32 weight gradient dW, from which the adapters' gradients
+ * follow.  One job per adapted matrix; a table of jobs exists twice, as a HOST array (every call checks it: nothing is launched
+ * on a table that could index out of bounds) and as a copy of the same bytes in DEVICE memory (what the kernels read).
+ *   w0 fp32 [rows, cols]; w16 its bf16 operand copy; wt (nullable) the W^T copy [cols, rows], bf16; a, b the adapters;
+ *   gw the dW slice; ga, gb the gradient slices of a and b.  All 16-byte aligned, rows and cols multiples of 8, 1 <= rank <= 64.
+ *   tile_start / strip_start / ws_start: running counts over the table of 64 x 64 tiles ((rows+63)/64 * (cols+63)/64 per job), of
+ *   64-row strips ((rows+63)/64) and of workspace floats (strips * rank * cols). */
+typedef struct ce_lora_job {
+    float* w0;
+    void* w16;
+    void* wt;
+    const float* a;
+    const float* b;
+    const float* gw;
+    float* ga;
+    float* gb;
+    int rows, cols, rank;
+    float scale;
+    int tile_start, strip_start;
+    long ws_start;
+} ce_lora_job;
+/* Merge: t = sum_k b[o,k] a[k,i] (an fp32 fmaf chain in k order from 0, v_mfma_f32_32x32x2_f32), w = fmaf(scale, t, w0[o,i]),
+ * w16[o,i] = bf16(w) (ce_cast_bf16's rounding), wt[i,o] the same bits; one 64 x 64 tile per workgroup.  w0 is read only unless
+ * write_master != 0, which also stores w into w0 (folding the adapters into the masters for good).  ga, gb, gw are not touched. */
+int ce_lora_merge(const ce_lora_job* jobs_host, const void* jobs_device, int njobs, int total_tiles, int write_master, void* stream);
+/* Gradients: ga[k,i] = scale * sum_o b[o,k] gw[o,i], gb[o,k] = scale * sum_i gw[o,i] a[k,i], fp32 throughout, STORED (calling it
+ * again gives the same bits).  One workgroup per 64-row strip reads its rows of gw once for both products: gb is complete there, the
+ * strip's share of ga goes to `workspace` (ce_lora_grad_workspace_bytes(jobs_host, njobs) bytes, 16-byte aligned) and a second
+ * launch adds the strips in ascending order.  No atomics: the same inputs give the same bits. */
+int ce_lora_grad(const ce_lora_job* jobs_host, const void* jobs_device, int njobs, int total_strips, void* workspace,
+                 size_t workspace_bytes, void* stream);
+/* host arithmetic; 0 for a table the calls above would refuse */
+size_t ce_lora_grad_workspace_bytes(const ce_lora_job* jobs_host, int njobs);
+
 /* ---- transformer tower runner (tower.cpp): the 12x ResidualAttentionBlock loop of
  * Transformer.forward (model_clip.py:171-211) and its backward, all launches issued from C++ ---- */
 typedef struct ce_block_params {

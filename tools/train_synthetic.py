@@ -30,7 +30,11 @@ the ramped decay of ``optim.ema_rate``); the checkpoint carries it, the resumed 
 ``--augment`` replaces the evaluation transform by open_clip's training transform on the device (``preprocess.Augment``:
 ``RandomResizedCrop(scale=(0.9, 1.0))``; ``--aug-scale``, ``--aug-hflip``, ``--aug-color-jitter B C S H``, ``--aug-color-jitter-prob``,
 ``--aug-gray-scale-prob`` are its ``--aug-cfg`` fields) with ``draw`` = the step, so that the run resumed at step 20 sees the crops the
-first run would have seen there."""
+first run would have seen there.
+
+``--lora RANK`` (``--lora-alpha A``, ``--lora-targets ...``, ``--lora-layers N``) trains low-rank adapters on the block matrices over a
+frozen base (``CLIP.enable_lora``) at 100 x the learning rate; the checkpoint carries the adapters and their config, and the model
+read back has them."""
 import argparse
 import os
 import sys
@@ -88,6 +92,10 @@ def main():
                     help="with --augment: ColorJitter(brightness, contrast, saturation, hue)")
     ap.add_argument("--aug-color-jitter-prob", type=float, default=None, metavar="P", help="with --aug-color-jitter: its probability (0.8)")
     ap.add_argument("--aug-gray-scale-prob", type=float, default=None, metavar="P", help="with --augment: RandomGrayscale probability (0)")
+    ap.add_argument("--lora", type=int, default=None, metavar="RANK", help="low-rank adapters on the block matrices (CLIP.enable_lora); the base is frozen")
+    ap.add_argument("--lora-alpha", type=float, default=None, metavar="A", help="with --lora: alpha (default 2 x RANK)")
+    ap.add_argument("--lora-targets", nargs="+", default=None, metavar="T", help="with --lora: of in_proj out_proj c_fc c_proj (default all)")
+    ap.add_argument("--lora-layers", type=int, default=None, metavar="N", help="with --lora: the top N blocks of each tower only")
     args = ap.parse_args()
     aug_cfg = {k: v for k, v in (("scale", args.aug_scale), ("hflip", args.aug_hflip), ("color_jitter", args.aug_color_jitter),
                                  ("color_jitter_prob", args.aug_color_jitter_prob), ("gray_scale_prob", args.aug_gray_scale_prob))
@@ -102,6 +110,8 @@ def main():
         ap.error("--ema-warmup goes with --ema")
     if args.adamw and args.optimizer != "adam":
         ap.error("--adamw goes with --optimizer adam")
+    if args.lora is None and (args.lora_alpha is not None or args.lora_targets is not None or args.lora_layers is not None):
+        ap.error("--lora-alpha / --lora-targets / --lora-layers go with --lora")
     mb = args.micro_batch
     dev = torch.device("cuda", 0)
     # (SGD's clipped step is lr x a unit-norm gradient: it needs a far larger lr than Adam's per-element lr to move the loss; Lion's
@@ -117,8 +127,14 @@ def main():
         model.enable_logit_bias(-10.0 if args.logit_bias is None else args.logit_bias)      # before the optimiser is built
     if args.no_decay_groups or args.adamw:
         cfg["weight_decay"] = 0.1
+    if args.lora is not None:
+        # B starts at 0 and only the adapters move: the usual adapter rates are 10 - 100 x the full fine-tuning rate
+        cfg["lr"] *= 100.0
 
     def lock(m):
+        if args.lora is not None and m.lora_config() is None:          # (a model read from a checkpoint brings its adapters along)
+            m.enable_lora(rank=args.lora, alpha=2.0 * args.lora if args.lora_alpha is None else args.lora_alpha,
+                          targets=args.lora_targets or ("in_proj", "out_proj", "c_fc", "c_proj"), layers=args.lora_layers)
         if args.lock_image_tower:
             m.lock_image_tower(args.unlocked_layers)
         if args.lock_text_tower:
@@ -170,12 +186,13 @@ def main():
     # wrong side -- and has 20 steps at lr 1e-5 to pull the positives up; so must Lion's, which at a tenth of Adam's rate moves
     # every weight by at most 1e-6 per step where Adam's first steps move it by 1e-5: measured 6.72 -> 5.81)
     slow = (args.lock_image_tower or args.lock_text_tower or args.patch_dropout or args.loss == "sigmoid" or args.distill_arch
-            or args.optimizer == "lion" or args.augment)
+            or args.optimizer == "lion" or args.augment or args.lora is not None)
     assert losses[-1] < (0.5 if not slow else 1.0) * losses[0]
     with tempfile.TemporaryDirectory() as d:
         path = checkpoint.save_model_on_master(model, d, cfg["task"], 20, 0.0, optimizer)      # engine.py:202-218
         model2, opt_state, begin_epoch, _ = checkpoint.load_checkpoint(path, device=dev)       # train.py:101-124
         assert (getattr(model2, "logit_bias", None) is not None) == (args.loss == "sigmoid")   # build_model enables it from the key
+        assert model2.lora_config() == model.lora_config()                                      # the checkpoint's 'lora' entry
         lock(model2)
         # neither the rate nor the draw counter is in the checkpoint: a resumed run sets them again
         model2.set_patch_dropout(args.patch_dropout, seed=0)
