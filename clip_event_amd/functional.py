@@ -18,6 +18,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from . import posembed
 from ._lib import check, lib, ptr, stream
 
 
@@ -318,15 +319,19 @@ class EncodeImageFn(torch.autograd.Function):
         image = _f32(image)                                   # image.type(self.dtype), model_clip.py:391
         B = image.shape[0]
         R, ps, g, D, E = v.input_resolution, v.patch_size, v.patch_num, model.vision_width, model.embed_dim
+        P = model._pmap
         if tuple(image.shape[1:]) != (3, R, R):
-            raise RuntimeError(f"expected image [B,3,{R},{R}], got {tuple(image.shape)}")
+            raise RuntimeError(f"expected image [B,3,{R},{R}], got {tuple(image.shape)} (CLIP.set_image_size runs the tower at "
+                               "another size)")
         N = g * g
+        pos = model._pos_run()                                # the table resampled to this run size, DESIGN.md 4m
+        if pos is None:
+            pos = P["visual.positional_embedding"]
         if keep_idx is not None and (use_grid or tuple(keep_idx.shape) != (B, keep_idx.shape[1]) or tuple(inv.shape) != (B, N)):
             raise RuntimeError("patch dropout tables do not fit this pass")
         keep = N if keep_idx is None else keep_idx.shape[1]  # patch rows per image
         T = keep + 1
         M = B * T
-        P = model._pmap
         desc = _vision_desc(model, T)
         patches = _empty((B * keep, model._kp), torch.bfloat16, dev)
         if keep_idx is None:
@@ -336,11 +341,11 @@ class EncodeImageFn(torch.autograd.Function):
         patch_out = ops.gemm_nt(patches, model._w16["visual.conv1.weight"], L.EPI_F32)
         xpre = _empty((M, D), torch.float32, dev)
         if keep_idx is None:
-            check(cl.ce_vision_assemble(ptr(patch_out), ptr(P["visual.class_embedding"]), ptr(P["visual.positional_embedding"]),
+            check(cl.ce_vision_assemble(ptr(patch_out), ptr(P["visual.class_embedding"]), ptr(pos),
                                         ptr(xpre), B, T, D, s), "ce_vision_assemble")
         else:
             check(cl.ce_vision_assemble_rows(ptr(patch_out), ptr(keep_idx), ptr(P["visual.class_embedding"]),
-                                             ptr(P["visual.positional_embedding"]), ptr(xpre), B, N, keep, D, s),
+                                             ptr(pos), ptr(xpre), B, N, keep, D, s),
                   "ce_vision_assemble_rows")
         sdt, _ = _stream_type(model)                          # residual stream: fp32, or fp16 (model.stream16)
         x0, mean_pre, rstd_pre = ops.layernorm_fwd_t(xpre, P["visual.ln_pre.weight"], P["visual.ln_pre.bias"], sdt)
@@ -363,7 +368,7 @@ class EncodeImageFn(torch.autograd.Function):
         if infer:
             return feat.view(B, T, E) if use_grid else feat
         ctx.model, ctx.lease, ctx.use_grid, ctx.B = model, lease, use_grid, B
-        ctx.keep, ctx.inv = keep, inv
+        ctx.keep, ctx.inv, ctx.g = keep, inv, g
         ctx.stream16 = sdt == torch.float16
         ctx.main_stream = getattr(model, "_main_stream", None)
         ctx.saved = (patches, xpre, mean_pre, rstd_pre, x0, xN, rows, hpost, mean_post, rstd_post)
@@ -378,7 +383,7 @@ class EncodeImageFn(torch.autograd.Function):
         patches, xpre, mean_pre, rstd_pre, x0, xN, rows, hpost, mean_post, rstd_post = ctx.saved
         v = model.visual
         dev = model._flat.device
-        B, g, D, E = ctx.B, v.patch_num, model.vision_width, model.embed_dim
+        B, g, D, E = ctx.B, ctx.g, model.vision_width, model.embed_dim      # the grid this pass ran at
         keep, inv = ctx.keep, ctx.inv                         # patch rows per image; patch dropout's inverse table or None
         T = keep + 1
         M = B * T
@@ -405,7 +410,18 @@ class EncodeImageFn(torch.autograd.Function):
                                     G("visual.ln_pre.bias"), _empty((M, D), torch.float32, dev), gscale=gs)
         # positional / class embedding gradients: sums over the batch axis (with patch dropout a sample adds to the
         # positional rows of the patches it kept)
-        if inv is None:
+        if g != v.native_patch_num:
+            # the tower ran on the resampled table: reduce into a scratch of that grid, then the transpose of the resampling adds
+            # into the parameter's gradient (a frozen parameter has no reader for either)
+            if P["visual.positional_embedding"].requires_grad:
+                dpos = _empty((g * g + 1, D), torch.float32, dev)
+                if inv is None:
+                    check(cl.ce_batch_reduce(ptr(dxpre), ptr(dpos), B, T * D, T * D, 0, s), "ce_batch_reduce(pos)")
+                else:           # rows that no sample kept stay zero
+                    dpos.zero_()
+                    check(cl.ce_pos_embed_bwd_rows(ptr(dxpre), ptr(inv), ptr(dpos), B, g * g, keep, D, s), "ce_pos_embed_bwd_rows")
+                posembed.resample_backward(dpos, v.native_patch_num, accumulate=True, out=G("visual.positional_embedding"))
+        elif inv is None:
             check(cl.ce_batch_reduce(ptr(dxpre), ptr(G("visual.positional_embedding")), B, T * D, T * D, 1, s),
                   "ce_batch_reduce(pos)")
         else:

@@ -117,6 +117,9 @@ class VisualTransformer(nn.Module):
         scale = width ** -0.5
         self.class_embedding = nn.Parameter(scale * torch.randn(width))
         self.patch_num = input_resolution // patch_size
+        # the size and grid ``positional_embedding`` was built for; ``input_resolution`` / ``patch_num`` are those the tower RUNS at
+        # (CLIP.set_image_size resamples the table for another size) and equal these until it is called
+        self.native_resolution, self.native_patch_num = input_resolution, self.patch_num
         self.positional_embedding = nn.Parameter(scale * torch.randn(self.patch_num ** 2 + 1, width))
         self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
         self.conv1 = _Conv1(width, patch_size)
@@ -336,7 +339,7 @@ class CLIP(nn.Module):
     _RUNTIME = ("_flat", "_flat_grad", "_flat16", "_offsets", "_ranges", "_layer_end", "_pmap", "_pool", "_trigger",
                 "_versions", "_w16", "_w16t", "_kp", "_kp_real", "_conv_pad", "_conv_gpad", "_cast_list", "_tjobs",
                 "_tjobs_bwd", "_adam_tiles_ok", "_wt_fresh", "_wt_event", "_aux_stream", "_mirror_fresh", "_mirror_versions", "_vdesc", "_tdesc", "_vblocks", "_tblocks",
-                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch", "_lease_batch", "_plist", "_plans", "_patch_pin", "_patch_off", "_lora_tab")
+                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch", "_lease_batch", "_plist", "_plans", "_patch_pin", "_patch_off", "_lora_tab", "_pos_cache", "_pos_epoch")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -1024,11 +1027,13 @@ class CLIP(nn.Module):
             d._keep = arr
             return d
 
-        self._vdesc = desc("visual.transformer.", self.visual.transformer, self.visual.patch_num ** 2 + 1, False)
+        self._vdesc = desc("visual.transformer.", self.visual.transformer, self.visual.native_patch_num ** 2 + 1, False)
         self._tdesc = desc("transformer.", self.transformer, self.context_length, True)
         self._w8 = None
         self._fp8_fresh = False
         self._lora_tab = self._build_lora_table()
+        self._pos_cache = {}              # run grid -> (resampled positional table, what it was made from): _refresh_pos
+        self._pos_epoch = 0
 
     def _job_table(self, names, groups=None):
         """``(device table, njobs, tiles)``: one ``ce_transpose_job`` per name (bf16 operand copy -> its W^T copy); ``groups``
@@ -1105,6 +1110,7 @@ class CLIP(nn.Module):
         if not force and vers == self._versions:
             if self.fp8 and not self._fp8_fresh:
                 self._refresh_fp8()
+            self._refresh_pos(False)
             return
         s = stream()
         cl = lib()
@@ -1147,6 +1153,46 @@ class CLIP(nn.Module):
         self._fp8_fresh = False
         if self.fp8:
             self._refresh_fp8()
+        self._refresh_pos(True)
+
+    # ---- the image tower at another resolution -------------------------------------------------------------------
+    def set_image_size(self, size: Optional[int] = None):
+        """Run (and train) the image tower on ``size`` x ``size`` inputs: a multiple of the patch size with
+        ``(size / patch)^2 + 1 <= 4096`` tokens, square only.  ``None`` or the native size switches the feature off.  The parameter
+        ``visual.positional_embedding`` keeps its shape; the tower adds the table resampled to the new grid (``posembed``) and the
+        backward applies the transpose.  ``visual.input_resolution`` / ``visual.patch_num`` report the run size from here on,
+        ``visual.native_resolution`` / ``visual.native_patch_num`` the parameter's.  A run-time switch like the patch-dropout rate:
+        not a parameter or a buffer, so not in ``state_dict()`` or a checkpoint; it may change between steps.  Returns the size."""
+        from .posembed import check_image_size
+        v = self.visual
+        size = v.native_resolution if size is None else int(size)
+        g = check_image_size(size, v.patch_size)
+        v.input_resolution, v.patch_num = size, g
+        return size
+
+    def _refresh_pos(self, moved: bool):
+        """Keep the resampled positional table of the current run size in step with the parameter: ``moved`` (refresh_operands saw
+        the masters move) drops every cached size; otherwise the table stands while the parameter's version does.  One small
+        launch; at the native size nothing is allocated or launched."""
+        if moved:
+            self._pos_epoch += 1
+        v = self.visual
+        g = v.patch_num
+        if g == v.native_patch_num:
+            return
+        from . import posembed
+        p = self._pmap["visual.positional_embedding"]
+        key = (self._pos_epoch, p._version)
+        hit = self._pos_cache.get(g)
+        if hit is not None and hit[1] == key:
+            return
+        table = posembed.resample(p.detach(), g, out=None if hit is None else hit[0])
+        self._pos_cache[g] = (table, key)
+
+    def _pos_run(self):
+        """The positional table the image tower adds at the current run size: None at the native size (the parameter itself)."""
+        v = self.visual
+        return None if v.patch_num == v.native_patch_num else self._pos_cache[v.patch_num][0]
 
     def wait_transposes(self):
         """Order the current stream behind the asynchronous rebuild of the blocks' W^T copies (refresh_operands)."""

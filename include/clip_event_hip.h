@@ -244,6 +244,18 @@ int ce_pos_embed_bwd_packed(const float* dx0, const int* cu_seqlens, float* dpos
                             void* stream);
 /* out[i] (+)= sum_b x[b*slab + i], i < n  (positional / class embedding gradients) */
 int ce_batch_reduce(const float* x, float* out, int B, long slab, long n, int accumulate, void* stream);
+/* ---- the image tower's positional table on another patch grid (posembed.hip) ----
+ * pos [g_in^2 + 1, D] -> out [g_out^2 + 1, D]:  out[0,:] = pos[0,:] (class token);
+ *     out[1 + i g_out + j, :] = sum_a wy[i,a] (sum_b wx[j,b] pos[1 + a g_in + b, :]),
+ * both sums in ascending index order in fp32, a zero weight skipped.  wy, wx: dense fp32 [g_out, g_in] in device memory, the
+ * caller's (the separable antialiased bicubic weights of clip_event_amd/posembed.py: host arithmetic).  The backward is the
+ * transpose in gather form, one thread per dpos element, no atomics: bit-identical run to run;
+ *     dpos[1 + a g_in + b, :] (+)= sum_i wy[i,a] (sum_j wx[j,b] dout[1 + i g_out + j, :]),   dpos[0,:] (+)= dout[0,:];
+ * accumulate = 0 stores, 1 adds.  1 <= g_in, g_out <= 63, D a multiple of 4, 16-byte aligned tables; nothing is allocated. */
+int ce_pos_resample_fwd(const float* pos, int g_in, const float* wy, const float* wx, float* out, int g_out, int D,
+                        void* stream);
+int ce_pos_resample_bwd(const float* dout, int g_out, const float* wy, const float* wx, float* dpos, int g_in, int D,
+                        int accumulate, void* stream);
 /* out[n] += sum_m x[m,n]  (bias gradients; atomics) */
 int ce_colsum_bf16(const void* x, long ld, float* out, int M, int N, void* stream);
 /* fp32 master weight [R,C] -> bf16 copy [R,C] (nullable) and bf16 transposed copy [C,R] (nullable) */

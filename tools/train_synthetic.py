@@ -34,7 +34,12 @@ first run would have seen there.
 
 ``--lora RANK`` (``--lora-alpha A``, ``--lora-targets ...``, ``--lora-layers N``) trains low-rank adapters on the block matrices over a
 frozen base (``CLIP.enable_lora``) at 100 x the learning rate; the checkpoint carries the adapters and their config, and the model
-read back has them."""
+read back has them.
+
+``--image-size R`` runs and trains the image tower at ``R`` x ``R`` instead of the checkpoint's own resolution (``CLIP.set_image_size``:
+the positional table is resampled, the parameter keeps its shape); ``--image-size-schedule STEP:R ...`` changes the size at the given
+steps (progressive resizing: cheap low-resolution steps first).  The synthetic images, the augmentation and the evaluation pass
+follow the size; the setting is not in the checkpoint, so the resumed run sets it again."""
 import argparse
 import os
 import sys
@@ -53,10 +58,10 @@ from clip_event_amd.preprocess import Augment, preprocess
 CAPTIONS = list(S.ASCII_CAPTIONS)
 
 
-def batch(rng, B, K, dev, aug=None, draw=0):
+def batch(rng, B, K, dev, aug=None, draw=0, n_px=224):
     sizes = [(int(rng.integers(240, 640)), int(rng.integers(240, 640))) for _ in range(B)]
     imgs = [torch.from_numpy(rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)).to(dev) for (w, h) in sizes]
-    image = preprocess(imgs) if aug is None else aug(imgs, draw=draw)           # clip.py:62-69 / the training transform, on the GPU
+    image = preprocess(imgs, n_px=n_px) if aug is None else aug(imgs, draw=draw)   # clip.py:62-69 / the training transform, on the GPU
     texts = [CAPTIONS[int(rng.integers(len(CAPTIONS)))] + f" number {int(rng.integers(1000))}" for _ in range(B * K)]
     text = clip.tokenize(texts)                                                 # clip.py:168-201: stays on the HOST, as the reference's loader
                                                                                 # yields it -- train_step copies it and keeps the caption lengths
@@ -96,7 +101,13 @@ def main():
     ap.add_argument("--lora-alpha", type=float, default=None, metavar="A", help="with --lora: alpha (default 2 x RANK)")
     ap.add_argument("--lora-targets", nargs="+", default=None, metavar="T", help="with --lora: of in_proj out_proj c_fc c_proj (default all)")
     ap.add_argument("--lora-layers", type=int, default=None, metavar="N", help="with --lora: the top N blocks of each tower only")
+    ap.add_argument("--image-size", type=int, default=None, metavar="R", help="run the image tower at R x R (CLIP.set_image_size)")
+    ap.add_argument("--image-size-schedule", nargs="+", default=(), metavar="STEP:R", help="from step STEP on, run at R x R")
     args = ap.parse_args()
+    try:
+        schedule = sorted((int(a), int(b)) for a, b in (item.split(":") for item in args.image_size_schedule))
+    except ValueError:
+        ap.error("--image-size-schedule takes STEP:R pairs of integers")
     aug_cfg = {k: v for k, v in (("scale", args.aug_scale), ("hflip", args.aug_hflip), ("color_jitter", args.aug_color_jitter),
                                  ("color_jitter_prob", args.aug_color_jitter_prob), ("gray_scale_prob", args.aug_gray_scale_prob))
                if v is not None}
@@ -165,17 +176,44 @@ def main():
                 timg = torch.nn.functional.interpolate(image.float(), size=(res, res), mode="bilinear", align_corners=False).to(image.dtype)
             return engine_train_step(m, crit, opt, image, *rest, distill=distill, teacher_image=timg, **kw)
 
+    native = int(model.visual.native_resolution)
+
+    def size_at(step):
+        size = native if args.image_size is None else args.image_size
+        for first, r in schedule:
+            if step >= first:
+                size = r
+        return size
+
+    augs = {}
+
+    def aug_at(size):
+        """The training transform at ``size`` (one per size: all of them count the same draws), or None."""
+        if not args.augment:
+            return None
+        if size not in augs:
+            augs[size] = Augment(size, seed=0, **aug_cfg)
+        return augs[size]
+
+    def images_at(size, imgs, draw):
+        return preprocess(imgs, n_px=size) if not args.augment else aug_at(size)(imgs, draw=draw)
+
     lock(model)
     model.set_patch_dropout(args.patch_dropout, seed=0)
+    size = model.set_image_size(size_at(0))           # a ValueError names the rule a bad size breaks
     optimizer = make_optimizer(model)
     if args.ema is not None:
         optimizer.enable_ema(args.ema, warmup=args.ema_warmup)
     scheduler = build_lr_scheduler(cfg, optimizer, 0)                           # engine.py:154-176
-    aug = Augment(model.visual.input_resolution, seed=0, **aug_cfg) if args.augment else None
-    data, decoded = batch(rng, B, K, dev, aug)                                  # one fixed batch: the loss must fall
+    aug = aug_at(size)
+    data, decoded = batch(rng, B, K, dev, aug, n_px=size)                       # one fixed batch: the loss must fall
     losses = []
     for it in range(20):
-        if aug is not None:
+        if size_at(it) != size:                                                 # progressive resizing: the same images at the new size
+            size = model.set_image_size(size_at(it))
+            aug = aug_at(size)
+            data = (images_at(size, decoded, it),) + data[1:]
+        elif aug is not None:
             data = (aug(decoded, draw=it),) + data[1:]                          # the same images, cropped (jittered) anew every step
         ld = train_step(model, criterion, optimizer, *data, check_finite=True, micro_batch=mb)
         scheduler.step()
@@ -186,7 +224,7 @@ def main():
     # wrong side -- and has 20 steps at lr 1e-5 to pull the positives up; so must Lion's, which at a tenth of Adam's rate moves
     # every weight by at most 1e-6 per step where Adam's first steps move it by 1e-5: measured 6.72 -> 5.81)
     slow = (args.lock_image_tower or args.lock_text_tower or args.patch_dropout or args.loss == "sigmoid" or args.distill_arch
-            or args.optimizer == "lion" or args.augment or args.lora is not None)
+            or args.optimizer == "lion" or args.augment or args.lora is not None or schedule)
     assert losses[-1] < (0.5 if not slow else 1.0) * losses[0]
     with tempfile.TemporaryDirectory() as d:
         path = checkpoint.save_model_on_master(model, d, cfg["task"], 20, 0.0, optimizer)      # engine.py:202-218
@@ -197,6 +235,11 @@ def main():
         # neither the rate nor the draw counter is in the checkpoint: a resumed run sets them again
         model2.set_patch_dropout(args.patch_dropout, seed=0)
         model2.patch_draw = model.patch_draw
+        assert model2.visual.input_resolution == native                                         # nor is the run size
+        size = model2.set_image_size(size_at(20))
+        if size != model.visual.input_resolution:
+            model.set_image_size(size)
+            data = (images_at(size, decoded, 20),) + data[1:]
         optimizer2 = make_optimizer(model2)
         optimizer2.load_state_dict(opt_state)
         ema = checkpoint.load_ema(path)
@@ -207,6 +250,7 @@ def main():
         scheduler2 = build_lr_scheduler(cfg, optimizer2, begin_epoch)
     if aug is not None:
         # the draws are a hash of (seed, rank, draw, sample): a resumed run needs the settings and the step, nothing else
+        aug = aug_at(size)
         aug.draw = 20
         aug2 = Augment(model2.visual.input_resolution, seed=0, **aug_cfg)
         aug2.load_state_dict(aug.state_dict())
@@ -219,14 +263,14 @@ def main():
     la, lb = float(sum(v.detach() for v in a.values())), float(sum(v.detach() for v in b.values()))
     print(f"resumed run continues: loss {la:.5f} vs {lb:.5f}")
     assert abs(la - lb) < 1e-3 * max(1.0, abs(la))
-    new, _ = batch(rng, B, K, dev, aug, 21)                                     # a fresh ragged batch goes through too
+    new, _ = batch(rng, B, K, dev, aug, 21, n_px=size)                          # a fresh ragged batch goes through too
     ld = train_step(model2, criterion, optimizer2, *new, micro_batch=mb)
     scheduler2.step()
     assert all(torch.isfinite(v) for v in ld.values())
     # a longer stretch of fresh batches with no host synchronisation in the loop: host-side caption lengths, the run-ahead
     # limit of engine.train_step, the asynchronous poll of the fp16-stream clamp counters (every 16 optimiser steps)
     import time
-    batches = [batch(rng, 32, K, dev, aug, 22 + i)[0] for i in range(8)]
+    batches = [batch(rng, 32, K, dev, aug, 22 + i, n_px=size)[0] for i in range(8)]
     for it in range(4):                                                         # new batch size: workspaces are allocated here
         train_step(model2, criterion, optimizer2, *batches[it], micro_batch=mb)
     torch.cuda.synchronize()
@@ -237,7 +281,7 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / 96
     assert all(torch.isfinite(v) for v in ld.values()) and model2.stream16_saturation() == (0, 0)
-    print(f"96 steps at B = 32, K = {K}: {dt * 1e3:.2f} ms/step, clamp counters {model2.stream16_saturation()}")
+    print(f"96 steps at B = 32, K = {K}, {size} px: {dt * 1e3:.2f} ms/step, clamp counters {model2.stream16_saturation()}")
     if args.ema is not None:
         image, text, _, _, ip = data
 
