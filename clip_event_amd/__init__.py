@@ -5,14 +5,15 @@ every compute entry point fails loudly when the HIP library or the GPU is missin
 from .tokenizer import tokenize  # noqa: F401
 from .utils_image import patch_from_norm_bbox  # noqa: F401
 
-__all__ = ["tokenize", "patch_from_norm_bbox", "CLIP", "build_model", "CriterionContrastive", "CriterionSigmoid", "CriterionAlignment"]
+__all__ = ["tokenize", "patch_from_norm_bbox", "CLIP", "build_model", "CriterionContrastive", "CriterionSigmoid", "CriterionMultiPositive",
+           "CriterionAlignment"]
 
 
 def __getattr__(name):
     if name in ("CLIP", "build_model"):
         from . import model
         return getattr(model, name)
-    if name in ("CriterionContrastive", "CriterionSigmoid", "CriterionAlignment"):
+    if name in ("CriterionContrastive", "CriterionSigmoid", "CriterionMultiPositive", "CriterionAlignment"):
         from . import losses
         return getattr(losses, name)
     raise AttributeError(name)

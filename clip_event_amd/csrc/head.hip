@@ -9,6 +9,7 @@
 //   ce_sgemm               C = alpha * op(A) op(B) (+ beta*C), arbitrary strides, fp32 LDS-tiled
 //   ce_xent_fwd / _bwd     row-wise cross entropy on selected rows (index_pos), mean reduction
 //   ce_soft_xent_fwd/_bwd  the same against a teacher's softmax instead of labels (distillation on materialised logits)
+//   ce_multipos_xent_fwd/_bwd  the same against the uniform distribution over a row's positives, given as group ids
 //   ce_dot                 out += sum a*b   (logit_scale gradient)
 #include "common.hpp"
 #include "../../include/clip_event_hip.h"
@@ -146,6 +147,61 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__
         float p = __expf(logits[src * ld + c] - l);
         if (c == y) p -= 1.0f;
         dlogits[src * ldd + c] = g * p;
+    }
+}
+
+// group-id targets (several positives per row): key column c is a positive of the row when kgroup[c] == qgroup[src] >= 0;
+// lse, invpos = 1 / (number of positives) (0: none), loss_sum += (lse - mean of the positives' logits) / nrows for rows that have one
+__global__ __launch_bounds__(256) void multipos_xent_fwd_kernel(const float* __restrict__ logits, long ld,
+                                                                const long* __restrict__ qgroup, const long* __restrict__ kgroup,
+                                                                const long* __restrict__ sel, float* __restrict__ row_lse,
+                                                                float* __restrict__ row_invpos, float* __restrict__ loss,
+                                                                int nrows, int C) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= nrows) return;
+    const long src = sel ? sel[r] : (long)r;
+    const float* row = logits + src * ld;
+    const long gq = qgroup[src];
+    float mx = -INFINITY;
+    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, row[c]);
+    mx = wave_max(mx);
+    float s = 0.f, cnt = 0.f, ps = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        s += __expf(row[c] - mx);
+        if (gq >= 0 && kgroup[c] == gq) {
+            cnt += 1.f;
+            ps += row[c];
+        }
+    }
+    s = wave_sum(s);
+    cnt = wave_sum(cnt);
+    ps = wave_sum(ps);
+    if (lane == 0) {
+        const float l = mx + __logf(s), inv = cnt > 0.f ? 1.f / cnt : 0.f;
+        row_lse[r] = l;
+        row_invpos[r] = inv;
+        if (cnt > 0.f) atomicAdd(loss, (l - ps * inv) / (float)nrows);
+    }
+}
+
+// dlogits[src, c] = g / nrows * (exp(logit - lse) - [c positive] invpos), a whole row of zeros where the row has no positive;
+// rows not selected are left untouched (caller zero-fills dlogits)
+__global__ __launch_bounds__(256) void multipos_xent_bwd_kernel(const float* __restrict__ logits, long ld,
+                                                                const long* __restrict__ qgroup, const long* __restrict__ kgroup,
+                                                                const long* __restrict__ sel, const float* __restrict__ row_lse,
+                                                                const float* __restrict__ row_invpos,
+                                                                const float* __restrict__ gptr, float* __restrict__ dlogits,
+                                                                long ldd, int nrows, int C) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= nrows) return;
+    const long src = sel ? sel[r] : (long)r;
+    const float g = *gptr / (float)nrows;
+    const float l = row_lse[r], inv = row_invpos[r];
+    const long gq = qgroup[src];
+    for (int c = lane; c < C; c += 64) {
+        float d = 0.f;
+        if (inv > 0.f) d = g * (__expf(logits[src * ld + c] - l) - (gq >= 0 && kgroup[c] == gq ? inv : 0.f));
+        dlogits[src * ldd + c] = d;
     }
 }
 
@@ -322,6 +378,27 @@ extern "C" int ce_xent_bwd(const float* logits, long ld, const int64_t* labels, 
     CE_CHECK_ARG(nrows > 0 && C > 0, "ce_xent_bwd: empty");
     hipLaunchKernelGGL(xent_bwd_kernel, dim3(ce_div_up(nrows, 4)), dim3(256), 0, (hipStream_t)stream, logits, ld,
                        (const long*)labels, (const long*)sel, row_lse, grad, dlogits, ldd, nrows, C);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_multipos_xent_fwd(const float* logits, long ld, const int64_t* qgroup, const int64_t* kgroup, const int64_t* sel,
+                                    float* row_lse, float* row_invpos, float* loss, int nrows, int C, void* stream) {
+    CE_CHECK_ARG(logits && qgroup && kgroup && row_lse && row_invpos && loss, "ce_multipos_xent_fwd: null buffer");
+    CE_CHECK_ARG(nrows > 0 && C > 0 && ld >= C, "ce_multipos_xent_fwd: bad shape");
+    hipLaunchKernelGGL(multipos_xent_fwd_kernel, dim3(ce_div_up(nrows, 4)), dim3(256), 0, (hipStream_t)stream, logits, ld,
+                       (const long*)qgroup, (const long*)kgroup, (const long*)sel, row_lse, row_invpos, loss, nrows, C);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_multipos_xent_bwd(const float* logits, long ld, const int64_t* qgroup, const int64_t* kgroup, const int64_t* sel,
+                                    const float* row_lse, const float* row_invpos, const float* grad, float* dlogits, long ldd,
+                                    int nrows, int C, void* stream) {
+    CE_CHECK_ARG(logits && qgroup && kgroup && row_lse && row_invpos && grad && dlogits, "ce_multipos_xent_bwd: null buffer");
+    CE_CHECK_ARG(nrows > 0 && C > 0 && ld >= C && ldd >= C, "ce_multipos_xent_bwd: bad shape");
+    hipLaunchKernelGGL(multipos_xent_bwd_kernel, dim3(ce_div_up(nrows, 4)), dim3(256), 0, (hipStream_t)stream, logits, ld,
+                       (const long*)qgroup, (const long*)kgroup, (const long*)sel, row_lse, row_invpos, grad, dlogits, ldd, nrows, C);
     CE_LAUNCH_CHECK();
     return 0;
 }

@@ -34,6 +34,14 @@
 // LOSS_DISTILL (cross entropy against a teacher's softmax; the entry points at the end of the file compose it from sweeps):
 // FWD leaves the log-sum-exp partials only; in DQ / DK G = c exp(x - lse) with no label, the gradient product streams a VALUE
 // matrix of its own width (HeadArgs::val) in place of the streamed operand, and the write has a scale of its own.
+// Group-id targets (several positives per query): every query source row and every key row carries a 64-bit id, and key c is a
+// positive of query r when the ids are equal and not negative.  LOSS_MULTIPOS is the softmax loss against the uniform
+// distribution over the row's positives P(r), n_r = |P(r)|:
+//   loss = (1/nq) sum_{n_r > 0} (lse_r - (1/n_r) sum_{c in P(r)} x[r,c]),   G[r,c] = g/nq (exp(x - lse_r) - [c in P(r)] / n_r)
+// FWD counts the positives and sums their x in the SAME sweep (partials (max, sum, count, possum) per split), the merge leaves
+// lse and invpos = 1 / n_r (0: a row without positives, which G then skips).  LOSS_SIGMOID_GROUP is LOSS_SIGMOID with z = +1
+// on every positive.  The ids of the 32 streamed rows sit in LDS (qinfo) in every mode; a padded streamed row has id -1 and a
+// padded resident lane id -1, so neither is ever a positive.
 #include <stdlib.h>
 
 #include <mutex>
@@ -47,7 +55,9 @@ using namespace head_sweep;
 namespace {
 
 enum { MODE_FWD = 0, MODE_DQ = 1, MODE_DK = 2 };
-enum { LOSS_SOFTMAX = 0, LOSS_SIGMOID = 1, LOSS_DISTILL = 2 };
+enum { LOSS_SOFTMAX = 0, LOSS_SIGMOID = 1, LOSS_DISTILL = 2, LOSS_MULTIPOS = 3, LOSS_SIGMOID_GROUP = 4 };
+constexpr bool is_sigmoid(int loss) { return loss == LOSS_SIGMOID || loss == LOSS_SIGMOID_GROUP; }
+constexpr bool is_group(int loss) { return loss == LOSS_MULTIPOS || loss == LOSS_SIGMOID_GROUP; }
 
 struct HeadArgs {
     const float* res; long ldres; int nres;       // resident matrix (queries for FWD / DQ, keys for DK)
@@ -72,6 +82,10 @@ struct HeadArgs {
     const float* sub;                             // DQ: [nres, Eval], the write also subtracts c exp(*out_logit_scale) sub[r] (nullable)
     const float* dot; long lddot;                 // DQ: part[split][r] = <dot[sel[r]], this split's share of output row r> (nullable)
     float csign;                                  // c = csign * (grad ? *grad / nq : 1)
+    // group-id targets only (LOSS_MULTIPOS: part is [splits][nq][4] = (max, sum, count, possum))
+    const long* qgroup;                           // id per query SOURCE row (qgroup[sel[r]])
+    const long* kgroup;                           // id per key row
+    const float* invpos;                          // [nq] 1 / n_r, 0 for a row without positives (DQ / DK of LOSS_MULTIPOS)
 };
 
 // log(1 + e) for 0 <= e <= 1, accurate where e is tiny (with the usual bias near -10 a negative pair's term is ~ 4.5e-5 and
@@ -99,6 +113,8 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
     float* part_l = res_l + HB * pitch;                                  // [NW][32][33]: partial tiles / output transpose
     float* qinfo = part_l + NW * HB * 33;                                 // [2][32]: lse, label (as float bits) of the streamed queries (DK)
                                                                           //          (sigmoid: label only; FWD: the waves' loss sums)
+    // group ids: the 64-bit ids of the 32 streamed rows, every mode -- behind [2][32] (lse, invpos; DK) for LOSS_MULTIPOS
+    long* const sid = reinterpret_cast<long*>(qinfo + (LOSS == LOSS_MULTIPOS ? 2 * HB : 0));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int r0 = blockIdx.x * HB;
@@ -111,17 +127,23 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
     // per-lane facts about resident row j
     const bool jvalid = r0 + j < a.nres;
     long jsrc = 0, jlabel = -1;
-    float jlse = 0.f, jlse_lo = 0.f;
+    long jgroup = -1;                                     // group id of resident row j (a query's, or in DK a key's)
+    float jlse = 0.f, jlse_lo = 0.f, jinv = 0.f;
     if (MODE != MODE_DK && jvalid) {
         jsrc = a.sel ? a.sel[r0 + j] : (long)(r0 + j);
-        if (LOSS != LOSS_DISTILL) jlabel = a.labels[jsrc];
-        if (MODE == MODE_DQ && LOSS == LOSS_SOFTMAX) jlse = a.lse[r0 + j];
+        if (LOSS != LOSS_DISTILL && !is_group(LOSS)) jlabel = a.labels[jsrc];
+        if (is_group(LOSS)) jgroup = a.qgroup[jsrc];
+        if (MODE == MODE_DQ && (LOSS == LOSS_SOFTMAX || LOSS == LOSS_MULTIPOS)) jlse = a.lse[r0 + j];
+        if (MODE == MODE_DQ && LOSS == LOSS_MULTIPOS) jinv = a.invpos[r0 + j];
         if (MODE == MODE_DQ && LOSS == LOSS_DISTILL) {
             jlse = a.lse[2 * (r0 + j)];
             jlse_lo = a.lse[2 * (r0 + j) + 1];
         }
     }
-    const float bias = (LOSS == LOSS_SIGMOID) ? *a.logit_bias : 0.f;
+    if (is_group(LOSS) && MODE == MODE_DK && jvalid) jgroup = a.kgroup[r0 + j];
+    // equal ids have the same sign: "both ids >= 0" is a fact about the resident row alone (false for a padded lane, id -1)
+    const bool jlive = jgroup >= 0;
+    const float bias = is_sigmoid(LOSS) ? *a.logit_bias : 0.f;
     const float coef = (MODE == MODE_FWD) ? 0.f
                        : (LOSS == LOSS_DISTILL) ? a.csign * (a.grad ? *a.grad / (float)a.nq : 1.f) : (*a.grad / (float)a.nq);
     __syncthreads();
@@ -129,6 +151,7 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
     float run_m = -INFINITY, run_l = 0.f;                 // FWD: online statistics of query j over this split
     float dls_acc = 0.f;
     float loss_acc = 0.f, dbias_acc = 0.f;                // sigmoid: FWD loss terms / DQ bias gradient of this lane
+    float pos_cnt = 0.f, pos_sum = 0.f;                   // LOSS_MULTIPOS FWD: positives of query j among this lane's rows, and their x
     constexpr int GT = 32 / NW;                           // gradient accumulators: up to 1024 / NW / 32 e-tiles of 32 per wave
     f32x16 gacc[MODE == MODE_FWD ? 1 : GT];
     // the gradient product runs over the value matrix: the streamed matrix itself, or (distillation) one of another width
@@ -175,14 +198,22 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
             const bool v = c0 + tid < a.nstr;
             const long src = v ? (a.sel ? a.sel[c0 + tid] : (long)(c0 + tid)) : 0;
             if (LOSS == LOSS_SOFTMAX) qinfo[tid] = v ? a.lse[c0 + tid] : 0.f;
-            if (LOSS != LOSS_DISTILL) qinfo[HB + tid] = v ? (float)a.labels[src] : -1.f;          // key indices < 2^24: exact in fp32
+            if (LOSS == LOSS_SOFTMAX || LOSS == LOSS_SIGMOID)
+                qinfo[HB + tid] = v ? (float)a.labels[src] : -1.f;                                // key indices < 2^24: exact in fp32
+            if (LOSS == LOSS_MULTIPOS) {
+                qinfo[tid] = v ? a.lse[c0 + tid] : 0.f;
+                qinfo[HB + tid] = v ? a.invpos[c0 + tid] : 0.f;
+            }
+            if (is_group(LOSS)) sid[tid] = v ? a.qgroup[src] : -1L;
             if (LOSS == LOSS_DISTILL) {                   // no label: the second slot carries the low part of the log-sum-exp
                 qinfo[tid] = v ? a.lse[2 * (c0 + tid)] : 0.f;
                 qinfo[HB + tid] = v ? a.lse[2 * (c0 + tid) + 1] : 0.f;
             }
         }
+        if (is_group(LOSS) && MODE != MODE_DK && tid < HB)       // ids of the 32 streamed keys (-1 behind nk: never a positive)
+            sid[tid] = c0 + tid < a.nstr ? a.kgroup[c0 + tid] : -1L;
         __syncthreads();
-        if (MODE == MODE_FWD && LOSS == LOSS_SIGMOID) {
+        if (MODE == MODE_FWD && is_sigmoid(LOSS)) {
             // pairs are independent: wave w takes the accumulator rows r = w * 16 / NW ... of every lane's column
             constexpr int RPW = 16 / NW;
 #pragma unroll
@@ -193,7 +224,10 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
                 for (int w = 0; w < NW; ++w) t += part_l[(w * HB + i) * 33 + j];
                 const float x = scale * t + bias;
                 // a zero-padded row or column would add softplus(0) = log 2
-                if (jvalid && c0 + i < a.nstr) loss_acc += neg_log_sigmoid((long)(c0 + i) == jlabel ? x : -x);
+                if (jvalid && c0 + i < a.nstr) {
+                    const bool pos = is_group(LOSS) ? (jlive && sid[i] == jgroup) : (long)(c0 + i) == jlabel;
+                    loss_acc += neg_log_sigmoid(pos ? x : -x);
+                }
             }
             continue;
         }
@@ -219,6 +253,16 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
             sum += __shfl_xor(sum, 32, 64);
             run_l = run_l * __expf(run_m - mx) + sum;      // run_m = -inf on the first block: exp(-inf) = 0
             run_m = mx;
+            if (LOSS == LOSS_MULTIPOS) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int i = row_of(r, h);
+                    if (jlive && c0 + i < a.nstr && sid[i] == jgroup) {
+                        pos_cnt += 1.f;
+                        pos_sum += S[r];
+                    }
+                }
+            }
         } else {
             // G^T[i][j] for this lane's resident j and its 16 streamed rows
             float G[16];
@@ -226,9 +270,11 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
             for (int r = 0; r < 16; ++r) {
                 const int i = row_of(r, h);
                 float g = 0.f;
-                if (LOSS == LOSS_SIGMOID) {
+                if (is_sigmoid(LOSS)) {
                     if (jvalid && c0 + i < a.nstr) {
-                        const bool pos = (MODE == MODE_DQ) ? (long)(c0 + i) == jlabel : (float)(r0 + j) == qinfo[HB + i];
+                        const bool pos = is_group(LOSS)     ? (jlive && sid[i] == jgroup)
+                                         : (MODE == MODE_DQ) ? (long)(c0 + i) == jlabel
+                                                             : (float)(r0 + j) == qinfo[HB + i];
                         const float x = S[r] + bias;
                         g = (pos ? -coef : coef) * sigmoid_neg(pos ? x : -x);
                     }
@@ -236,6 +282,10 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
                 } else if (LOSS == LOSS_DISTILL) {                      // no label term: c softmax
                     if (jvalid && c0 + i < a.nstr)
                         g = coef * __expf((S[r] - (MODE == MODE_DQ ? jlse : qinfo[i])) - (MODE == MODE_DQ ? jlse_lo : qinfo[HB + i]));
+                } else if (LOSS == LOSS_MULTIPOS) {                     // uniform over the row's positives; no positive: no row
+                    const float inv = (MODE == MODE_DQ) ? jinv : qinfo[HB + i];
+                    if (jvalid && c0 + i < a.nstr && inv > 0.f)
+                        g = coef * (__expf(S[r] - (MODE == MODE_DQ ? jlse : qinfo[i])) - (jlive && sid[i] == jgroup ? inv : 0.f));
                 } else if (MODE == MODE_DQ) {
                     if (jvalid && c0 + i < a.nstr) g = coef * (__expf(S[r] - jlse) - ((long)(c0 + i) == jlabel ? 1.f : 0.f));
                 } else {
@@ -265,7 +315,7 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
         }
     }
 
-    if (MODE == MODE_FWD && LOSS == LOSS_SIGMOID) {
+    if (MODE == MODE_FWD && is_sigmoid(LOSS)) {
         loss_acc = wave_sum(loss_acc);
         __syncthreads();                                  // the last tile's readers of part_l are done (qinfo sits behind it)
         if (lane == 0) qinfo[wave] = loss_acc;
@@ -276,6 +326,13 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
             for (int w = 0; w < NW; ++w) t += qinfo[w];
             a.loss_part[(long)blockIdx.y * gridDim.x + blockIdx.x] = t;
         }
+        return;
+    }
+    if (MODE == MODE_FWD && LOSS == LOSS_MULTIPOS) {      // every wave holds the same tile sums: wave 0 writes
+        pos_cnt += __shfl_xor(pos_cnt, 32, 64);
+        pos_sum += __shfl_xor(pos_sum, 32, 64);
+        if (wave == 0 && h == 0 && jvalid)
+            *reinterpret_cast<f32x4*>(a.part + ((long)blockIdx.y * a.nq + r0 + j) * 4) = f32x4{run_m, run_l, pos_cnt, pos_sum};
         return;
     }
     if (MODE == MODE_FWD) {
@@ -290,7 +347,7 @@ __global__ __launch_bounds__(64 * NW) void infonce_kernel(HeadArgs a) {
     if (MODE == MODE_DQ && LOSS != LOSS_DISTILL) {
         dls_acc = wave_sum(dls_acc);
         if (lane == 0 && wave == 0) atomicAdd(a.dls, dls_acc);        // every wave holds the same tile sums: count once
-        if (LOSS == LOSS_SIGMOID) {
+        if (is_sigmoid(LOSS)) {
             dbias_acc = wave_sum(dbias_acc);
             if (lane == 0 && wave == 0) atomicAdd(a.dbias, dbias_acc);
         }
@@ -381,6 +438,8 @@ __global__ __launch_bounds__(256) void sigmoid_loss_sum_kernel(const float* __re
 }
 
 size_t head_lds_bytes(int E, int nw) { return lds_bytes(E, nw) + 2 * HB * 4; }      // + qinfo
+// LOSS_MULTIPOS keeps (lse, invpos) AND the 64-bit ids of the 32 streamed rows: [2][32] floats more than qinfo
+constexpr size_t group_lds_extra(int loss) { return loss == LOSS_MULTIPOS ? 2 * HB * 4 : 0; }
 
 struct Side {      // one matrix of a sweep: [n, E] fp32 rows, ld floats apart
     const float* p; long ld; int n;
@@ -395,9 +454,9 @@ int sweep(HeadArgs& a, Side res, Side str, int E, int cap, hipStream_t s) {
     static std::once_flag flag;
     std::call_once(flag, [] {
         hipFuncSetAttribute(reinterpret_cast<const void*>(infonce_kernel<MODE, 4, LOSS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)head_lds_bytes(1024, 4));
+                            (int)(head_lds_bytes(1024, 4) + group_lds_extra(LOSS)));
         hipFuncSetAttribute(reinterpret_cast<const void*>(infonce_kernel<MODE, 8, LOSS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)head_lds_bytes(768, 8));
+                            (int)(head_lds_bytes(768, 8) + group_lds_extra(LOSS)));
     });
     a.res = res.p; a.ldres = res.ld; a.nres = res.n;
     a.str = str.p; a.ldstr = str.ld; a.nstr = str.n;
@@ -408,8 +467,11 @@ int sweep(HeadArgs& a, Side res, Side str, int E, int cap, hipStream_t s) {
     const int rb = ce_div_up(res.n, HB);
     static const int force_nw = getenv("CE_HEAD_WAVES") ? atoi(getenv("CE_HEAD_WAVES")) : 0;
     if (eight_waves(E, LOSS == LOSS_DISTILL ? a.Eval : E) && force_nw != 4)
-        hipLaunchKernelGGL((infonce_kernel<MODE, 8, LOSS>), dim3(rb, a.splits), dim3(512), head_lds_bytes(E, 8), s, a);
-    else hipLaunchKernelGGL((infonce_kernel<MODE, 4, LOSS>), dim3(rb, a.splits), dim3(256), head_lds_bytes(E, 4), s, a);
+        hipLaunchKernelGGL((infonce_kernel<MODE, 8, LOSS>), dim3(rb, a.splits), dim3(512), head_lds_bytes(E, 8) + group_lds_extra(LOSS), s,
+                           a);
+    else
+        hipLaunchKernelGGL((infonce_kernel<MODE, 4, LOSS>), dim3(rb, a.splits), dim3(256), head_lds_bytes(E, 4) + group_lds_extra(LOSS), s,
+                           a);
     CE_LAUNCH_CHECK();
     return 0;
 }
@@ -504,6 +566,122 @@ extern "C" int ce_sigmoid_head_bwd(const float* q, long ldq, const int64_t* sel,
     // dk: resident = keys, streamed = queries
     a.dres = dk;
     return sweep<MODE_DK, LOSS_SIGMOID>(a, K, Q, E, NO_CAP, s);
+}
+
+// ---- group-id targets: several positives per query, softmax and sigmoid ------------------------------------------------
+
+namespace {
+
+// merge the per-split (max, sum, count, possum): lse, invpos = 1 / n_r (0 without positives), and the row's term of the mean loss
+// lse - possum / n_r (rows without positives add nothing; the divisor stays nq).  One thread per query, one atomic per wave.
+__global__ __launch_bounds__(256) void multipos_merge_kernel(const float* __restrict__ part, int splits, int nq,
+                                                             float* __restrict__ lse_out, float* __restrict__ invpos_out,
+                                                             float* __restrict__ loss) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    float term = 0.f;
+    if (r < nq) {
+        float m, l;
+        merge_max_sum(part + 4L * r, 4L * nq, splits, m, l);
+        float cnt = 0.f, ps = 0.f;
+        for (int s = 0; s < splits; ++s) {
+            cnt += part[4L * ((long)s * nq + r) + 2];
+            ps += part[4L * ((long)s * nq + r) + 3];
+        }
+        const float lse = m + __logf(l), inv = cnt > 0.f ? 1.f / cnt : 0.f;
+        lse_out[r] = lse;
+        invpos_out[r] = inv;
+        if (cnt > 0.f) term = (lse - ps * inv) / (float)nq;
+    }
+    term = wave_sum(term);
+    if ((threadIdx.x & 63) == 0 && term != 0.f) atomicAdd(loss, term);
+}
+
+int check_groups(const char* what, const float* q, long ldq, int nq, const float* k, long ldk, int nk, int E,
+                 const float* logit_scale, const int64_t* qgroup, const int64_t* kgroup) {
+    if (int rc = check_features(what, "E", q, ldq, E)) return rc;
+    if (int rc = check_features(what, "E", k, ldk, E)) return rc;
+    CE_CHECK_ARG(logit_scale && qgroup && kgroup, "%s: null buffer", what);
+    CE_CHECK_ARG(nq > 0 && nk > 0, "%s: empty problem", what);
+    CE_CHECK_ARG(nk < (1 << 24), "%s: more than 2^24 keys", what);          // a row's positive count is kept in fp32
+    return 0;
+}
+
+}  // namespace
+
+extern "C" size_t ce_multipos_head_workspace_bytes(int nq) {
+    return nq > 0 ? (size_t)CE_INFONCE_MAX_SPLITS * nq * 4 * sizeof(float) : 0;
+}
+
+extern "C" int ce_multipos_head_fwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                                    const float* logit_scale, const int64_t* qgroup, const int64_t* kgroup, float* lse,
+                                    float* invpos, float* loss, void* workspace, void* stream) {
+    if (int rc = check_groups("ce_multipos_head_fwd", q, ldq, nq, k, ldk, nk, E, logit_scale, qgroup, kgroup)) return rc;
+    CE_CHECK_ARG(lse && invpos && loss && workspace, "ce_multipos_head_fwd: null output");
+    hipStream_t s = (hipStream_t)stream;
+    const Side Q{q, ldq, nq}, K{k, ldk, nk};
+    HeadArgs a{};
+    a.sel = (const long*)sel; a.qgroup = (const long*)qgroup; a.kgroup = (const long*)kgroup; a.logit_scale = logit_scale;
+    a.nq = nq;
+    // per-split (max, sum, count, possum) of every query from ONE sweep, then the merge
+    a.part = (float*)workspace;
+    if (int rc = sweep<MODE_FWD, LOSS_MULTIPOS>(a, Q, K, E, CE_INFONCE_MAX_SPLITS, s)) return rc;
+    hipLaunchKernelGGL(multipos_merge_kernel, dim3(ce_div_up(nq, 256)), dim3(256), 0, s, (const float*)workspace, a.splits, nq, lse,
+                       invpos, loss);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_multipos_head_bwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                                    const float* logit_scale, const int64_t* qgroup, const int64_t* kgroup, const float* lse,
+                                    const float* invpos, const float* grad, float* dq, float* dk, float* dlogit_scale,
+                                    void* stream) {
+    if (int rc = check_groups("ce_multipos_head_bwd", q, ldq, nq, k, ldk, nk, E, logit_scale, qgroup, kgroup)) return rc;
+    CE_CHECK_ARG(lse && invpos && grad && dq && dk && dlogit_scale, "ce_multipos_head_bwd: null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    const Side Q{q, ldq, nq}, K{k, ldk, nk};
+    HeadArgs a{};
+    a.sel = (const long*)sel; a.qgroup = (const long*)qgroup; a.kgroup = (const long*)kgroup; a.logit_scale = logit_scale;
+    a.lse = lse; a.invpos = invpos; a.grad = grad; a.nq = nq; a.dls = dlogit_scale;
+    a.dres = dq;
+    if (int rc = sweep<MODE_DQ, LOSS_MULTIPOS>(a, Q, K, E, NO_CAP, s)) return rc;
+    a.dres = dk;
+    return sweep<MODE_DK, LOSS_MULTIPOS>(a, K, Q, E, NO_CAP, s);
+}
+
+extern "C" int ce_sigmoid_head_group_fwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                                         const float* logit_scale, const float* logit_bias, const int64_t* qgroup,
+                                         const int64_t* kgroup, float* loss, void* workspace, void* stream) {
+    if (int rc = check_groups("ce_sigmoid_head_group_fwd", q, ldq, nq, k, ldk, nk, E, logit_scale, qgroup, kgroup)) return rc;
+    CE_CHECK_ARG(logit_bias && loss && workspace, "ce_sigmoid_head_group_fwd: null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    const Side Q{q, ldq, nq}, K{k, ldk, nk};
+    HeadArgs a{};
+    a.sel = (const long*)sel; a.qgroup = (const long*)qgroup; a.kgroup = (const long*)kgroup; a.logit_scale = logit_scale;
+    a.logit_bias = logit_bias; a.nq = nq;
+    // the partial-sum loss path of ce_sigmoid_head_fwd (workspace of ce_sigmoid_head_workspace_bytes): the same bits every run
+    a.loss_part = (float*)workspace;
+    if (int rc = sweep<MODE_FWD, LOSS_SIGMOID_GROUP>(a, Q, K, E, CE_INFONCE_MAX_SPLITS, s)) return rc;
+    hipLaunchKernelGGL(sigmoid_loss_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)workspace, ce_div_up(nq, HB) * a.splits, nq,
+                       loss);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ce_sigmoid_head_group_bwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                                         const float* logit_scale, const float* logit_bias, const int64_t* qgroup,
+                                         const int64_t* kgroup, const float* grad, float* dq, float* dk, float* dlogit_scale,
+                                         float* dlogit_bias, void* stream) {
+    if (int rc = check_groups("ce_sigmoid_head_group_bwd", q, ldq, nq, k, ldk, nk, E, logit_scale, qgroup, kgroup)) return rc;
+    CE_CHECK_ARG(logit_bias && grad && dq && dk && dlogit_scale && dlogit_bias, "ce_sigmoid_head_group_bwd: null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    const Side Q{q, ldq, nq}, K{k, ldk, nk};
+    HeadArgs a{};
+    a.sel = (const long*)sel; a.qgroup = (const long*)qgroup; a.kgroup = (const long*)kgroup; a.logit_scale = logit_scale;
+    a.logit_bias = logit_bias; a.grad = grad; a.nq = nq; a.dls = dlogit_scale; a.dbias = dlogit_bias;
+    a.dres = dq;
+    if (int rc = sweep<MODE_DQ, LOSS_SIGMOID_GROUP>(a, Q, K, E, NO_CAP, s)) return rc;
+    a.dres = dk;
+    return sweep<MODE_DK, LOSS_SIGMOID_GROUP>(a, K, Q, E, NO_CAP, s);
 }
 
 // ---- distillation: cross entropy against a teacher's softmax, on sweeps of the same skeleton --------------------------

@@ -131,6 +131,39 @@ def global_labels(batch: int, num_pos: int = 1, num_neg: int = 0, overbatch: boo
     return labels_per_image, labels_per_text, index_pos
 
 
+def global_groups(batch: int, num_pos: int = 1, num_neg: int = 0, device=None, rank_: Optional[int] = None):
+    """Group ids for the reference's layout with ``num_pos`` positive descriptions per image (dataset_voa.py:615-663, whose loss
+    for more than one was never finished): ``(groups_per_image [batch], groups_per_text [batch * (num_pos + num_neg)],
+    index_pos)``.  Image i of rank r has the global id r*batch + i; the first ``num_pos`` of its ``num_pos + num_neg`` texts carry
+    that id, the rest -1 (nobody's positive); ``index_pos`` selects the local positive rows (dataset_voa.py:658-663).  The ids
+    are global, so gathered across ranks they stay distinct.  For ``losses.CriterionMultiPositive`` and
+    ``CriterionSigmoid(multi_positive=True)``."""
+    if num_pos < 1 or num_neg < 0:
+        raise ValueError(f"global_groups: num_pos >= 1 and num_neg >= 0 (got {num_pos}, {num_neg})")
+    r = rank() if rank_ is None else rank_
+    ids = torch.arange(batch, dtype=torch.long, device=device) + r * batch
+    mask = torch.tensor([1] * num_pos + [0] * num_neg, dtype=torch.long, device=device)
+    per_text = torch.where(mask.bool().unsqueeze(0), ids.unsqueeze(1), torch.full((), -1, dtype=torch.long, device=device))
+    return ids, per_text.flatten(), torch.nonzero(mask.repeat(batch)).flatten()
+
+
+def gather_group_ids(groups_per_image: torch.Tensor, groups_per_text: torch.Tensor):
+    """The two id vectors of every rank in ONE collective, without grad: ``(groups_per_image_all [W*B], groups_per_text_all
+    [W*n])`` in rank order, the order ``gather_feature_pair`` gives the feature rows."""
+    if not active():
+        return groups_per_image, groups_per_text
+    W = world_size()
+    B, n = groups_per_image.shape[0], groups_per_text.shape[0]
+    mine = torch.cat([groups_per_image.reshape(-1), groups_per_text.reshape(-1)]).to(torch.int64).contiguous()
+    out = torch.empty(W * (B + n), dtype=torch.int64, device=mine.device)
+    if dist.get_backend() == "gloo":
+        dist.all_gather(list(out.chunk(W, dim=0)), mine)
+    else:
+        dist.all_gather_into_tensor(out, mine)
+    out = out.view(W, B + n)
+    return out[:, :B].reshape(-1), out[:, B:].reshape(-1)
+
+
 def reduce_dict(input_dict: Dict[str, torch.Tensor], average: bool = True) -> Dict[str, torch.Tensor]:
     """utils.py:136-160: all-reduce a dict of scalars (sorted keys), mean over ranks."""
     W = world_size()

@@ -18,7 +18,7 @@ import torch
 
 from . import distributed as D
 from .functional import (attach_lengths, distill_losses, fused_contrastive_losses, fused_head_ok, logits_from_features,
-                         sigmoid_contrastive_losses, small_contrastive_losses, small_head_ok, tokens_to_device)
+                         multipos_contrastive_losses, sigmoid_contrastive_losses, small_contrastive_losses, small_head_ok, tokens_to_device)
 from .losses import CriterionAlignment, CriterionContrastive, CriterionDistill
 
 
@@ -117,12 +117,12 @@ DISTILL_FUSED_MIN_LOGITS = 1 << 28
 def head_route(kind, *, rows, keys, width, teacher_width=None, dist_global=False, overbatch=True, has_index_pos=True,
                small_ok=False, fused_env="", small_env="1") -> str:
     """Which head a loss runs on: "small" (the three-launch head), "fused" (no logits matrix) or "logits" (logits + criterion).
-    Pure: everything it looks at is an argument.  ``kind``: the criterion's ("ce", "sigmoid", "bce", "kl", ...) or "distill";
+    Pure: everything it looks at is an argument.  ``kind``: the criterion's ("ce", "sigmoid", "multipos", "bce", "kl", ...) or "distill";
     ``rows`` x ``keys``: local query rows and all key rows of one direction (the logits the direction would materialise);
     ``width`` / ``teacher_width``: the feature widths; ``dist_global``: the keys are gathered across ranks; ``small_ok``:
     ``small_head_ok`` of the shapes; ``fused_env`` / ``small_env``: the values of CE_FUSED_HEAD ("" unset) and CE_SMALL_HEAD."""
     logits = rows * keys
-    if kind == "sigmoid":              # the fused head at every size the kernels take: the three-launch small head is 'ce'-only
+    if kind in ("sigmoid", "multipos"):    # the fused head at every size the kernels take: the three-launch small head is 'ce'-only
         return "fused" if fused_env != "0" and fused_head_ok(width) else "logits"
     if kind == "distill":
         fused = (fused_env != "0" and (fused_env == "1" or logits >= DISTILL_FUSED_MIN_LOGITS) and fused_head_ok(width)
@@ -183,7 +183,10 @@ def _criterion_from_features(model, criterion, fi, ft, labels_per_image, labels_
     """``pair``: the gathered (image, text) features when the caller has them already, else None."""
     dist_global = D.active() and global_batch
     if getattr(criterion, "kind", None) == "sigmoid":
-        return _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_global, None if pair is None else pair[1])
+        return _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_global, None if pair is None else pair[1],
+                                      labels_per_text)
+    if getattr(criterion, "kind", None) == "multipos":
+        return _multipos_from_features(model, criterion, fi, ft, labels_per_image, labels_per_text, index_pos, dist_global, pair)
     route = head_route(getattr(criterion, "kind", None), rows=int(fi.shape[0]),
                        keys=int(ft.shape[0]) * (D.world_size() if dist_global else 1), width=model.embed_dim,
                        dist_global=dist_global, overbatch=model.constrastive_overbatch, has_index_pos=index_pos is not None,
@@ -203,7 +206,35 @@ def _criterion_from_features(model, criterion, fi, ft, labels_per_image, labels_
     return criterion(lpi, lpt, labels_per_image, labels_per_text, index_pos=index_pos, constrastive_overbatch=overbatch)
 
 
-def _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_global, ft_all=None):
+def _multipos_from_features(model, criterion, fi, ft, groups_per_image, groups_per_text, index_pos, dist_global, pair):
+    """``CriterionMultiPositive``: the local images against all texts and the ``index_pos`` rows of the local texts against all
+    images, each row's target uniform over the keys that carry its group id.  Across ranks the features are gathered as for
+    'ce' and the two id vectors in one more collective, without grad.  The fused head at every size the kernels take, else
+    logits + criterion; CE_FUSED_HEAD=0 forces the latter."""
+    if not model.constrastive_overbatch:
+        raise RuntimeError("the multi-positive loss needs constrastive_overbatch=True: the per-instance layout has no negatives "
+                           "from other images")
+    if groups_per_image is None or groups_per_text is None:
+        raise RuntimeError("the multi-positive loss needs the group ids of the images and of the texts (distributed.global_groups)")
+    fi_all, ft_all = pair if pair is not None else (D.gather_feature_pair(fi, ft) if dist_global else (fi, ft))
+    gi_all, gt_all = groups_per_image, groups_per_text
+    if dist_global:
+        with torch.no_grad():
+            gi_all, gt_all = D.gather_group_ids(groups_per_image.to(fi.device), groups_per_text.to(fi.device))
+    if head_route("multipos", rows=int(fi.shape[0]), keys=int(ft_all.shape[0]), width=model.embed_dim,
+                  fused_env=os.environ.get("CE_FUSED_HEAD", "")) == "fused":
+        return multipos_contrastive_losses(fi, ft, fi_all, ft_all, model.logit_scale, groups_per_image, groups_per_text, gi_all,
+                                           gt_all, index_pos)
+    if dist_global:
+        lpi, _ = logits_from_features(fi, ft_all, model.logit_scale, True, want="image")
+        _, lpt = logits_from_features(fi_all, ft, model.logit_scale, True, want="text")
+    else:
+        lpi, lpt = logits_from_features(fi, ft, model.logit_scale, True)
+    return criterion(lpi, lpt, groups_per_image, groups_per_text, index_pos=index_pos, constrastive_overbatch=True,
+                     all_groups=(gi_all, gt_all))
+
+
+def _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_global, ft_all=None, labels_per_text=None):
     """``CriterionSigmoid``: the local images against all texts, one direction.  Across ranks only the TEXT features are gathered
     (half of ``gather_feature_pair``'s bytes): the rank's loss is over its own rows, DDP's mean over the ranks makes it the global
     loss, and the reduce-scatter in the gather's backward brings the other ranks' text gradients home.  The fused head (three
@@ -217,6 +248,20 @@ def _sigmoid_from_features(model, criterion, fi, ft, labels_per_image, dist_glob
         raise RuntimeError("the sigmoid loss needs a logit bias: call model.enable_logit_bias() before building the optimiser")
     if ft_all is None:
         ft_all = D.gather_features(ft) if dist_global else ft
+    if getattr(criterion, "multi_positive", False):
+        # the labels are group ids: a pair is positive wherever the ids match.  Across ranks the ids travel in one more collective
+        if labels_per_image is None or labels_per_text is None:
+            raise RuntimeError("CriterionSigmoid(multi_positive=True) needs the group ids of the images and of the texts")
+        groups = (labels_per_image, labels_per_text)
+        if dist_global:
+            with torch.no_grad():
+                groups = (labels_per_image, D.gather_group_ids(labels_per_image.to(fi.device), labels_per_text.to(fi.device))[1])
+        if head_route("sigmoid", rows=int(fi.shape[0]), keys=int(ft_all.shape[0]), width=model.embed_dim,
+                      fused_env=os.environ.get("CE_FUSED_HEAD", "")) == "fused":
+            return sigmoid_contrastive_losses(fi, ft_all, model.logit_scale, bias, None, groups)
+        lpi, _ = logits_from_features(fi, ft_all, model.logit_scale, True, want="image")
+        return criterion(lpi, None, labels_per_image, labels_per_text, constrastive_overbatch=True, logit_bias=bias,
+                         all_groups=(None, groups[1]))
     if head_route("sigmoid", rows=int(fi.shape[0]), keys=int(ft_all.shape[0]), width=model.embed_dim,
                   fused_env=os.environ.get("CE_FUSED_HEAD", "")) == "fused":
         return sigmoid_contrastive_losses(fi, ft_all, model.logit_scale, bias, labels_per_image)

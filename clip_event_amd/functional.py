@@ -784,15 +784,83 @@ def fused_contrastive_losses(fi, ft, fi_all, ft_all, logit_scale, labels_per_ima
             "loss_t": InfoNCEFn.apply(ft, fi_all, logit_scale, labels_per_text, index_pos)}
 
 
+class MultiPosHeadFn(torch.autograd.Function):
+    """Softmax cross entropy against the uniform distribution over each query's SET of positives (UniCL's supervised contrastive
+    loss; with one positive per row ``InfoNCEFn``): key c is a positive of query r when ``groups_b[c] == groups_a[src(r)]`` and
+    the id is not negative.  mean over the query rows ``sel_ab`` of ``a`` (rows without a positive add nothing, the divisor
+    stays the row count) against all rows of ``b``, without the logits matrix (``ce_multipos_head_fwd/bwd``: the positives are
+    counted and their logits summed in the sweep that takes the log-sum-exp).  ``both``: also the rows ``sel_ba`` of ``b`` against
+    all rows of ``a`` -- the same two id vectors, read the other way round.  Across ranks, where the keys are gathered: one direction
+    per node, ``groups_b`` the ids of the gathered rows."""
+
+    @staticmethod
+    def forward(ctx, a, b, logit_scale, groups_a, groups_b, sel_ab, both=False, sel_ba=None):
+        cl, s = lib(), stream()
+        dev = a.device
+        mats, invs = _head_normalise(a, b)
+        E = mats[0].shape[1]
+        groups = (_index64(groups_a, dev), _index64(groups_b, dev))
+        if groups[0].shape[0] != mats[0].shape[0] or groups[1].shape[0] != mats[1].shape[0]:
+            raise RuntimeError(f"multi-positive head: {groups[0].shape[0]} / {groups[1].shape[0]} group ids for "
+                               f"{mats[0].shape[0]} / {mats[1].shape[0]} feature rows")
+        dirs = _head_directions(mats, (None, sel_ab), *([(None, sel_ba)] if both else []))
+        ls = logit_scale.detach().reshape(1)
+        losses = torch.zeros(len(dirs), dtype=torch.float32, device=dev)                   # the merge kernel adds the rows' terms
+        ws = _empty((cl.ce_multipos_head_workspace_bytes(max(nq for _, nq, _, _ in dirs)),), torch.uint8, dev)
+        stats = []
+        for t, (iq, nq, _, sel) in enumerate(dirs):
+            q, k = mats[iq], mats[1 - iq]
+            stats.append(_empty((2, nq), torch.float32, dev))                              # lse | 1 / positives
+            check(cl.ce_multipos_head_fwd(ptr(q), E, ptr(sel), nq, ptr(k), E, k.shape[0], E, ptr(ls), ptr(groups[iq]),
+                                          ptr(groups[1 - iq]), ptr(stats[t][0]), ptr(stats[t][1]), ptr(losses[t:t + 1]), ptr(ws), s),
+                  "ce_multipos_head_fwd")
+        ctx.saved = (mats, invs, ls, groups, dirs, stats)
+        return _head_result(losses)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        cl, s = lib(), stream()
+        mats, invs, ls, groups, dirs, stats = ctx.saved
+        E = mats[0].shape[1]
+        g = _head_upstream(gs, mats[0].device)
+        grads, scalars = _head_grad_buffers(mats)                                           # da^ | db^ | dlogit_scale
+        for t, (iq, nq, _, sel) in enumerate(dirs):
+            q, k = mats[iq], mats[1 - iq]
+            check(cl.ce_multipos_head_bwd(ptr(q), E, ptr(sel), nq, ptr(k), E, k.shape[0], E, ptr(ls), ptr(groups[iq]),
+                                          ptr(groups[1 - iq]), ptr(stats[t][0]), ptr(stats[t][1]), ptr(g[t:t + 1]), ptr(grads[iq]),
+                                          ptr(grads[1 - iq]), ptr(scalars[0:1]), s), "ce_multipos_head_bwd")
+        return (_l2norm_bwd(grads[0], mats[0], invs[0]), _l2norm_bwd(grads[1], mats[1], invs[1]), scalars[0].reshape(()),
+                None, None, None, None, None)
+
+
+def multipos_contrastive_losses(fi, ft, fi_all, ft_all, logit_scale, groups_per_image, groups_per_text, groups_per_image_all,
+                                groups_per_text_all, index_pos):
+    """``CriterionMultiPositive`` over the batch on raw features: loss_i = the local images against all texts, loss_t = the
+    ``index_pos`` rows of the local texts against all images, the logits never materialised."""
+    if fi_all is fi and ft_all is ft:          # one process: one node for both directions
+        loss_i, loss_t = MultiPosHeadFn.apply(fi, ft, logit_scale, groups_per_image, groups_per_text, None, True, index_pos)
+        return {"loss_i": loss_i, "loss_t": loss_t}
+    return {"loss_i": MultiPosHeadFn.apply(fi, ft_all, logit_scale, groups_per_image, groups_per_text_all, None),
+            "loss_t": MultiPosHeadFn.apply(ft, fi_all, logit_scale, groups_per_text, groups_per_image_all, index_pos)}
+
+
 class SigmoidHeadFn(torch.autograd.Function):
     """The sigmoid pairwise loss of SigLIP, -(1/nq) sum_r sum_c log sigma(z (s q^_r . k^_c + b)) with z = +1 where c is the label
     of query r and -1 elsewhere, over the query rows ``sel_ab`` of ``a`` against all rows of ``b`` -- without the [nq, nk] logits
     matrix (``ce_sigmoid_head_fwd/bwd``: three sweeps, nothing saved but the normalised features); with ``labels_ba`` also over the
     rows ``sel_ba`` of ``b`` against all rows of ``a``.  Gradients for both raw feature matrices, ``logit_scale`` and
-    ``logit_bias``."""
+    ``logit_bias``.
+
+    ``groups`` = (ids of the rows of ``a``, ids of the rows of ``b``): the multi-positive form.  z = +1 wherever the key's id equals
+    the query's and is not negative (``ce_sigmoid_head_group_fwd/bwd``); ``labels_ab`` / ``labels_ba`` are then not read, and the
+    second direction is asked for with ``labels_ba`` not None (any value) or ``sel_ba``."""
 
     @staticmethod
-    def forward(ctx, a, b, logit_scale, logit_bias, labels_ab, sel_ab, labels_ba=None, sel_ba=None):
+    def forward(ctx, a, b, logit_scale, logit_bias, labels_ab, sel_ab, labels_ba=None, sel_ba=None, groups=None):
+        if groups is not None:
+            return SigmoidHeadFn._forward_groups(ctx, a, b, logit_scale, logit_bias, sel_ab, labels_ba is not None or sel_ba is not None,
+                                                 sel_ba, groups)
+        ctx.groups = None
         cl, s = lib(), stream()
         dev = a.device
         mats, invs = _head_normalise(a, b)
@@ -809,6 +877,28 @@ class SigmoidHeadFn(torch.autograd.Function):
         return _head_result(losses)
 
     @staticmethod
+    def _forward_groups(ctx, a, b, logit_scale, logit_bias, sel_ab, both, sel_ba, groups):
+        cl, s = lib(), stream()
+        dev = a.device
+        mats, invs = _head_normalise(a, b)
+        E = mats[0].shape[1]
+        ctx.groups = (_index64(groups[0], dev), _index64(groups[1], dev))
+        if ctx.groups[0].shape[0] != mats[0].shape[0] or ctx.groups[1].shape[0] != mats[1].shape[0]:
+            raise RuntimeError(f"sigmoid head: {ctx.groups[0].shape[0]} / {ctx.groups[1].shape[0]} group ids for "
+                               f"{mats[0].shape[0]} / {mats[1].shape[0]} feature rows")
+        dirs = _head_directions(mats, (None, sel_ab), *([(None, sel_ba)] if both else []))
+        ls, lb = logit_scale.detach().reshape(1), logit_bias.detach().float().reshape(1)
+        losses = _empty((len(dirs),), torch.float32, dev)
+        for t, (iq, nq, _, sel) in enumerate(dirs):
+            q, k = mats[iq], mats[1 - iq]
+            ws = _empty((cl.ce_sigmoid_head_workspace_bytes(nq, k.shape[0]),), torch.uint8, dev)
+            check(cl.ce_sigmoid_head_group_fwd(ptr(q), E, ptr(sel), nq, ptr(k), E, k.shape[0], E, ptr(ls), ptr(lb),
+                                               ptr(ctx.groups[iq]), ptr(ctx.groups[1 - iq]), ptr(losses[t:t + 1]), ptr(ws), s),
+                  "ce_sigmoid_head_group_fwd")
+        ctx.saved = (mats, invs, ls, lb, dirs)
+        return _head_result(losses)
+
+    @staticmethod
     def backward(ctx, *gs):
         cl, s = lib(), stream()
         mats, invs, ls, lb, dirs = ctx.saved
@@ -817,15 +907,24 @@ class SigmoidHeadFn(torch.autograd.Function):
         grads, scalars = _head_grad_buffers(mats)                                           # da^ | db^ | dscale, dbias
         for t, (iq, nq, labels, sel) in enumerate(dirs):
             q, k = mats[iq], mats[1 - iq]
+            if ctx.groups is not None:
+                check(cl.ce_sigmoid_head_group_bwd(ptr(q), E, ptr(sel), nq, ptr(k), E, k.shape[0], E, ptr(ls), ptr(lb),
+                                                   ptr(ctx.groups[iq]), ptr(ctx.groups[1 - iq]), ptr(g[t:t + 1]), ptr(grads[iq]),
+                                                   ptr(grads[1 - iq]), ptr(scalars[0:1]), ptr(scalars[1:2]), s),
+                      "ce_sigmoid_head_group_bwd")
+                continue
             check(cl.ce_sigmoid_head_bwd(ptr(q), E, ptr(sel), nq, ptr(k), E, k.shape[0], E, ptr(ls), ptr(lb), ptr(labels),
                                          ptr(g[t:t + 1]), ptr(grads[iq]), ptr(grads[1 - iq]), ptr(scalars[0:1]), ptr(scalars[1:2]), s),
                   "ce_sigmoid_head_bwd")
         return (_l2norm_bwd(grads[0], mats[0], invs[0]), _l2norm_bwd(grads[1], mats[1], invs[1]), scalars[0].reshape(()),
-                scalars[1].reshape(()), None, None, None, None)
+                scalars[1].reshape(()), None, None, None, None, None)
 
 
-def sigmoid_contrastive_losses(fi, ft_all, logit_scale, logit_bias, labels_per_image):
-    """``CriterionSigmoid`` over the batch on raw features: the local images against all (gathered) texts, one direction."""
+def sigmoid_contrastive_losses(fi, ft_all, logit_scale, logit_bias, labels_per_image, groups=None):
+    """``CriterionSigmoid`` over the batch on raw features: the local images against all (gathered) texts, one direction.
+    ``groups`` = (ids of the images, ids of all texts): ``CriterionSigmoid(multi_positive=True)``."""
+    if groups is not None:
+        return {"loss_sig": SigmoidHeadFn.apply(fi, ft_all, logit_scale, logit_bias, None, None, None, None, groups)}
     return {"loss_sig": SigmoidHeadFn.apply(fi, ft_all, logit_scale, logit_bias, labels_per_image, None)}
 
 

@@ -43,6 +43,46 @@ def cross_entropy(logits, labels, sel=None):
     return _CrossEntropyFn.apply(logits, labels, sel)
 
 
+class _MultiPosCrossEntropyFn(torch.autograd.Function):
+    """mean over the rows ``sel`` (or all rows) of lse(x_r) - mean_{c in P(r)} x_r,c, P(r) the columns whose group id equals the
+    row's (and is not negative); a row without positives adds nothing and the divisor stays the row count."""
+
+    @staticmethod
+    def forward(ctx, logits, row_groups, col_groups, sel):
+        if not logits.is_cuda:
+            raise RuntimeError("clip_event_amd losses run on the GPU only (no CPU fallback)")
+        logits = logits if (logits.dtype == torch.float32 and logits.is_contiguous()) else logits.contiguous().float()
+        dev = logits.device
+        row_groups = row_groups.to(device=dev, dtype=torch.int64).contiguous()
+        col_groups = col_groups.to(device=dev, dtype=torch.int64).contiguous()
+        if row_groups.shape[0] != logits.shape[0] or col_groups.shape[0] != logits.shape[1]:
+            raise RuntimeError(f"{row_groups.shape[0]} row / {col_groups.shape[0]} column group ids for logits {tuple(logits.shape)}")
+        if sel is not None:
+            sel = sel.to(device=dev, dtype=torch.int64).contiguous()
+        nrows = logits.shape[0] if sel is None else sel.shape[0]
+        stats = torch.empty(2, nrows, dtype=torch.float32, device=dev)                     # lse | 1 / positives
+        loss = torch.zeros((), dtype=torch.float32, device=dev)
+        check(lib().ce_multipos_xent_fwd(ptr(logits), logits.stride(0), ptr(row_groups), ptr(col_groups), ptr(sel), ptr(stats[0]),
+                                         ptr(stats[1]), ptr(loss), nrows, logits.shape[1], stream()), "ce_multipos_xent_fwd")
+        ctx.saved = (logits, row_groups, col_groups, sel, stats)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, row_groups, col_groups, sel, stats = ctx.saved
+        nrows = logits.shape[0] if sel is None else sel.shape[0]
+        d = torch.zeros_like(logits) if sel is not None else torch.empty_like(logits)
+        g = g.contiguous().float()
+        check(lib().ce_multipos_xent_bwd(ptr(logits), logits.stride(0), ptr(row_groups), ptr(col_groups), ptr(sel), ptr(stats[0]),
+                                         ptr(stats[1]), ptr(g), ptr(d), d.stride(0), nrows, logits.shape[1], stream()),
+              "ce_multipos_xent_bwd")
+        return d, None, None, None
+
+
+def multipos_cross_entropy(logits, row_groups, col_groups, sel=None):
+    return _MultiPosCrossEntropyFn.apply(logits, row_groups, col_groups, sel)
+
+
 class _ElemLossFn(torch.autograd.Function):
     """nn.BCEWithLogitsLoss() (mode 0) / nn.KLDivLoss() (mode 1), default 'mean' reduction."""
 
@@ -97,17 +137,48 @@ class CriterionContrastive(nn.Module):
         return {"loss_i": loss_i, "loss_t": loss_t}
 
 
+class CriterionMultiPositive(nn.Module):
+    """Several positive texts per image (and several images per text): each row's target is uniform over the SET of columns
+    that carry the row's group id -- UniCL's bidirectional supervised contrastive loss; with one positive per row it is
+    ``CriterionContrastive('ce')``.  ``labels_per_image`` [B] holds the images' group ids, ``labels_per_text`` [N] the texts'; a
+    negative id belongs to no group (a text that is nobody's positive).  ``index_pos`` selects the text-direction query rows.
+    When the logits' columns were gathered across ranks, ``all_groups=(groups_per_image_all, groups_per_text_all)`` gives the
+    ids of the columns; without it the rows' ids are the columns' ids.  This is the logits path (``ce_multipos_xent_*``);
+    ``engine`` runs the fused head (``functional.MultiPosHeadFn``) where the kernels take the width."""
+
+    kind = "multipos"
+
+    def forward(self, logits_per_image, logits_per_text, labels_per_image=None, labels_per_text=None,
+                index_pos=None, constrastive_overbatch=True, all_groups=None):
+        if not constrastive_overbatch:
+            raise RuntimeError("CriterionMultiPositive needs constrastive_overbatch=True: the per-instance layout scores an image "
+                               "against its own descriptions only, so it has no negatives from other images")
+        if labels_per_image is None or labels_per_text is None:
+            raise RuntimeError("CriterionMultiPositive needs the group ids of the images (labels_per_image) and of the texts "
+                               "(labels_per_text): distributed.global_groups lays them out")
+        gi_all, gt_all = (labels_per_image, labels_per_text) if all_groups is None else all_groups
+        return {"loss_i": multipos_cross_entropy(logits_per_image, labels_per_image, gt_all),
+                "loss_t": multipos_cross_entropy(logits_per_text, labels_per_text, gi_all, index_pos)}
+
+
 class CriterionSigmoid(nn.Module):
     """The sigmoid pairwise loss of SigLIP (open_clip's ``SigLipLoss``) on a materialised ``logits_per_image`` [nq, nk]: every
     (image, text) pair is its own binary term, positive where the column is the image's label,
     loss = -(1/nq) sum_r sum_c log sigma(z (logits + logit_bias)).  One direction: ``logits_per_text`` and its labels are
     accepted for the common call and not used.  This is the general path, for embed dims the fused head
-    (``functional.SigmoidHeadFn``) does not take; ``engine`` picks between them."""
+    (``functional.SigmoidHeadFn``) does not take; ``engine`` picks between them.
+
+    ``multi_positive=True`` reads ``labels_per_image`` / ``labels_per_text`` as the group ids of the images and of the texts (as
+    ``CriterionMultiPositive`` does): a pair is positive wherever the ids are equal and not negative.  ``all_groups`` as there."""
 
     kind = "sigmoid"
 
+    def __init__(self, multi_positive: bool = False):
+        super().__init__()
+        self.multi_positive = bool(multi_positive)
+
     def forward(self, logits_per_image, logits_per_text, labels_per_image=None, labels_per_text=None,
-                index_pos=None, constrastive_overbatch=True, logit_bias=None):
+                index_pos=None, constrastive_overbatch=True, logit_bias=None, all_groups=None):
         if not constrastive_overbatch:
             raise RuntimeError("CriterionSigmoid needs constrastive_overbatch=True: the per-instance layout scores an image against "
                                "its own descriptions only, so it has no negatives from other images")
@@ -115,6 +186,13 @@ class CriterionSigmoid(nn.Module):
             raise RuntimeError("CriterionSigmoid needs logit_bias (model.enable_logit_bias())")
         nq, nk = logits_per_image.shape
         dev = logits_per_image.device
+        if self.multi_positive:
+            if labels_per_image is None or labels_per_text is None:
+                raise RuntimeError("CriterionSigmoid(multi_positive=True) needs the group ids of the images and of the texts")
+            gq = labels_per_image.to(device=dev, dtype=torch.int64).reshape(nq, 1)
+            gk = (labels_per_text if all_groups is None else all_groups[1]).to(device=dev, dtype=torch.int64).reshape(1, nk)
+            multihot = ((gq == gk) & (gq >= 0)).float()
+            return {"loss_sig": _ElemLossFn.apply(logits_per_image + logit_bias, multihot, 0) * nk}
         if labels_per_image is None:
             labels_per_image = torch.arange(nq, device=dev)
         onehot = torch.zeros(nq, nk, dtype=torch.float32, device=dev)

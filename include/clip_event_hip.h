@@ -348,6 +348,15 @@ int ce_xent_fwd(const float* logits, long ld, const int64_t* labels, const int64
                 float* loss, int nrows, int C, void* stream);
 int ce_xent_bwd(const float* logits, long ld, const int64_t* labels, const int64_t* sel, const float* row_lse,
                 const float* grad, float* dlogits, long ldd, int nrows, int C, void* stream);
+/* the multi-positive cross entropy on materialised logits [., C], one wave per selected row (sel = index_pos or NULL): column c
+ * is a positive of row src when kgroup[c] == qgroup[src] >= 0; row_lse / row_invpos [nrows] (1 / positives, 0 without) are kept
+ * for the backward; *loss += (1/nrows) sum over rows with a positive of (lse - mean of the positives' logits);
+ * dlogits[src, c] = grad / nrows (softmax_c - [c positive] invpos), zeros for a row without positives (rows not selected untouched) */
+int ce_multipos_xent_fwd(const float* logits, long ld, const int64_t* qgroup, const int64_t* kgroup, const int64_t* sel,
+                         float* row_lse, float* row_invpos, float* loss, int nrows, int C, void* stream);
+int ce_multipos_xent_bwd(const float* logits, long ld, const int64_t* qgroup, const int64_t* kgroup, const int64_t* sel,
+                         const float* row_lse, const float* row_invpos, const float* grad, float* dlogits, long ldd, int nrows, int C,
+                         void* stream);
 /* soft-target cross entropy over the selected rows: *loss += mean_r (lse(x_r) - sum_c softmax(t_r)_c x_r,c), x = logits,
  * t = teacher_logits (a constant; same shape, own leading dimension); row_lse / row_lse_t [nrows] are kept for the backward,
  * dlogits[src, c] = grad / nrows (softmax(x)_c - softmax(t)_c) (rows not selected untouched) */
@@ -649,6 +658,32 @@ int ce_sigmoid_head_fwd(const float* q, long ldq, const int64_t* sel, int nq, co
 int ce_sigmoid_head_bwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
                         const float* logit_scale, const float* logit_bias, const int64_t* labels, const float* grad, float* dq,
                         float* dk, float* dlogit_scale, float* dlogit_bias, void* stream);
+
+/* Group-id targets on the same sweep (several positives per query), one direction.  q, k, sel, nq, nk as ce_infonce_fwd;
+ * qgroup holds one 64-bit id per query SOURCE row (query r reads qgroup[sel[r]]), kgroup one per key row.  Key c is a positive of
+ * query r when kgroup[c] == qgroup[sel[r]] over all 64 bits AND the id is >= 0: a negative id belongs to no group.
+ *   P(r) the positives of row r, n_r = |P(r)|, x[r,c] = s <q_r, k_c>
+ *   fwd: lse[r] = log sum_c exp(x[r,c]); invpos[r] = 1 / n_r, 0 where n_r = 0;
+ *        *loss += (1/nq) sum_{n_r > 0} (lse[r] - (1/n_r) sum_{c in P(r)} x[r,c]) -- ONE sweep counts and sums the positives next
+ *        to the log-sum-exp; workspace = ce_multipos_head_workspace_bytes(nq) bytes.
+ *   bwd: G[r,c] = grad/nq (exp(x - lse[r]) - [c in P(r)] invpos[r]), a row with n_r = 0 contributes nothing;
+ *        dq, dk, *dlogit_scale from G as in ce_infonce_bwd.
+ * With one positive per row this is ce_infonce_fwd/bwd.  nk < 2^24.  No allocation, no synchronisation. */
+size_t ce_multipos_head_workspace_bytes(int nq);
+int ce_multipos_head_fwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                         const float* logit_scale, const int64_t* qgroup, const int64_t* kgroup, float* lse, float* invpos,
+                         float* loss, void* workspace, void* stream);
+int ce_multipos_head_bwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                         const float* logit_scale, const int64_t* qgroup, const int64_t* kgroup, const float* lse,
+                         const float* invpos, const float* grad, float* dq, float* dk, float* dlogit_scale, void* stream);
+/* ce_sigmoid_head_fwd / _bwd with z[r,c] = +1 on every positive of the row (group ids as above) in place of one label; the
+ * workspace is ce_sigmoid_head_workspace_bytes(nq, nk) and *loss is WRITTEN from partials summed in a fixed order. */
+int ce_sigmoid_head_group_fwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                              const float* logit_scale, const float* logit_bias, const int64_t* qgroup, const int64_t* kgroup,
+                              float* loss, void* workspace, void* stream);
+int ce_sigmoid_head_group_bwd(const float* q, long ldq, const int64_t* sel, int nq, const float* k, long ldk, int nk, int E,
+                              const float* logit_scale, const float* logit_bias, const int64_t* qgroup, const int64_t* kgroup,
+                              const float* grad, float* dq, float* dk, float* dlogit_scale, float* dlogit_bias, void* stream);
 
 /* Distillation loss on the same sweep, one direction: cross entropy of the student's softmax against a teacher's, the
  * logits of neither materialised.  q, k, sel, nq, nk as ce_infonce_fwd (student, width Es, s = exp(*logit_scale)); tq / tk are

@@ -9,7 +9,9 @@ Shapes (images x texts x embed dim): 256 x 256 x 512 (config 2), 512 x 2560 x 51
 ``--logits`` adds the logits + criterion path of both losses where its matrix stays below 1 GB.  ``--distill`` adds the
 distillation row: the fused distillation head with both directions (``DistillHeadFn``, student width 512, teacher width 768)
 against logits + ``CriterionDistill`` (four logits matrices) at all three shapes.  ``--topk`` adds ``ops.score_topk`` (k = 10, with
-a target: pre-pass, sweep and merge, forward only) on the normalised features at the same shapes."""
+a target: pre-pass, sweep and merge, forward only) on the normalised features at the same shapes.  ``--multipos P`` adds the
+multi-positive head with both directions (``MultiPosHeadFn``: the first P of every image's texts carry its group id; six sweeps and
+two merges, as the InfoNCE pair, the second direction over P times as many rows)."""
 import argparse
 import json
 import os
@@ -20,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from clip_event_amd import ops
-from clip_event_amd.functional import DistillHeadFn, InfoNCEFn, SigmoidHeadFn, logits_from_features
+from clip_event_amd.functional import DistillHeadFn, InfoNCEFn, MultiPosHeadFn, SigmoidHeadFn, logits_from_features
 from clip_event_amd.losses import CriterionContrastive, CriterionDistill, CriterionSigmoid
 
 DEV = "cuda:0"
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--logits", action="store_true", help="also time logits + criterion")
     ap.add_argument("--distill", action="store_true", help="also time the distillation head, fused and on logits")
     ap.add_argument("--topk", action="store_true", help="also time ops.score_topk (k = 10, with a target)")
+    ap.add_argument("--multipos", type=int, default=0, metavar="P", help="also time the multi-positive head, P positives per image")
     ap.add_argument("--teacher-dim", type=int, default=768)
     args = ap.parse_args()
     torch.manual_seed(0)
@@ -94,6 +97,18 @@ def main():
                 (ld["loss_dist_i"] + ld["loss_dist_t"]).backward()
 
             heads.update(distill=distill, distill_logits=distill_logits)
+        if args.multipos:
+            P = min(args.multipos, K)
+            col = torch.arange(nk, device=DEV)
+            gi = torch.arange(nq, device=DEV)
+            gt = torch.where(col % K < P, col // K, torch.full_like(col, -1))
+            ip_mp = torch.nonzero(col % K < P).flatten()
+
+            def multipos():
+                li, lt = MultiPosHeadFn.apply(fi, ft, ls, gi, gt, None, True, ip_mp)
+                (li + lt).backward()
+
+            heads.update(multipos=multipos)
         if args.topk:
             with torch.no_grad():
                 qn, kn = torch.nn.functional.normalize(fi.detach(), dim=1), torch.nn.functional.normalize(ft.detach(), dim=1)
@@ -115,12 +130,15 @@ def main():
         for name, ts in times.items():
             row[name] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
         row["sigmoid_over_infonce_pair"] = row["sigmoid"]["median_ms"] / row["infonce_pair"]["median_ms"]
+        if args.multipos:
+            row["multipos_over_infonce_pair"] = row["multipos"]["median_ms"] / row["infonce_pair"]["median_ms"]
         if args.distill:
             row["distill_over_distill_logits"] = row["distill"]["median_ms"] / row["distill_logits"]["median_ms"]
         results.append(row)
         print(f"{nq} x {nk} x {E}: " + "; ".join(f"{name} {r['median_ms']:.3f} ms ({r['min_ms']:.3f} .. {r['max_ms']:.3f})"
                                                  for name, r in row.items() if isinstance(r, dict))
               + f"; sigmoid / InfoNCE pair {row['sigmoid_over_infonce_pair']:.2f}"
+              + (f"; multipos / InfoNCE pair {row['multipos_over_infonce_pair']:.2f}" if args.multipos else "")
               + (f"; distill fused / logits {row['distill_over_distill_logits']:.2f}" if args.distill else ""), flush=True)
         del fi, ft
     print(json.dumps({"bench": "head", "iters": args.iters, "results": results}))

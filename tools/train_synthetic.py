@@ -19,6 +19,10 @@ is always decoupled).
 ``--loss sigmoid`` trains with the sigmoid pairwise loss of SigLIP (losses.CriterionSigmoid on the fused sigmoid head) and its
 learnable logit bias (``CLIP.enable_logit_bias``; ``--logit-bias INIT``, default -10); the checkpoint carries the bias.
 
+``--loss multipos --positives P`` trains with P positive captions per image (``distributed.global_groups``: the first P of every
+image's P + 2 captions carry its group id) on ``losses.CriterionMultiPositive`` (the fused multi-positive head: each row's target is
+uniform over its positives); ``--positives P`` with ``--loss sigmoid`` is ``CriterionSigmoid(multi_positive=True)`` on the same layout.
+
 ``--distill-arch ARCH`` adds knowledge distillation (``engine.Distillation``: ``loss_dist_i`` / ``loss_dist_t``; at this batch size
 on logits + ``losses.CriterionDistill``, CE_FUSED_HEAD=1 for the fused distillation head) from a frozen teacher of the named geometry, randomly initialised or loaded from ``--distill-checkpoint``;
 ``--distill-weight W`` scales the two terms.  A teacher of another resolution gets the batch resized to its own.
@@ -51,21 +55,24 @@ import torch
 
 from clip_event_amd import checkpoint, clip, distributed as D, inference, synthetic as S
 from clip_event_amd.engine import Distillation, train_step as engine_train_step
-from clip_event_amd.losses import CriterionContrastive, CriterionSigmoid
+from clip_event_amd.losses import CriterionContrastive, CriterionMultiPositive, CriterionSigmoid
 from clip_event_amd.optim import FusedAdam, FusedLion, FusedSGD, build_lr_scheduler, build_optimizer, no_decay_groups
 from clip_event_amd.preprocess import Augment, preprocess
 
 CAPTIONS = list(S.ASCII_CAPTIONS)
 
 
-def batch(rng, B, K, dev, aug=None, draw=0, n_px=224):
+def batch(rng, B, K, dev, aug=None, draw=0, n_px=224, positives=None):
     sizes = [(int(rng.integers(240, 640)), int(rng.integers(240, 640))) for _ in range(B)]
     imgs = [torch.from_numpy(rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)).to(dev) for (w, h) in sizes]
     image = preprocess(imgs, n_px=n_px) if aug is None else aug(imgs, draw=draw)   # clip.py:62-69 / the training transform, on the GPU
     texts = [CAPTIONS[int(rng.integers(len(CAPTIONS)))] + f" number {int(rng.integers(1000))}" for _ in range(B * K)]
     text = clip.tokenize(texts)                                                 # clip.py:168-201: stays on the HOST, as the reference's loader
                                                                                 # yields it -- train_step copies it and keeps the caption lengths
-    yi, yt, ip = D.global_labels(B, 1, K - 1, True, device=dev)                 # dataset_voa.py:605-664
+    if positives is None:
+        yi, yt, ip = D.global_labels(B, 1, K - 1, True, device=dev)             # dataset_voa.py:605-664
+    else:                                                                       # group ids: the first `positives` captions of an image
+        yi, yt, ip = D.global_groups(B, positives, K - positives, device=dev)
     return (image, text, yi, yt, ip), imgs
 
 
@@ -83,7 +90,10 @@ def main():
                     help="train the image tower on a random 1 - P of the patches (CLIP.set_patch_dropout)")
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="weight EMA in the fused step (optimizer.enable_ema)")
     ap.add_argument("--ema-warmup", action="store_true", help="with --ema: ramp the decay up (optim.ema_rate)")
-    ap.add_argument("--loss", choices=("ce", "sigmoid"), default="ce", help="contrastive criterion: InfoNCE or the sigmoid pairwise loss")
+    ap.add_argument("--loss", choices=("ce", "sigmoid", "multipos"), default="ce",
+                    help="contrastive criterion: InfoNCE, the sigmoid pairwise loss, or InfoNCE over a set of positives per row")
+    ap.add_argument("--positives", type=int, default=None, metavar="P",
+                    help="with --loss multipos (default 2) or --loss sigmoid: positive captions per image, labels as group ids")
     ap.add_argument("--logit-bias", type=float, default=None, metavar="INIT",
                     help="with --loss sigmoid: initial logit bias (default -10)")
     ap.add_argument("--distill-arch", choices=sorted(S.GEOMETRY), default=None, metavar="ARCH",
@@ -117,6 +127,10 @@ def main():
         ap.error("--distill-weight / --distill-checkpoint go with --distill-arch")
     if args.logit_bias is not None and args.loss != "sigmoid":
         ap.error("--logit-bias goes with --loss sigmoid")
+    if args.positives is not None and (args.loss == "ce" or args.positives < 1):
+        ap.error("--positives P >= 1 goes with --loss multipos or --loss sigmoid")
+    if args.loss == "multipos" and args.positives is None:
+        args.positives = 2
     if args.ema_warmup and args.ema is None:
         ap.error("--ema-warmup goes with --ema")
     if args.adamw and args.optimizer != "adam":
@@ -129,11 +143,13 @@ def main():
     # step is lr per element whatever the gradient is: a tenth of Adam's rate, as its paper advises)
     cfg = {"optimizer": args.optimizer, "lr": {"adam": 1e-5, "lion": 1e-6, "sgd": 0.05}[args.optimizer], "weight_decay": 0.0, "momentum": 0.9, "lr_scheduler": "warmup",
            "max_epoch": 40, "warmup_epoch": 4, "lr_steps": [], "lr_gamma": 0.1, "task": "clipevent"}
-    B, K = 16, 3
+    B, K = 16, 3 if args.positives is None else args.positives + 2
+    P = args.positives
     rng = np.random.default_rng(0)
     model = S.synthetic_model("vit_b32", seed=0).to(dev)
     model.set_hyps(constrastive_overbatch=True, alignment=False, multiattention=False)
-    criterion = CriterionContrastive("ce") if args.loss == "ce" else CriterionSigmoid()
+    criterion = {"ce": lambda: CriterionContrastive("ce"), "sigmoid": lambda: CriterionSigmoid(multi_positive=P is not None),
+                 "multipos": CriterionMultiPositive}[args.loss]()
     if args.loss == "sigmoid":
         model.enable_logit_bias(-10.0 if args.logit_bias is None else args.logit_bias)      # before the optimiser is built
     if args.no_decay_groups or args.adamw:
@@ -206,7 +222,7 @@ def main():
         optimizer.enable_ema(args.ema, warmup=args.ema_warmup)
     scheduler = build_lr_scheduler(cfg, optimizer, 0)                           # engine.py:154-176
     aug = aug_at(size)
-    data, decoded = batch(rng, B, K, dev, aug, n_px=size)                       # one fixed batch: the loss must fall
+    data, decoded = batch(rng, B, K, dev, aug, n_px=size, positives=P)                       # one fixed batch: the loss must fall
     losses = []
     for it in range(20):
         if size_at(it) != size:                                                 # progressive resizing: the same images at the new size
@@ -223,7 +239,8 @@ def main():
     # must still fall; so must the sigmoid loss, which starts at about |logit_bias| per image -- every positive pair far on the
     # wrong side -- and has 20 steps at lr 1e-5 to pull the positives up; so must Lion's, which at a tenth of Adam's rate moves
     # every weight by at most 1e-6 per step where Adam's first steps move it by 1e-5: measured 6.72 -> 5.81)
-    slow = (args.lock_image_tower or args.lock_text_tower or args.patch_dropout or args.loss == "sigmoid" or args.distill_arch
+    # (with P positives per image the image rows cannot go below log P: the uniform target over P unrelated captions)
+    slow = (args.lock_image_tower or args.lock_text_tower or args.patch_dropout or args.loss != "ce" or args.distill_arch
             or args.optimizer == "lion" or args.augment or args.lora is not None or schedule)
     assert losses[-1] < (0.5 if not slow else 1.0) * losses[0]
     with tempfile.TemporaryDirectory() as d:
@@ -263,14 +280,14 @@ def main():
     la, lb = float(sum(v.detach() for v in a.values())), float(sum(v.detach() for v in b.values()))
     print(f"resumed run continues: loss {la:.5f} vs {lb:.5f}")
     assert abs(la - lb) < 1e-3 * max(1.0, abs(la))
-    new, _ = batch(rng, B, K, dev, aug, 21, n_px=size)                          # a fresh ragged batch goes through too
+    new, _ = batch(rng, B, K, dev, aug, 21, n_px=size, positives=P)                          # a fresh ragged batch goes through too
     ld = train_step(model2, criterion, optimizer2, *new, micro_batch=mb)
     scheduler2.step()
     assert all(torch.isfinite(v) for v in ld.values())
     # a longer stretch of fresh batches with no host synchronisation in the loop: host-side caption lengths, the run-ahead
     # limit of engine.train_step, the asynchronous poll of the fp16-stream clamp counters (every 16 optimiser steps)
     import time
-    batches = [batch(rng, 32, K, dev, aug, 22 + i, n_px=size)[0] for i in range(8)]
+    batches = [batch(rng, 32, K, dev, aug, 22 + i, n_px=size, positives=P)[0] for i in range(8)]
     for it in range(4):                                                         # new batch size: workspaces are allocated here
         train_step(model2, criterion, optimizer2, *batches[it], micro_batch=mb)
     torch.cuda.synchronize()
