@@ -44,6 +44,36 @@ __device__ __forceinline__ bf16x8 pack8(const f32x4& a, const f32x4& b) {
     return __builtin_bit_cast(bf16x8, v);
 }
 
+// Which head-dim columns a 16-row accumulator tile ct of the short kernels' output products (O^T, dQ^T, dV^T, dK^T: head dim on the
+// accumulator rows) holds is chosen by the address of the A operand's transposed read alone; products and summation order do not
+// depend on it.  A-row 4 q + e of tile ct (the 4-column chunk that lane li, q = li & 3, reads) is head-dim column
+//   plain (CE_ATTN_WIDE_STORES=0):  16 ct + 4 q + e            -> lane group g owns columns 16 ct + 4 g .. + 3: one 8-byte store per tile
+//   paired:   32 (ct >> 1) + 8 q + 4 (ct & 1) + e              -> g owns 32 p + 8 g .. + 7 in tiles 2 p, 2 p + 1: one 16-byte store per pair
+#ifndef CE_ATTN_WIDE_STORES
+#define CE_ATTN_WIDE_STORES 1
+#endif
+__device__ __forceinline__ constexpr int tile_col(int ct, int q) {      // first column of that chunk; q = g for the accumulator rows 4 g ..
+    return CE_ATTN_WIDE_STORES ? 32 * (ct >> 1) + 8 * q + 4 * (ct & 1) : 16 * ct + 4 * q;
+}
+typedef u32x4 __attribute__((aligned(8))) u32x4_a8;      // leading dimensions are multiples of 4 elements: rows are 8-byte aligned
+// the lane's 16 columns of one output row (row + h * 64 given; acc[ct][r] = column tile_col(ct, g) + r), scaled, as bf16
+__device__ __forceinline__ void store_row_tiles(bf16_t* row, const f32x4 (&acc)[4], int g, float mul) {
+#if CE_ATTN_WIDE_STORES
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        u32x4 pk = {pack_bf2(acc[2 * p][0] * mul, acc[2 * p][1] * mul), pack_bf2(acc[2 * p][2] * mul, acc[2 * p][3] * mul),
+                    pack_bf2(acc[2 * p + 1][0] * mul, acc[2 * p + 1][1] * mul), pack_bf2(acc[2 * p + 1][2] * mul, acc[2 * p + 1][3] * mul)};
+        *reinterpret_cast<u32x4_a8*>(row + tile_col(2 * p, g)) = pk;
+    }
+#else
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+        u32x2 pk = {pack_bf2(acc[ct][0] * mul, acc[ct][1] * mul), pack_bf2(acc[ct][2] * mul, acc[ct][3] * mul)};
+        *reinterpret_cast<u32x2*>(row + tile_col(ct, g)) = pk;
+    }
+#endif
+}
+
 // cooperative copy of the K and the V [L][64] head slices (row stride ld elements) into their LDS images, rows >= L zero-filled up to
 // Lp.  Bounds-checked buffer loads on one-slice descriptors (a row past L reads as zeros, no branch), BOTH slices' loads in flight
 // before the first LDS write: as two `if (r < L) v = load; store` loops, one per slice, every load was waited for inside its
@@ -152,21 +182,17 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const bf16_t* __restrict_
         for (int sidx = 0; sidx < T / 2; ++sidx) {
             if (2 * sidx >= Tl) continue;
             bf16x8 pf = pack8(s[2 * sidx], s[2 * sidx + 1]);
-            const char* vrow = sV + (32 * sidx + 4 * g + (li >> 2)) * ROW + (4 * (li & 3)) * 2;
+            const char* vrow = sV + (32 * sidx + 4 * g + (li >> 2)) * ROW;
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) {
-                bf16x8 vf = tr_pair(vrow + ct * 32, vrow + ct * 32 + 16 * ROW);
+                const char* vt = vrow + tile_col(ct, li & 3) * 2;
+                bf16x8 vf = tr_pair(vt, vt + 16 * ROW);
                 acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, acc[ct], 0, 0, 0);
             }
         }
         if (i < L) {
             const float inv = 1.0f / sum;
-            bf16_t* orow = o + (row0 + i) * ldo + h * HD + 4 * g;
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
-                u32x2 pk = {pack_bf2(acc[ct][0] * inv, acc[ct][1] * inv), pack_bf2(acc[ct][2] * inv, acc[ct][3] * inv)};
-                *reinterpret_cast<u32x2*>(orow + ct * 16) = pk;
-            }
+            store_row_tiles(o + (row0 + i) * ldo + h * HD, acc, g, inv);
             if (g == 0) lse[((long)b * H + h) * Lmax + i] = mx + __logf(sum);
         }
     }
@@ -177,9 +203,12 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const bf16_t* __restrict_
                                                        const bf16_t* __restrict__ o, long ldo,
                                                        const bf16_t* __restrict__ dout, long lddo,
                                                        const float* __restrict__ lse, bf16_t* __restrict__ dqkv,
-                                                       long lddq, float* __restrict__ bias_grad,
+                                                       long lddq, float* __restrict__ bias_grad, float* __restrict__ partials,
                                                        const int* __restrict__ cu, int Lmax, int H, int D,
                                                        int causal, float scale) {
+    // The in_proj bias gradient (192 column sums of dq | dk | dv per workgroup) leaves in one of two forms: added atomically into
+    // bias_grad[3][D], or -- `partials` -- stored as this workgroup's entries of partials[B][3][D] (sample b, columns h*64 ..), which
+    // ce_layernorm_fold adds up later: B H workgroups adding into the same 3 D addresses serialise at the memory side (6 of 48 us).
     // LDS: two [Lp][64] operand images (K,V in phase 1; re-filled with Q,dO for phase 2) + the P / dS images
     // [query i][key j]; the 192 column-sum floats live in the 32 pad bytes of the P image's first 24 rows.  72 KiB at L=77 (two
     // workgroups per CU), 40 KiB EXACTLY at L=50: four workgroups per CU (with the sums in 768 bytes of their own it was three).
@@ -190,14 +219,27 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const bf16_t* __restrict_
     char* sB = sA + Lp * ROW;                    // V, then dO
     char* sP = sB + Lp * ROW;
     char* sDS = sP + Lp * PROW;
-    // [3][64] column sums of dq | dk | dv (in_proj bias gradient): element i in the pad of P-image row i >> 3 (the images use bytes 0 .. 2 Lp - 1 of a row)
-    auto csum = [&](int i) __attribute__((always_inline)) -> float* { return reinterpret_cast<float*>(sP + (i >> 3) * PROW + Lp * 2 + (i & 7) * 4); };
+    // [3][64] column sums of dq | dk | dv (in_proj bias gradient), one set per wave: wave w's element i is float f = 192 w + i of the
+    // 2 Lp row pads of the P and dS images (8 floats each, row f >> 3; the images use bytes 0 .. 2 Lp - 1 of a row, and sDS = sP + Lp
+    // rows): 192 T <= 256 T floats.  A wave STORES the sums of its query strip (dq) and of its key tile (dk, dv) -- phase 2 hands a
+    // wave at most one tile, the launch has T >= ceil(L / 16) waves -- and the workgroup adds the sets in wave order at the end, so
+    // its sums come out the same bit for bit in every run (added with LDS atomics they came out in the order the waves arrived).
+    auto csum = [&](int w, int i) __attribute__((always_inline)) -> float* {
+        const int f = w * 192 + i;
+        return reinterpret_cast<float*>(sP + (f >> 3) * PROW + Lp * 2 + (f & 7) * 4);
+    };
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = blockDim.x >> 6;
     const int b = blockIdx.x / H, h = blockIdx.x - b * H;
     const long row0 = cu ? (long)cu[b] : (long)b * Lmax;         // packed batches: see attn_fwd_kernel
     const int L = cu ? min(cu[b + 1] - cu[b], Lmax) : Lmax;
-    if (L <= 0) return;
+    float* part = partials ? partials + (long)b * 3 * D + h * HD : nullptr;
+    if (L <= 0) {                                                // an empty sample still owns its partial entries: the fold reads every one
+        if (part)
+            for (int i = tid; i < 192; i += blockDim.x) part[(i >> 6) * D + (i & 63)] = 0.f;
+        return;
+    }
+    const bool sums = bias_grad || partials;
     const int Tl = ((L + 31) >> 5) << 1;                         // live 16-row tiles (even), block-uniform
     const int Ll = Tl * 16;
     const bf16_t* base = qkv + row0 * ld + h * HD;
@@ -205,7 +247,6 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const bf16_t* __restrict_
     const bf16_t* ob = o + row0 * ldo + h * HD;
     bf16_t* dbase = dqkv + row0 * lddq + h * HD;
 
-    for (int i = tid; i < 192; i += blockDim.x) *csum(i) = 0.f;  // the workgroup may have fewer than 192 threads
     const int li = lane & 15, g = lane >> 4;
     // ---- every global read of the workgroup is issued up front (one exposed memory latency instead of three):
     // the K, V, Q, dO head slices (<= 2 16-byte chunks per matrix per thread: blockDim = 64 T >= Lp*8/2) and this
@@ -297,22 +338,16 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const bf16_t* __restrict_
         for (int sidx = 0; sidx < T / 2; ++sidx) {
             if (2 * sidx >= Tl) continue;
             bf16x8 sf = pack8(ds[2 * sidx], ds[2 * sidx + 1]);
-            const char* krow = sA + (32 * sidx + 4 * g + (li >> 2)) * ROW + (4 * (li & 3)) * 2;
+            const char* krow = sA + (32 * sidx + 4 * g + (li >> 2)) * ROW;
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) {
-                bf16x8 kf = tr_pair(krow + ct * 32, krow + ct * 32 + 16 * ROW);
+                const char* kt = krow + tile_col(ct, li & 3) * 2;
+                bf16x8 kf = tr_pair(kt, kt + 16 * ROW);
                 acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, sf, acc[ct], 0, 0, 0);
             }
         }
-        if (iok) {
-            bf16_t* qrow = dbase + (long)i * lddq + 4 * g;
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
-                u32x2 pk = {pack_bf2(acc[ct][0], acc[ct][1]), pack_bf2(acc[ct][2], acc[ct][3])};
-                *reinterpret_cast<u32x2*>(qrow + ct * 16) = pk;
-            }
-        }
-        if (bias_grad) {   // sum over the strip's 16 queries (one DPP row); padded queries are exact zeros
+        if (iok) store_row_tiles(dbase + (long)i * lddq, acc, g, 1.0f);
+        if (sums) {   // sum over the strip's 16 queries (one DPP row); padded queries are exact zeros
             float vals[16];
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct)
@@ -320,7 +355,7 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const bf16_t* __restrict_
                 for (int r = 0; r < 4; ++r) vals[ct * 4 + r] = acc[ct][r];
             const float tot = row16_colsum(vals, li);
             const int k = row16_colsum_index(li);
-            atomicAdd(csum((k >> 2) * 16 + 4 * g + (k & 3)), tot);
+            *csum(wave, tile_col(k >> 2, g) + (k & 3)) = tot;
         }
     }
     __syncthreads();                                             // K, V no longer needed; P / dS images complete
@@ -354,27 +389,20 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const bf16_t* __restrict_
             bf16x8 pf = tr_pair(pcol, pcol + 4 * PROW);
             bf16x8 sf = tr_pair(scol, scol + 4 * PROW);
             // A operands: dO^T / Q^T rows c
-            const int roff = irow * ROW + (4 * (li & 3)) * 2;
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) {
-                bf16x8 dof = tr_pair(sB + roff + ct * 32, sB + roff + ct * 32 + 4 * ROW);
-                bf16x8 qf = tr_pair(sA + roff + ct * 32, sA + roff + ct * 32 + 4 * ROW);
+                const int roff = irow * ROW + tile_col(ct, li & 3) * 2;
+                bf16x8 dof = tr_pair(sB + roff, sB + roff + 4 * ROW);
+                bf16x8 qf = tr_pair(sA + roff, sA + roff + 4 * ROW);
                 av[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dof, pf, av[ct], 0, 0, 0);
                 ak[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, sf, ak[ct], 0, 0, 0);
             }
         }
         if (j < L) {
-            bf16_t* krow = dbase + (long)j * lddq + D + 4 * g;
-            bf16_t* vrow = dbase + (long)j * lddq + 2 * D + 4 * g;
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
-                u32x2 pk = {pack_bf2(ak[ct][0], ak[ct][1]), pack_bf2(ak[ct][2], ak[ct][3])};
-                u32x2 pv = {pack_bf2(av[ct][0], av[ct][1]), pack_bf2(av[ct][2], av[ct][3])};
-                *reinterpret_cast<u32x2*>(krow + ct * 16) = pk;
-                *reinterpret_cast<u32x2*>(vrow + ct * 16) = pv;
-            }
+            store_row_tiles(dbase + (long)j * lddq + D, ak, g, 1.0f);
+            store_row_tiles(dbase + (long)j * lddq + 2 * D, av, g, 1.0f);
         }
-        if (bias_grad) {   // rows j >= L of the tile are exact zeros (their P / dS columns are)
+        if (sums) {   // rows j >= L of the tile are exact zeros (their P / dS columns are)
             float vk[16], vv[16];
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct)
@@ -385,13 +413,19 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const bf16_t* __restrict_
                 }
             const float tk = row16_colsum(vk, li), tv = row16_colsum(vv, li);
             const int k = row16_colsum_index(li);
-            atomicAdd(csum(64 + (k >> 2) * 16 + 4 * g + (k & 3)), tk);
-            atomicAdd(csum(128 + (k >> 2) * 16 + 4 * g + (k & 3)), tv);
+            *csum(jt, 64 + tile_col(k >> 2, g) + (k & 3)) = tk;
+            *csum(jt, 128 + tile_col(k >> 2, g) + (k & 3)) = tv;
         }
     }
-    if (bias_grad) {
+    if (sums) {
         __syncthreads();
-        for (int i = tid; i < 192; i += blockDim.x) atomicAdd(bias_grad + (i >> 6) * D + h * HD + (i & 63), *csum(i));
+        for (int i = tid; i < 192; i += blockDim.x) {            // the workgroup may have fewer than 192 threads
+            const int nset = i < 64 ? Tl : nkt;                     // dq: one set per live strip; dk, dv: one per key tile (jt = wave there)
+            float t = 0.f;
+            for (int w = 0; w < nset; ++w) t += *csum(w, i);
+            if (part) part[(i >> 6) * D + (i & 63)] = t;
+            else atomicAdd(bias_grad + (i >> 6) * D + h * HD + (i & 63), t);
+        }
     }
 }
 
@@ -1016,6 +1050,37 @@ extern "C" int ce_attention_fwd(const void* qkv, long ld, void* o, long ldo, flo
     return 0;
 }
 
+// the one-workgroup-per-(sample, head) backward (L <= 128) in either form of the bias gradient (attn_bwd_kernel): atomic into
+// bias_grad (nullable), or per-workgroup entries of partials
+static int attn_bwd_short(const void* qkv, long ld, const void* o, long ldo, const void* dout, long lddo, const float* lse,
+                          void* dqkv, long lddq, float* bias_grad, float* partials, const int* cu_seqlens, int B, int L, int H,
+                          int causal, void* stream) {
+    const int D = H * HD;
+    const int T = tiles_for(L);
+    const int Lp = T * 16;
+    int nw = T;
+    if (nw > 8) nw = 8;
+    const size_t lds = 2 * (size_t)Lp * ROW + 2 * (size_t)Lp * (Lp * 2 + 32);      // (the bias-gradient sums sit in the P image's row pads)
+    const float scale = 0.125f;
+    hipStream_t s = (hipStream_t)stream;
+    CeProfScope prof(CE_PROF_ATTN_BWD, 10.0 * B * H * (double)L * L * HD, 2.0 * (double)B * L * (8.0 * D), s);
+#define CALL(TT)                                                                                                   \
+    do {                                                                                                           \
+        static std::once_flag attr;                                                                                \
+        std::call_once(attr, [] {                                                                                  \
+            hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<TT>),                                \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                           \
+        });                                                                                                        \
+        hipLaunchKernelGGL(attn_bwd_kernel<TT>, dim3(B * H), dim3(64 * nw), lds, s, (const bf16_t*)qkv, ld,        \
+                           (const bf16_t*)o, ldo, (const bf16_t*)dout, lddo, lse, (bf16_t*)dqkv, lddq, bias_grad, partials, cu_seqlens, L, \
+                           H, D, causal, scale);                                                                           \
+    } while (0)
+    ATTN_DISPATCH(T, CALL);
+#undef CALL
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int ce_attention_bwd(const void* qkv, long ld, const void* o, long ldo, const void* dout, long lddo,
                                 const float* lse, void* dqkv, long lddq, float* bias_grad, const int* cu_seqlens, int B,
                                 int L, int H, int causal, void* stream) {
@@ -1053,27 +1118,15 @@ extern "C" int ce_attention_bwd(const void* qkv, long ld, const void* o, long ld
         CE_LAUNCH_CHECK();
         return 0;
     }
-    const int T = tiles_for(L);
-    const int Lp = T * 16;
-    int nw = T;
-    if (nw > 8) nw = 8;
-    const size_t lds = 2 * (size_t)Lp * ROW + 2 * (size_t)Lp * (Lp * 2 + 32);      // (the bias-gradient sums sit in the P image's row pads)
-    const float scale = 0.125f;
-    hipStream_t s = (hipStream_t)stream;
-    CeProfScope prof(CE_PROF_ATTN_BWD, 10.0 * B * H * (double)L * L * HD, 2.0 * (double)B * L * (8.0 * D), s);
-#define CALL(TT)                                                                                                   \
-    do {                                                                                                           \
-        static std::once_flag attr;                                                                                \
-        std::call_once(attr, [] {                                                                                  \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<TT>),                                \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                           \
-        });                                                                                                        \
-        hipLaunchKernelGGL(attn_bwd_kernel<TT>, dim3(B * H), dim3(64 * nw), lds, s, (const bf16_t*)qkv, ld,        \
-                           (const bf16_t*)o, ldo, (const bf16_t*)dout, lddo, lse, (bf16_t*)dqkv, lddq, bias_grad, cu_seqlens, L, \
-                           H, D, causal, scale);                                                                           \
-    } while (0)
-    ATTN_DISPATCH(T, CALL);
-#undef CALL
-    CE_LAUNCH_CHECK();
-    return 0;
+    return attn_bwd_short(qkv, ld, o, ldo, dout, lddo, lse, dqkv, lddq, bias_grad, nullptr, cu_seqlens, B, L, H, causal, stream);
+}
+
+extern "C" int ce_attention_bwd_partials(const void* qkv, long ld, const void* o, long ldo, const void* dout, long lddo,
+                                         const float* lse, void* dqkv, long lddq, float* partials, const int* cu_seqlens, int B,
+                                         int L, int H, int causal, void* stream) {
+    CE_CHECK_ARG(B > 0 && L > 0 && H > 0, "ce_attention_bwd_partials: empty problem");
+    CE_CHECK_ARG(L <= 128, "ce_attention_bwd_partials: sequences of at most 128 tokens (got %d)", L);
+    CE_CHECK_ARG(partials, "ce_attention_bwd_partials: null partials buffer");
+    CE_CHECK_ARG(ld % 8 == 0 && ldo % 8 == 0 && lddo % 8 == 0 && lddq % 4 == 0, "ce_attention_bwd_partials: bad leading dimension");
+    return attn_bwd_short(qkv, ld, o, ldo, dout, lddo, lse, dqkv, lddq, nullptr, partials, cu_seqlens, B, L, H, causal, stream);
 }

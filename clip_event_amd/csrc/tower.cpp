@@ -28,8 +28,10 @@ constexpr int WG_MAX_BLOCKS = TN_GROUP_MAX_BLOCKS;   // blocks per grouped launc
 constexpr int WG_SETS = WG_MAX_BLOCKS + 1;  // a block writes its own set and the next block's dxb
 // LayerNorm-backward partial sums: a ring of LNP_RING buffer sets (two per block); ce_layernorm_fold runs whenever the ring is
 // full and at the end of a backward call, so a tower workspace carries 8 sets, not one per layer (ViT-L: 24) -- they only live
-// between a LayerNorm backward and the next fold on the same stream.
+// between a LayerNorm backward and the next fold on the same stream.  Towers of at most ATTN_FOLD_TOKENS tokens carry a third
+// buffer per slot: the attention backward's partial in_proj bias gradient (ce_attention_bwd_partials), folded by the same launch.
 constexpr int LNP_RING = 8;
+constexpr int ATTN_FOLD_TOKENS = 128;       // ce_attention_bwd_partials: the one-workgroup-per-(sample, head) kernel only
 
 struct Carver {
     char* base;
@@ -64,6 +66,7 @@ struct Layout {
     float *xs_in, *xs_mid, *dxs_mid, *means, *rstds;
     bf16_t *os, *h2s, *as, *gs, *dxbs, *dxb2s, *das, *dhs, *dos;
     float* lnp[LNP_RING][2];        // backward: per-workgroup partial sums of the two LayerNorm backwards of a block ([blocks][3][width], ce_layernorm_fold), ring slot l % LNP_RING
+    float* attnp[LNP_RING];         // backward: the attention backward's partial bias gradient ([batch][3][width]), same ring; tokens <= ATTN_FOLD_TOKENS only
     size_t bytes;
 };
 
@@ -109,6 +112,8 @@ void carve(const ce_tower_desc* d, int batch, size_t rows, void* ws, Layout& L) 
         L.lnp[l][0] = l < d->layers ? c.take<float>(lnp_floats) : nullptr;
         L.lnp[l][1] = l < d->layers ? c.take<float>(lnp_floats) : nullptr;
     }
+    for (int l = 0; l < LNP_RING; ++l)
+        L.attnp[l] = (l < d->layers && d->tokens <= ATTN_FOLD_TOKENS) ? c.take<float>(Bn * 3 * w) : nullptr;
     L.bytes = (c.off + 255) & ~size_t(255);
 }
 
@@ -310,9 +315,23 @@ extern "C" int ce_tower_backward_range(const ce_tower_desc* d, int batch, int ro
     // carry instead of adding them atomically (every workgroup of a launch adds into the same rows: 3.7 us of a 23 us launch);
     // one ce_layernorm_fold at the end of the call adds them into the gradients.  CE_LN_FOLD=0: the atomic form.
     static const int ln_fold = getenv("CE_LN_FOLD") ? atoi(getenv("CE_LN_FOLD")) : 1;
-    ce_ln_fold_job fold_jobs[2 * LNP_RING];
-    int n_fold = 0;
-    int fold_rc = 0;
+    // The attention backward's in_proj bias gradient goes the same way (ce_attention_bwd_partials: batch * heads workgroups adding
+    // into the same 3 width addresses, 6 of 48 us), as a third job of the block's ring slot.  CE_ATTN_FOLD=0: the atomic form.
+    static const int attn_fold_env = getenv("CE_ATTN_FOLD") ? atoi(getenv("CE_ATTN_FOLD")) : 1;
+    const bool attn_fold = ln_fold && attn_fold_env && d->tokens <= ATTN_FOLD_TOKENS;
+    ce_ln_fold_job fold_jobs[3 * LNP_RING];
+    int n_fold = 0, ring_used = 0;                                 // jobs queued; ring slots (blocks) they occupy
+    // called before a block queues its first job: block l uses slot l % LNP_RING, so after LNP_RING blocks the slots come round
+    auto ring_enter = [&]() -> int {
+        int rc = 0;
+        if (ring_used == LNP_RING) {                               // ring full: fold now, the slots are free again (same stream)
+            if (n_fold > 0) rc = ce_layernorm_fold(fold_jobs, n_fold, stream);
+            n_fold = 0;
+            ring_used = 0;
+        }
+        ++ring_used;
+        return rc;
+    };
     const int ln_blocks = ce_layernorm_bwd_blocks(M, w);
     auto ln_bwd = [&](const void* dy, const void* xin, const float* mean, const float* rstd, const float* gamma, void* dxb, float* dgw, float* dgb,
                       float* dxs, void* q8, float* partial) -> int {
@@ -320,14 +339,15 @@ extern "C" int ce_tower_backward_range(const ce_tower_desc* d, int batch, int ro
             return ce_layernorm_bwd_q8(dy, CE_T_BF16, w, xin, ST, w, nullptr, mean, rstd, gamma, dx, ST, dx, ST, w, dxb, w, dgw, dgb, dxs, GS, M, w, q8, w,
                                        L.q8s, stream);
         fold_jobs[n_fold++] = ce_ln_fold_job{partial, dgw, dgb, dxs, ln_blocks, w};
-        const int rc = ce_layernorm_bwd_partials(dy, CE_T_BF16, w, xin, ST, w, nullptr, mean, rstd, gamma, dx, ST, dx, ST, w, dxb, w, dxs ? 1 : 0, GS, M, w, q8, w,
-                                                 L.q8s, partial, stream);
-        if (rc == 0 && n_fold == 2 * LNP_RING) {               // ring full: fold now, the slots are free again (same stream)
-            fold_rc = ce_layernorm_fold(fold_jobs, n_fold, stream);
-            n_fold = 0;
-            return fold_rc;
-        }
-        return rc;
+        return ce_layernorm_bwd_partials(dy, CE_T_BF16, w, xin, ST, w, nullptr, mean, rstd, gamma, dx, ST, dx, ST, w, dxb, w, dxs ? 1 : 0, GS, M, w, q8, w,
+                                         L.q8s, partial, stream);
+    };
+    auto attn_bwd = [&](const BlockStash& s, const void* d_o, void* dqkv, float* g_b_qkv, float* partial) -> int {
+        if (!attn_fold || !g_b_qkv)
+            return ce_attention_bwd(s.qkv, 3 * w, s.o, w, d_o, w, s.lse, dqkv, 3 * w, g_b_qkv, cu_seqlens, batch, d->tokens, d->heads, d->causal, stream);
+        fold_jobs[n_fold++] = ce_ln_fold_job{partial, g_b_qkv, g_b_qkv + w, g_b_qkv + 2 * w, batch, w};
+        return ce_attention_bwd_partials(s.qkv, 3 * w, s.o, w, d_o, w, s.lse, dqkv, 3 * w, partial, cu_seqlens, batch, d->tokens, d->heads, d->causal,
+                                         stream);
     };
     // Where to cut the block sequence into grouped launches: tn_group_cuts (tn_plan.cpp) minimises the rounds the launches
     // take.  ViT-B/32 image tower, 108 tiles per block, 11 blocks below the pruned one: 7 blocks (756 tiles, 2.95 rounds) +
@@ -388,8 +408,8 @@ extern "C" int ce_tower_backward_range(const ce_tower_desc* d, int batch, int ro
                        stream));
         // attention sees dO only on the selected rows
         TRY(ce_scatter_rows_zero(L.dos, w * 2L, L.d_o, w * 2L, sel_rows, Bn, M, w * 2, stream));
-        TRY(ce_attention_bwd(s.qkv, 3 * w, s.o, w, L.d_o, w, s.lse, L.dqkv[q], 3 * w, p.g_b_qkv, cu_seqlens, batch, d->tokens, d->heads,
-                             d->causal, stream));
+        TRY(ring_enter());
+        TRY(attn_bwd(s, L.d_o, L.dqkv[q], p.g_b_qkv, L.attnp[l % LNP_RING]));
         {
             const void* P[3] = {L.dxbs, L.das, L.dxb2s};
             const long ldp[3] = {w, 4L * w, w};
@@ -421,6 +441,7 @@ extern "C" int ce_tower_backward_range(const ce_tower_desc* d, int batch, int ro
         const int q = l % WG_SETS;
         bf16_t *dxb_a = L.dxb[q], *dxb_b = L.dxb2[q], *da = L.da[q], *dqkv = L.dqkv[q];
         const void* x_in = (l == 0) ? x0 : L.blk[l - 1].x_out;
+        TRY(ring_enter());
         // ---- mlp.c_proj : x_out = x_mid + g Wp^T + bp ----
         TRY(linear(b8, L, q8_of, dxb_a, w, p.wt_proj, p.wt8_proj, p.st8_proj, M, 4 * w, w, CE_EPI_GELUGRAD_BF16, nullptr, nullptr, 0, da, 4 * w, p.g_b_fc,
                        4 * w, s.a, 4 * w, stream));                               // da = (dx Wp) * a (the saved gelu'); g_b_fc += colsum(da)
@@ -435,8 +456,7 @@ extern "C" int ce_tower_backward_range(const ce_tower_desc* d, int batch, int ro
         TRY(linear(b8, L, q8_of, dxb_b, w, p.wt_out, p.wt8_out, p.st8_out, M, w, w, CE_EPI_BF16, nullptr, nullptr, 0, L.d_o, w, nullptr, 0, nullptr, 0,
                        stream));                                                  // d_o = dx Wo
         // ---- attention core ----
-        TRY(ce_attention_bwd(s.qkv, 3 * w, s.o, w, L.d_o, w, s.lse, dqkv, 3 * w, p.g_b_qkv, cu_seqlens, batch, d->tokens, d->heads,
-                             d->causal, stream));
+        TRY(attn_bwd(s, L.d_o, dqkv, p.g_b_qkv, L.attnp[l % LNP_RING]));
         // ---- the four weight gradients of this block: queued, launched with the neighbouring blocks' ----
         queue(dxb_a, w, s.g, 4L * w, w, 4 * w, p.g_w_proj, 4L * w);
         queue(da, 4L * w, s.h2, w, 4 * w, w, p.g_w_fc, w);

@@ -192,6 +192,14 @@ int ce_attention_fwd(const void* qkv, long ld, void* o, long ldo, float* lse, co
 int ce_attention_bwd(const void* qkv, long ld, const void* o, long ldo, const void* dout, long lddo,
                      const float* lse, void* dqkv, long lddq, float* bias_grad, const int* cu_seqlens, int B, int L,
                      int H, int causal, void* stream);
+/* The same backward (L <= 128 only) WITHOUT atomics on the bias gradient: workgroup (b, h) stores its 192 column sums as
+ * partials[b][j][h*64 + c] (f32 [B][3][H*64]; j = dq | dk | dv), zeros for an empty sample of a packed batch, so every entry is
+ * written by every call and the buffer needs no memset.  It is ce_layernorm_fold's job format: one job with blocks = B, D = H*64,
+ * dw = bias_grad, db = bias_grad + D, dxsum = bias_grad + 2 D adds the rows into the gradient, in a fixed order (the atomic form's
+ * order varies from run to run).  dqkv is bit-identical to ce_attention_bwd's. */
+int ce_attention_bwd_partials(const void* qkv, long ld, const void* o, long ldo, const void* dout, long lddo,
+                              const float* lse, void* dqkv, long lddq, float* partials, const int* cu_seqlens, int B,
+                              int L, int H, int causal, void* stream);
 
 /* ---- input side, bookkeeping (embed.hip) ---- */
 /* image f32 [B,3,R,R] -> patch rows bf16 [B*(R/p)^2, k_padded], columns ordered (c, py, px) like the
