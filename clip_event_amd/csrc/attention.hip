@@ -498,10 +498,15 @@ __device__ __forceinline__ void long_block_coords(int xcd_order, int& blk, int& 
 // these kernels live on occupancy (barriers, dependent exp chains), not on LDS bandwidth.  Defaults: forward 1, dQ 2, dK / dV 1;
 // every form (CE_ATTN_NS_FWD / CE_ATTN_NS / CE_ATTN_NK, and CE_ATTN_XCD=0) runs tests/test_attention_ops.py's long table against
 // fp64 in a process of its own.
-template <int NS>
+//
+// PK (ce_attention_*_packed): a variable-length batch.  Sample b owns rows cu[b] .. cu[b+1]-1 and its own length L <= Lmax takes
+// the place of the uniform one everywhere (key / query block counts, load bounds, clamps, masks); the grid stays sized for Lmax
+// and a workgroup whose first query (forward, dQ) or first key (dK / dV) lies at or past L -- an empty sample included -- returns
+// before its first barrier.  lse and delta stay [B, H, Lmax].  A compile-time flag: the dense instantiations never read cu.
+template <int NS, bool PK>
 __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const bf16_t* __restrict__ qkv, long ld, bf16_t* __restrict__ o,
-                                                            long ldo, float* __restrict__ lse, int L, int H, int D,
-                                                            int causal, float scale, int xcd_order) {
+                                                            long ldo, float* __restrict__ lse, int Lmax, int H, int D,
+                                                            int causal, float scale, int xcd_order, const int* __restrict__ cu) {
     __shared__ __attribute__((aligned(16))) char smem[2 * LB * ROW];
     char* sK = smem;
     char* sV = smem + LB * ROW;
@@ -510,9 +515,16 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const bf16_t* __rest
     int qb, bh_;
     long_block_coords(xcd_order, qb, bh_);
     const int b = bh_ / H, h = bh_ - b * H;
-    const bf16_t* base = qkv + (long)b * L * ld + h * HD;
-    const int li = lane & 15, g = lane >> 4;
     constexpr int QB = LB * NS;                                // queries per workgroup
+    long row0 = (long)b * Lmax;
+    int L = Lmax;
+    if constexpr (PK) {
+        row0 = cu[b];
+        L = min(cu[b + 1] - cu[b], Lmax);
+        if (qb * QB >= L) return;                              // (workgroup-uniform; no barrier has been reached)
+    }
+    const bf16_t* base = qkv + row0 * ld + h * HD;
+    const int li = lane & 15, g = lane >> 4;
     int i[NS];
     bf16x8 qf[NS][2];
     float m[NS], l[NS];                                        // m: running maximum of the RAW scores q.k
@@ -613,13 +625,13 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const bf16_t* __rest
     for (int s = 0; s < NS; ++s) {
         if (i[s] < L) {
             const float inv = 1.0f / l[s];
-            bf16_t* orow = o + ((long)b * L + i[s]) * ldo + h * HD + 4 * g;
+            bf16_t* orow = o + (row0 + i[s]) * ldo + h * HD + 4 * g;
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) {
                 u32x2 pk = {pack_bf2(acc[s][ct][0] * inv, acc[s][ct][1] * inv), pack_bf2(acc[s][ct][2] * inv, acc[s][ct][3] * inv)};
                 *reinterpret_cast<u32x2*>(orow + ct * 16) = pk;
             }
-            if (g == 0) lse[((long)b * H + h) * L + i[s]] = m[s] * scale + __logf(l[s]);
+            if (g == 0) lse[((long)b * H + h) * Lmax + i[s]] = m[s] * scale + __logf(l[s]);
         }
     }
 }
@@ -657,13 +669,14 @@ __device__ __forceinline__ StripOps load_strip(const bf16_t* base, long ld, cons
 // K / V fragment read (see attn_fwd_long_kernel).  Per probability one fma + v_exp_f32 (p = exp2(s c - lse log2 e), c = scale
 // log2 e); the softmax scale of dS is applied once to the finished dQ accumulators (a power of two: the same bits); the
 // validity / causal mask only where the key block needs it (block-uniform).
-template <int NS>
+template <int NS, bool PK>
 __global__ __launch_bounds__(256) void attn_bwd_long_dq_kernel(const bf16_t* __restrict__ qkv, long ld,
                                                                const bf16_t* __restrict__ o, long ldo,
                                                                const bf16_t* __restrict__ dout, long lddo,
                                                                const float* __restrict__ lse, bf16_t* __restrict__ dqkv,
                                                                long lddq, float* __restrict__ bias_grad, float* __restrict__ delta_out,
-                                                               int L, int H, int D, int causal, float scale, int xcd_order) {
+                                                               int Lmax, int H, int D, int causal, float scale, int xcd_order,
+                                                               const int* __restrict__ cu) {
     __shared__ __attribute__((aligned(16))) char smem[2 * LB * ROW + 64 * 4];
     char* sK = smem;
     char* sV = smem + LB * ROW;
@@ -673,12 +686,19 @@ __global__ __launch_bounds__(256) void attn_bwd_long_dq_kernel(const bf16_t* __r
     int qb, bh_;
     long_block_coords(xcd_order, qb, bh_);
     const int b = bh_ / H, h = bh_ - b * H;
-    const bf16_t* base = qkv + (long)b * L * ld + h * HD;
-    const bf16_t* dob = dout + (long)b * L * lddo + h * HD;
-    const bf16_t* ob = o + (long)b * L * ldo + h * HD;
-    bf16_t* dbase = dqkv + (long)b * L * lddq + h * HD;
-    const int li = lane & 15, g = lane >> 4;
     constexpr int QB = LB * NS;
+    long row0 = (long)b * Lmax;
+    int L = Lmax;
+    if constexpr (PK) {                                        // see attn_fwd_long_kernel
+        row0 = cu[b];
+        L = min(cu[b + 1] - cu[b], Lmax);
+        if (qb * QB >= L) return;
+    }
+    const bf16_t* base = qkv + row0 * ld + h * HD;
+    const bf16_t* dob = dout + row0 * lddo + h * HD;
+    const bf16_t* ob = o + row0 * ldo + h * HD;
+    bf16_t* dbase = dqkv + row0 * lddq + h * HD;
+    const int li = lane & 15, g = lane >> 4;
     if (tid < 64) csum[tid] = 0.f;
     const float c2 = scale * 1.4426950408889634f;
     int i[NS];
@@ -690,11 +710,11 @@ __global__ __launch_bounds__(256) void attn_bwd_long_dq_kernel(const bf16_t* __r
     for (int s = 0; s < NS; ++s) {
         i[s] = qb * QB + (wave * NS + s) * 16 + li;
         iok[s] = i[s] < L;
-        q[s] = load_strip(base, ld, dob, lddo, ob, ldo, lse + ((long)b * H + h) * L, min(i[s], L - 1), g);
+        q[s] = load_strip(base, ld, dob, lddo, ob, ldo, lse + ((long)b * H + h) * Lmax, min(i[s], L - 1), g);
         lse2[s] = q[s].lse * 1.4426950408889634f;
         // delta_i = sum_c dO[i][c] O[i][c], computed here once per query: handed to the dK / dV kernel (launched behind this one),
         // whose every key block would otherwise recompute it for all L queries
-        if (delta_out && g == 0 && iok[s]) delta_out[((long)b * H + h) * L + i[s]] = q[s].dl;
+        if (delta_out && g == 0 && iok[s]) delta_out[((long)b * H + h) * Lmax + i[s]] = q[s].dl;
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) acc[s][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
@@ -798,14 +818,14 @@ __global__ __launch_bounds__(256) void attn_bwd_long_dq_kernel(const bf16_t* __r
 // products need as B operands (contraction over the queries, in the permuted order the transposed dO^T / Q^T reads match --
 // the forward kernel's P V trick with keys and queries swapped): no P / dS images in LDS, only the Q and dO blocks (requested
 // one block ahead) and 64 delta / log-sum-exp values.  Every Q / dO fragment read, plain and transposed, serves NK key tiles.
-template <int NK>
+template <int NK, bool PK>
 __global__ __launch_bounds__(256) void attn_bwd_long_dkv_kernel(const bf16_t* __restrict__ qkv, long ld,
                                                                 const bf16_t* __restrict__ o, long ldo,
                                                                 const bf16_t* __restrict__ dout, long lddo,
                                                                 const float* __restrict__ lse, bf16_t* __restrict__ dqkv,
                                                                 long lddq, float* __restrict__ bias_grad,
-                                                                const float* __restrict__ delta_in, int L, int H, int D,
-                                                                int causal, float scale, int xcd_order) {
+                                                                const float* __restrict__ delta_in, int Lmax, int H, int D,
+                                                                int causal, float scale, int xcd_order, const int* __restrict__ cu) {
     __shared__ __attribute__((aligned(16))) char smem[2 * LB * ROW + (2 * LB + 128) * 4];
     char* sQ = smem;
     char* sDO = sQ + LB * ROW;
@@ -817,13 +837,20 @@ __global__ __launch_bounds__(256) void attn_bwd_long_dkv_kernel(const bf16_t* __
     int kb, bh_;
     long_block_coords(xcd_order, kb, bh_);
     const int b = bh_ / H, h = bh_ - b * H;
-    const bf16_t* base = qkv + (long)b * L * ld + h * HD;
-    const bf16_t* dob = dout + (long)b * L * lddo + h * HD;
-    (void)o; (void)ldo;                                         // (delta arrives from the dQ kernel)
-    bf16_t* dbase = dqkv + (long)b * L * lddq + h * HD;
-    const float* lse_row = lse + ((long)b * H + h) * L;
-    const int li = lane & 15, g = lane >> 4;
     constexpr int KB = LB * NK;                                 // keys per workgroup
+    long row0 = (long)b * Lmax;
+    int L = Lmax;
+    if constexpr (PK) {                                         // see attn_fwd_long_kernel
+        row0 = cu[b];
+        L = min(cu[b + 1] - cu[b], Lmax);
+        if (kb * KB >= L) return;
+    }
+    const bf16_t* base = qkv + row0 * ld + h * HD;
+    const bf16_t* dob = dout + row0 * lddo + h * HD;
+    (void)o; (void)ldo;                                         // (delta arrives from the dQ kernel)
+    bf16_t* dbase = dqkv + row0 * lddq + h * HD;
+    const float* lse_row = lse + ((long)b * H + h) * Lmax;
+    const int li = lane & 15, g = lane >> 4;
     int j[NK];                                                  // this lane's keys (accumulator columns)
     bool jok[NK];
     bf16x8 kf[NK][2], vf[NK][2];                                // B operands: K / V rows of key j
@@ -850,7 +877,7 @@ __global__ __launch_bounds__(256) void attn_bwd_long_dkv_kernel(const bf16_t* __
     const float c2 = scale * 1.4426950408889634f;               // scale * log2(e)
     // per-query scalars of the block, one per thread: threads 0 .. 63 the log-sum-exp (stored in log2 units: p = exp2(s c - lse
     // log2 e)), threads 64 .. 127 delta = sum_c dO O as the dQ kernel left it; requested one block ahead like Q and dO
-    const float* delta_row = delta_in + ((long)b * H + h) * L;
+    const float* delta_row = delta_in + ((long)b * H + h) * Lmax;
     auto scalar_of = [&](int qb) __attribute__((always_inline)) -> float {
         if (tid >= 2 * LB) return 0.f;
         const int iq = min(qb * LB + (tid & (LB - 1)), L - 1);
@@ -1012,6 +1039,59 @@ float* delta_scratch(hipStream_t s, size_t floats) {
         default: CE_CHECK_ARG(false, "attention: sequence length %d not supported", L); \
     }
 
+// The launches of the long kernels (L > 128), dense (PK = false, cu unused) or packed (cu = the samples' row offsets, L = Lmax:
+// the grids are sized for it).  The profiler scope of a packed call keeps the B Lmax^2 convention of the short packed path.
+template <bool PK>
+static int attn_fwd_long(const void* qkv, long ld, void* o, long ldo, float* lse, const int* cu, int B, int L, int H, int causal,
+                         void* stream) {
+    const int D = H * HD;
+    hipStream_t sl = (hipStream_t)stream;
+    CeProfScope prof(CE_PROF_ATTN_FWD, 4.0 * B * H * (double)L * L * HD, 2.0 * (double)B * L * (4.0 * D), sl);
+    // strips per wave (CE_ATTN_NS_FWD = 1 / 2, default 1): a workgroup takes 64 NS queries
+    static const int ns = getenv("CE_ATTN_NS_FWD") ? atoi(getenv("CE_ATTN_NS_FWD")) : 1;
+    if (ns == 1)
+        hipLaunchKernelGGL((attn_fwd_long_kernel<1, PK>), dim3((L + LB - 1) / LB, B * H), dim3(256), 0, sl, (const bf16_t*)qkv, ld,
+                           (bf16_t*)o, ldo, lse, L, H, D, causal, 0.125f, attn_xcd_order(), cu);
+    else
+        hipLaunchKernelGGL((attn_fwd_long_kernel<2, PK>), dim3((L + 2 * LB - 1) / (2 * LB), B * H), dim3(256), 0, sl, (const bf16_t*)qkv, ld,
+                           (bf16_t*)o, ldo, lse, L, H, D, causal, 0.125f, attn_xcd_order(), cu);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
+template <bool PK>
+static int attn_bwd_long(const void* qkv, long ld, const void* o, long ldo, const void* dout, long lddo, const float* lse,
+                         void* dqkv, long lddq, float* bias_grad, const int* cu, int B, int L, int H, int causal, void* stream) {
+    const int D = H * HD;
+    hipStream_t sl = (hipStream_t)stream;
+    CeProfScope prof(CE_PROF_ATTN_BWD, 14.0 * B * H * (double)L * L * HD, 2.0 * (double)B * L * (8.0 * D), sl);
+    // strips (dQ) / key tiles (dK, dV) per wave: CE_ATTN_NS, CE_ATTN_NK = 1 / 2 (default 2 / 1: see attn_fwd_long_kernel)
+    static const int ns = getenv("CE_ATTN_NS") ? atoi(getenv("CE_ATTN_NS")) : 2;
+    static const int nk = getenv("CE_ATTN_NK") ? atoi(getenv("CE_ATTN_NK")) : 1;
+    const dim3 grid1((L + LB - 1) / LB, B * H), grid2((L + 2 * LB - 1) / (2 * LB), B * H);
+    // delta = rowsum(dO O), [B, H, L] floats: written by the dQ kernel, read by the dK / dV kernel behind it on the same stream;
+    // one grow-only scratch per stream, so two towers' backward passes on two streams never share it
+    float* delta = delta_scratch(sl, (size_t)B * H * L);
+    if (!delta) {
+        ce_set_error("%s: no memory for %ld bytes of scratch", PK ? "ce_attention_bwd_packed" : "ce_attention_bwd", (long)B * H * L * 4);
+        return -12; /* -ENOMEM */
+    }
+    if (ns == 1)
+        hipLaunchKernelGGL((attn_bwd_long_dq_kernel<1, PK>), grid1, dim3(256), 0, sl, (const bf16_t*)qkv, ld, (const bf16_t*)o, ldo,
+                           (const bf16_t*)dout, lddo, lse, (bf16_t*)dqkv, lddq, bias_grad, delta, L, H, D, causal, 0.125f, attn_xcd_order(), cu);
+    else
+        hipLaunchKernelGGL((attn_bwd_long_dq_kernel<2, PK>), grid2, dim3(256), 0, sl, (const bf16_t*)qkv, ld, (const bf16_t*)o, ldo,
+                           (const bf16_t*)dout, lddo, lse, (bf16_t*)dqkv, lddq, bias_grad, delta, L, H, D, causal, 0.125f, attn_xcd_order(), cu);
+    if (nk == 1)
+        hipLaunchKernelGGL((attn_bwd_long_dkv_kernel<1, PK>), grid1, dim3(256), 0, sl, (const bf16_t*)qkv, ld, (const bf16_t*)o, ldo,
+                           (const bf16_t*)dout, lddo, lse, (bf16_t*)dqkv, lddq, bias_grad, delta, L, H, D, causal, 0.125f, attn_xcd_order(), cu);
+    else
+        hipLaunchKernelGGL((attn_bwd_long_dkv_kernel<2, PK>), grid2, dim3(256), 0, sl, (const bf16_t*)qkv, ld, (const bf16_t*)o, ldo,
+                           (const bf16_t*)dout, lddo, lse, (bf16_t*)dqkv, lddq, bias_grad, delta, L, H, D, causal, 0.125f, attn_xcd_order(), cu);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int ce_attention_fwd(const void* qkv, long ld, void* o, long ldo, float* lse, const int* cu_seqlens, int B,
                                 int L, int H, int causal, void* stream) {
     CE_CHECK_ARG(B > 0 && L > 0 && H > 0, "ce_attention_fwd: empty problem");
@@ -1020,18 +1100,7 @@ extern "C" int ce_attention_fwd(const void* qkv, long ld, void* o, long ldo, flo
     if (L > 128) {
         CE_CHECK_ARG(!cu_seqlens, "ce_attention_fwd: packed batches are limited to 128 tokens per sample");
         CE_CHECK_ARG((long)B * H <= 65535, "ce_attention_fwd: B*H = %ld exceeds the grid", (long)B * H);
-        hipStream_t sl = (hipStream_t)stream;
-        CeProfScope prof(CE_PROF_ATTN_FWD, 4.0 * B * H * (double)L * L * HD, 2.0 * (double)B * L * (4.0 * D), sl);
-        // strips per wave (CE_ATTN_NS_FWD = 1 / 2, default 1): a workgroup takes 64 NS queries
-        static const int ns = getenv("CE_ATTN_NS_FWD") ? atoi(getenv("CE_ATTN_NS_FWD")) : 1;
-        if (ns == 1)
-            hipLaunchKernelGGL(attn_fwd_long_kernel<1>, dim3((L + LB - 1) / LB, B * H), dim3(256), 0, sl, (const bf16_t*)qkv, ld,
-                               (bf16_t*)o, ldo, lse, L, H, D, causal, 0.125f, attn_xcd_order());
-        else
-            hipLaunchKernelGGL(attn_fwd_long_kernel<2>, dim3((L + 2 * LB - 1) / (2 * LB), B * H), dim3(256), 0, sl, (const bf16_t*)qkv, ld,
-                               (bf16_t*)o, ldo, lse, L, H, D, causal, 0.125f, attn_xcd_order());
-        CE_LAUNCH_CHECK();
-        return 0;
+        return attn_fwd_long<false>(qkv, ld, o, ldo, lse, nullptr, B, L, H, causal, stream);
     }
     const int T = tiles_for(L);
     const int Lp = T * 16;
@@ -1086,37 +1155,10 @@ extern "C" int ce_attention_bwd(const void* qkv, long ld, const void* o, long ld
                                 int L, int H, int causal, void* stream) {
     CE_CHECK_ARG(B > 0 && L > 0 && H > 0, "ce_attention_bwd: empty problem");
     CE_CHECK_ARG(ld % 8 == 0 && ldo % 8 == 0 && lddo % 8 == 0 && lddq % 4 == 0, "ce_attention_bwd: bad leading dimension");
-    const int D = H * HD;
     if (L > 128) {
         CE_CHECK_ARG(!cu_seqlens, "ce_attention_bwd: packed batches are limited to 128 tokens per sample");
         CE_CHECK_ARG((long)B * H <= 65535, "ce_attention_bwd: B*H = %ld exceeds the grid", (long)B * H);
-        hipStream_t sl = (hipStream_t)stream;
-        CeProfScope prof(CE_PROF_ATTN_BWD, 14.0 * B * H * (double)L * L * HD, 2.0 * (double)B * L * (8.0 * D), sl);
-        // strips (dQ) / key tiles (dK, dV) per wave: CE_ATTN_NS, CE_ATTN_NK = 1 / 2 (default 2 / 1: see attn_fwd_long_kernel)
-        static const int ns = getenv("CE_ATTN_NS") ? atoi(getenv("CE_ATTN_NS")) : 2;
-        static const int nk = getenv("CE_ATTN_NK") ? atoi(getenv("CE_ATTN_NK")) : 1;
-        const dim3 grid1((L + LB - 1) / LB, B * H), grid2((L + 2 * LB - 1) / (2 * LB), B * H);
-        // delta = rowsum(dO O), [B, H, L] floats: written by the dQ kernel, read by the dK / dV kernel behind it on the same stream;
-        // one grow-only scratch per stream, so two towers' backward passes on two streams never share it
-        float* delta = delta_scratch(sl, (size_t)B * H * L);
-        if (!delta) {
-            ce_set_error("ce_attention_bwd: no memory for %ld bytes of scratch", (long)B * H * L * 4);
-            return -12; /* -ENOMEM */
-        }
-        if (ns == 1)
-            hipLaunchKernelGGL(attn_bwd_long_dq_kernel<1>, grid1, dim3(256), 0, sl, (const bf16_t*)qkv, ld, (const bf16_t*)o, ldo,
-                               (const bf16_t*)dout, lddo, lse, (bf16_t*)dqkv, lddq, bias_grad, delta, L, H, D, causal, 0.125f, attn_xcd_order());
-        else
-            hipLaunchKernelGGL(attn_bwd_long_dq_kernel<2>, grid2, dim3(256), 0, sl, (const bf16_t*)qkv, ld, (const bf16_t*)o, ldo,
-                               (const bf16_t*)dout, lddo, lse, (bf16_t*)dqkv, lddq, bias_grad, delta, L, H, D, causal, 0.125f, attn_xcd_order());
-        if (nk == 1)
-            hipLaunchKernelGGL(attn_bwd_long_dkv_kernel<1>, grid1, dim3(256), 0, sl, (const bf16_t*)qkv, ld, (const bf16_t*)o, ldo,
-                               (const bf16_t*)dout, lddo, lse, (bf16_t*)dqkv, lddq, bias_grad, delta, L, H, D, causal, 0.125f, attn_xcd_order());
-        else
-            hipLaunchKernelGGL(attn_bwd_long_dkv_kernel<2>, grid2, dim3(256), 0, sl, (const bf16_t*)qkv, ld, (const bf16_t*)o, ldo,
-                               (const bf16_t*)dout, lddo, lse, (bf16_t*)dqkv, lddq, bias_grad, delta, L, H, D, causal, 0.125f, attn_xcd_order());
-        CE_LAUNCH_CHECK();
-        return 0;
+        return attn_bwd_long<false>(qkv, ld, o, ldo, dout, lddo, lse, dqkv, lddq, bias_grad, nullptr, B, L, H, causal, stream);
     }
     return attn_bwd_short(qkv, ld, o, ldo, dout, lddo, lse, dqkv, lddq, bias_grad, nullptr, cu_seqlens, B, L, H, causal, stream);
 }
@@ -1129,4 +1171,29 @@ extern "C" int ce_attention_bwd_partials(const void* qkv, long ld, const void* o
     CE_CHECK_ARG(partials, "ce_attention_bwd_partials: null partials buffer");
     CE_CHECK_ARG(ld % 8 == 0 && ldo % 8 == 0 && lddo % 8 == 0 && lddq % 4 == 0, "ce_attention_bwd_partials: bad leading dimension");
     return attn_bwd_short(qkv, ld, o, ldo, dout, lddo, lse, dqkv, lddq, nullptr, partials, cu_seqlens, B, L, H, causal, stream);
+}
+
+// Variable-length batches of any length up to 4096: L <= 128 is ce_attention_fwd / ce_attention_bwd itself (the one-workgroup-per-
+// (sample, head) kernels, the same bits); longer, the long kernels in their packed form (attn_fwd_long_kernel).
+extern "C" int ce_attention_fwd_packed(const void* qkv, long ld, void* o, long ldo, float* lse, const int* cu_seqlens, int B,
+                                       int L, int H, int causal, void* stream) {
+    CE_CHECK_ARG(B > 0 && L > 0 && H > 0, "ce_attention_fwd_packed: empty problem");
+    CE_CHECK_ARG(cu_seqlens, "ce_attention_fwd_packed: null cu_seqlens");
+    CE_CHECK_ARG(ld % 8 == 0 && ldo % 4 == 0, "ce_attention_fwd_packed: ld must be a multiple of 8, ldo of 4");
+    if (L <= 128) return ce_attention_fwd(qkv, ld, o, ldo, lse, cu_seqlens, B, L, H, causal, stream);
+    CE_CHECK_ARG(L <= 4096, "ce_attention_fwd_packed: at most 4096 tokens per sample (got %d)", L);
+    CE_CHECK_ARG((long)B * H <= 65535, "ce_attention_fwd_packed: B*H = %ld exceeds the grid", (long)B * H);
+    return attn_fwd_long<true>(qkv, ld, o, ldo, lse, cu_seqlens, B, L, H, causal, stream);
+}
+
+extern "C" int ce_attention_bwd_packed(const void* qkv, long ld, const void* o, long ldo, const void* dout, long lddo,
+                                       const float* lse, void* dqkv, long lddq, float* bias_grad, const int* cu_seqlens, int B,
+                                       int L, int H, int causal, void* stream) {
+    CE_CHECK_ARG(B > 0 && L > 0 && H > 0, "ce_attention_bwd_packed: empty problem");
+    CE_CHECK_ARG(cu_seqlens, "ce_attention_bwd_packed: null cu_seqlens");
+    CE_CHECK_ARG(ld % 8 == 0 && ldo % 8 == 0 && lddo % 8 == 0 && lddq % 4 == 0, "ce_attention_bwd_packed: bad leading dimension");
+    if (L <= 128) return ce_attention_bwd(qkv, ld, o, ldo, dout, lddo, lse, dqkv, lddq, bias_grad, cu_seqlens, B, L, H, causal, stream);
+    CE_CHECK_ARG(L <= 4096, "ce_attention_bwd_packed: at most 4096 tokens per sample (got %d)", L);
+    CE_CHECK_ARG((long)B * H <= 65535, "ce_attention_bwd_packed: B*H = %ld exceeds the grid", (long)B * H);
+    return attn_bwd_long<true>(qkv, ld, o, ldo, dout, lddo, lse, dqkv, lddq, bias_grad, cu_seqlens, B, L, H, causal, stream);
 }

@@ -212,7 +212,10 @@ int forward_run(const ce_tower_desc* d, int batch, int rows, const int* cu_seqle
         if (lnq) q8_of = s.h1;
         TRY(linear(f8, L, q8_of, s.h1, w, p.w_qkv, p.w8_qkv, p.s8_qkv, M, 3 * w, w, CE_EPI_BIAS_BF16, p.b_qkv, nullptr, 0, s.qkv, 3 * w, nullptr, 0,
                        nullptr, 0, stream));
-        TRY(ce_attention_fwd(s.qkv, 3 * w, s.o, w, s.lse, cu_seqlens, batch, d->tokens, d->heads, d->causal, stream));
+        if (cu_seqlens && d->tokens > 128)       // packed captions of a long context: the tiled kernels with per-sample lengths
+            TRY(ce_attention_fwd_packed(s.qkv, 3 * w, s.o, w, s.lse, cu_seqlens, batch, d->tokens, d->heads, d->causal, stream));
+        else
+            TRY(ce_attention_fwd(s.qkv, 3 * w, s.o, w, s.lse, cu_seqlens, batch, d->tokens, d->heads, d->causal, stream));
         if (sel_rows && l + 1 == d->layers) {
             // pruned last block: only the selected token of each sample feeds the head, so the out-projection
             // and the MLP run on `batch` rows (75 % of this block's GEMM work is never needed)
@@ -343,6 +346,9 @@ extern "C" int ce_tower_backward_range(const ce_tower_desc* d, int batch, int ro
                                          L.q8s, partial, stream);
     };
     auto attn_bwd = [&](const BlockStash& s, const void* d_o, void* dqkv, float* g_b_qkv, float* partial) -> int {
+        if (cu_seqlens && d->tokens > 128)                         // (attn_fold is off above ATTN_FOLD_TOKENS: g_b_qkv as the dense long path)
+            return ce_attention_bwd_packed(s.qkv, 3 * w, s.o, w, d_o, w, s.lse, dqkv, 3 * w, g_b_qkv, cu_seqlens, batch, d->tokens, d->heads, d->causal,
+                                           stream);
         if (!attn_fold || !g_b_qkv)
             return ce_attention_bwd(s.qkv, 3 * w, s.o, w, d_o, w, s.lse, dqkv, 3 * w, g_b_qkv, cu_seqlens, batch, d->tokens, d->heads, d->causal, stream);
         fold_jobs[n_fold++] = ce_ln_fold_job{partial, g_b_qkv, g_b_qkv + w, g_b_qkv + 2 * w, batch, w};

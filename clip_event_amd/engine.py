@@ -452,6 +452,10 @@ def micro_batched_backward(model, criterion, image, text, labels_per_image, labe
         gs.expect_passes({t: len(chunks) for t in live})
     # every chunk, the shorter last one included, runs in buffers leased for a full chunk (the pool is keyed by byte count)
     model._lease_batch = {"vision": mb, "text": mb * K}
+    # ... and on the attention kernels the step's longest caption selects (functional.text_tower_tokens), not the chunk's own: a chunk
+    # of short captions would otherwise take the one-workgroup kernels where the unchunked step takes the tiled ones, and the
+    # chunked step would differ from it by more than a tile choice
+    model._route_longest = int(lens.max()) if len(lens) else None
     # patch dropout: ONE draw for the step; both passes of the chunk [lo, hi) run pinned to it with their samples counted from
     # lo, so the chunked step drops exactly the patches the unchunked step drops
     draw = model.next_patch_draw() if model.drops_patches() else None
@@ -493,6 +497,7 @@ def micro_batched_backward(model, criterion, image, text, labels_per_image, labe
             del outs
     finally:
         model._lease_batch = None
+        model._route_longest = None
     return loss_dict
 
 

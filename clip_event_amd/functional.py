@@ -109,11 +109,27 @@ def _tower_backward(model, desc, tower: str, batch: int, rows: int, cu, x0, leas
 class TextPacking:
     """Row layout of one caption batch in the text tower.  ``cu is None``: dense, every caption owns
     ``context_length`` rows.  Otherwise only the live tokens (SOT .. EOT) are rows: ``cu`` int32 [n+1] prefix sums,
-    ``src`` int32 [rows] flat index into the [n, T] id matrix, ``sel`` int32 [n] = each caption's EOT row."""
-    __slots__ = ("rows", "cu", "src", "sel", "_keep")
+    ``src`` int32 [rows] flat index into the [n, T] id matrix, ``sel`` int32 [n] = each caption's EOT row, ``longest`` = the
+    longest caption's length (host int; ``text_tower_tokens`` routes by it)."""
+    __slots__ = ("rows", "cu", "src", "sel", "longest", "_keep")
 
-    def __init__(self, rows, cu, src, sel, keep=None):
-        self.rows, self.cu, self.src, self.sel, self._keep = rows, cu, src, sel, keep
+    def __init__(self, rows, cu, src, sel, keep=None, longest=None):
+        self.rows, self.cu, self.src, self.sel, self.longest, self._keep = rows, cu, src, sel, longest, keep
+
+
+SHORT_ATTENTION_TOKENS = 128      # the one-workgroup-per-(sample, head) attention kernels' limit
+
+
+def text_tower_tokens(run_length: int, longest: int, packed: bool) -> int:
+    """The ``tokens`` the text tower's descriptor gets for one pass (forward, backward, workspace and ``lse`` alike) at run
+    length ``run_length`` when the batch's longest caption has ``longest`` tokens.  Dense batches and contexts of at most 128
+    tokens run at the run length (what they always did).  A packed batch of a longer context whose captions all fit 128
+    tokens is sized for 128, so the short attention kernels run -- ordinary captions cost what they cost in a 77-token
+    context; any longer caption sends the pass to the packed long kernels at the run length."""
+    run_length, longest = int(run_length), int(longest)
+    if not packed or run_length <= SHORT_ATTENTION_TOKENS:
+        return run_length
+    return SHORT_ATTENTION_TOKENS if longest <= SHORT_ATTENTION_TOKENS else run_length
 
 
 def attach_lengths(text: torch.Tensor, lengths) -> torch.Tensor:
@@ -212,7 +228,8 @@ def text_packing(model, text, lengths=None) -> TextPacking:
         meta.numpy()[n + 1: 2 * n + 1] = cu[1:] - 1
         meta.numpy()[2 * n + 1:] = src
         meta_d = meta.to(dev, non_blocking=True)
-        pk = TextPacking(R, meta_d[: n + 1], meta_d[2 * n + 1:], meta_d[n + 1: 2 * n + 1], keep=(meta, meta_d))
+        pk = TextPacking(R, meta_d[: n + 1], meta_d[2 * n + 1:], meta_d[n + 1: 2 * n + 1], keep=(meta, meta_d),
+                         longest=int(lens.max()))
     if len(cache) >= _PACK_CACHE_SLOTS:
         for k in [k for k, v in cache.items() if v[0]() is None] or [next(iter(cache))]:
             cache.pop(k, None)
@@ -292,7 +309,19 @@ def _vision_desc(model, tokens: int):
     copy (cached per length on ``model._vdesc``, so it goes when the device tables are rebuilt) that shares the block table
     and whose per-pass switches are brought up to date here.  The workspace lease is sized from it: with patch dropout the
     stash shrinks with the rows."""
-    base = model._vdesc
+    return _desc_at(model._vdesc, tokens)
+
+
+def _text_desc(model, pk: "TextPacking"):
+    """The text tower's descriptor for the packing ``pk`` at the current run length (``text_tower_tokens``): ``model._tdesc``
+    itself at the native length, otherwise a copy cached on it as ``_vision_desc``'s are.  ``model._route_longest`` (set by the
+    micro-batched step: the longest caption of the whole step) keeps every chunk on the attention kernels the unchunked step takes."""
+    T = model.context_length
+    longest = T if pk.longest is None else max(pk.longest, getattr(model, "_route_longest", None) or 0)
+    return _desc_at(model._tdesc, text_tower_tokens(T, longest, pk.cu is not None))
+
+
+def _desc_at(base, tokens: int):
     if tokens == base.tokens:
         return base
     cache = base.__dict__.setdefault("_by_tokens", {})
@@ -463,20 +492,25 @@ class EncodeTextFn(torch.autograd.Function):
         M = pk.rows                                        # activation rows: live tokens only when packed
         sdt, ST = _stream_type(model)                      # residual stream: fp32, or fp16 (model.stream16)
         x0 = _empty((M, D), sdt, dev)
-        check(cl.ce_token_embed_t(ptr(text), ptr(pk.src), ptr(P["token_embedding.weight"]), ptr(P["positional_embedding"]),
+        pos = model._text_pos_run()                        # the table at this run length, DESIGN.md 4o
+        if pos is None:
+            pos = P["positional_embedding"]
+        desc = _text_desc(model, pk)
+        check(cl.ce_token_embed_t(ptr(text), ptr(pk.src), ptr(P["token_embedding.weight"]), ptr(pos),
                                   ptr(x0), ST, M, T, D, model.vocab_size, s), "ce_token_embed")
         rows = pk.sel                                      # EOT row of each caption (argmax token id, model_clip.py:415)
         xN = _empty((n, D), sdt, dev)                      # pruned last block: only the EOT rows are produced
         if infer:                  # grad mode was off at the call (CLIP.encode_text): no stash, nothing kept for a backward
-            _tower_forward_infer(model, model._tdesc, "text", n, M, pk.cu, x0, xN, rows)
+            _tower_forward_infer(model, desc, "text", n, M, pk.cu, x0, xN, rows)
         else:
-            lease = _tower_workspace(model, model._tdesc, n, "text")
-            check(cl.ce_tower_forward(ctypes.byref(model._tdesc), n, M, ptr(pk.cu), ptr(x0), ptr(lease.buf), ptr(xN), ptr(rows),
+            lease = _tower_workspace(model, desc, n, "text")
+            check(cl.ce_tower_forward(ctypes.byref(desc), n, M, ptr(pk.cu), ptr(x0), ptr(lease.buf), ptr(xN), ptr(rows),
                                       s), "ce_tower_forward(text)")
         feat, hfin, mean_f, rstd_f = _tower_top_forward(model, xN, "ln_final", "text_projection")
         if infer:
             return feat
         ctx.model, ctx.lease, ctx.n = model, lease, n
+        ctx.T, ctx.keep, ctx.desc = T, model.context_keep, desc      # the run length, stretch and descriptor of THIS pass
         ctx.stream16 = sdt == torch.float16
         ctx.main_stream = getattr(model, "_main_stream", None)
         ctx.saved = (text, x0, xN, pk, hfin, mean_f, rstd_f)
@@ -490,25 +524,40 @@ class EncodeTextFn(torch.autograd.Function):
         cl, s = lib(), stream()
         text, x0, xN, pk, hfin, mean_f, rstd_f = ctx.saved
         dev = model._flat.device
-        T, D = model.context_length, model.transformer.width
+        T, D, desc = ctx.T, model.transformer.width, ctx.desc
         M, rows = pk.rows, pk.sel
         model._attach_grads()
         G = model._gview
         _check_stream(ctx, model)
         # dxn: [n, D] gradient at the EOT rows (dx_sel of the pruned tower: fp32)
-        dxn, gs = _tower_top_backward(model, model._tdesc, _f32(dfeat), xN, hfin, mean_f, rstd_f, "ln_final", "text_projection")
+        dxn, gs = _tower_top_backward(model, desc, _f32(dfeat), xN, hfin, mean_f, rstd_f, "ln_final", "text_projection")
         dx = _empty((M, D), xN.dtype, dev)
-        stop = _tower_backward(model, model._tdesc, "text", n, M, pk.cu, x0, lease, dx, rows, dxn)
+        stop = _tower_backward(model, desc, "text", n, M, pk.cu, x0, lease, dx, rows, dxn)
         lease.release()
         if stop > 0:      # as in EncodeImageFn.backward: no stream cast, no positional sum, no token-embedding scatter
             return _tower_backward_done(ctx, "text", 4)
         if gs is not None:            # the embedding gradients below take the fp32 gradient in true units
             dx = ops.cast_scaled(dx, torch.float32, gs, divide=True)
-        if pk.cu is None:
-            check(cl.ce_batch_reduce(ptr(dx), ptr(G("positional_embedding")), n, T * D, T * D, 1, s), "ce_batch_reduce(text pos)")
+        native = T == model.native_context_length
+        if not native and not model._pmap["positional_embedding"].requires_grad:
+            dpos = None                                        # a frozen table has no reader for either step
+        elif native:
+            dpos = G("positional_embedding")
         else:
-            check(cl.ce_pos_embed_bwd_packed(ptr(dx), ptr(pk.cu), ptr(G("positional_embedding")), n, T, D, s),
+            # the tower ran on the run-length table: reduce into a scratch of that length, then the transpose of the stretch adds
+            # into the parameter's gradient
+            dpos = _empty((T, D), torch.float32, dev)
+        if dpos is None:
+            pass
+        elif pk.cu is None:
+            check(cl.ce_batch_reduce(ptr(dx), ptr(dpos), n, T * D, T * D, 1 if native else 0, s), "ce_batch_reduce(text pos)")
+        else:
+            if not native:
+                dpos.zero_()
+            check(cl.ce_pos_embed_bwd_packed(ptr(dx), ptr(pk.cu), ptr(dpos), n, T, D, s),
                   "ce_pos_embed_bwd_packed")
+        if dpos is not None and not native:
+            posembed.stretch_backward(dpos, model.native_context_length, ctx.keep, accumulate=True, out=G("positional_embedding"))
         check(cl.ce_token_embed_bwd(ptr(text), ptr(pk.src), ptr(dx), ptr(G("token_embedding.weight")), M, D, model.vocab_size, s),
               "ce_token_embed_bwd")
         return _tower_backward_done(ctx, "text", 4)

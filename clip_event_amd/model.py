@@ -287,7 +287,10 @@ class CLIP(nn.Module):
         super().__init__()
         if isinstance(vision_layers, (tuple, list)):
             raise NotImplementedError("ModifiedResNet towers are out of scope (BASELINE.json names ViT only)")
-        self.context_length = context_length
+        # the length ``positional_embedding`` was built for; ``context_length`` is the one the text tower RUNS at
+        # (set_context_length stretches or truncates the table for another length) and equals it until that is called
+        self.context_length = self.native_context_length = context_length
+        self.context_keep = 20
         self.vision_width = vision_width
         self.embed_dim = embed_dim
         vision_heads = vision_width // 64
@@ -339,7 +342,7 @@ class CLIP(nn.Module):
     _RUNTIME = ("_flat", "_flat_grad", "_flat16", "_offsets", "_ranges", "_layer_end", "_pmap", "_pool", "_trigger",
                 "_versions", "_w16", "_w16t", "_kp", "_kp_real", "_conv_pad", "_conv_gpad", "_cast_list", "_tjobs",
                 "_tjobs_bwd", "_adam_tiles_ok", "_wt_fresh", "_wt_event", "_aux_stream", "_mirror_fresh", "_mirror_versions", "_vdesc", "_tdesc", "_vblocks", "_tblocks",
-                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch", "_lease_batch", "_plist", "_plans", "_patch_pin", "_patch_off", "_lora_tab", "_pos_cache", "_pos_epoch")
+                "_side_streams", "_main_stream", "_pack_cache", "_cls_rows", "_sat", "_sat_poll", "_step_events", "grad_sync", "_w8", "_fp8_fresh", "_zero_table", "_zero_tables", "_adam_segs", "_first_touch", "_lease_batch", "_route_longest", "_plist", "_plans", "_patch_pin", "_patch_off", "_lora_tab", "_pos_cache", "_pos_epoch", "_tpos_cache")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -1028,12 +1031,13 @@ class CLIP(nn.Module):
             return d
 
         self._vdesc = desc("visual.transformer.", self.visual.transformer, self.visual.native_patch_num ** 2 + 1, False)
-        self._tdesc = desc("transformer.", self.transformer, self.context_length, True)
+        self._tdesc = desc("transformer.", self.transformer, self.native_context_length, True)
         self._w8 = None
         self._fp8_fresh = False
         self._lora_tab = self._build_lora_table()
         self._pos_cache = {}              # run grid -> (resampled positional table, what it was made from): _refresh_pos
         self._pos_epoch = 0
+        self._tpos_cache = {}             # (run length, keep) -> (text positional table at that length, what it was made from)
 
     def _job_table(self, names, groups=None):
         """``(device table, njobs, tiles)``: one ``ce_transpose_job`` per name (bf16 operand copy -> its W^T copy); ``groups``
@@ -1111,6 +1115,7 @@ class CLIP(nn.Module):
             if self.fp8 and not self._fp8_fresh:
                 self._refresh_fp8()
             self._refresh_pos(False)
+            self._refresh_text_pos(False)
             return
         s = stream()
         cl = lib()
@@ -1154,6 +1159,7 @@ class CLIP(nn.Module):
         if self.fp8:
             self._refresh_fp8()
         self._refresh_pos(True)
+        self._refresh_text_pos(True)
 
     # ---- the image tower at another resolution -------------------------------------------------------------------
     def set_image_size(self, size: Optional[int] = None):
@@ -1188,6 +1194,42 @@ class CLIP(nn.Module):
             return
         table = posembed.resample(p.detach(), g, out=None if hit is None else hit[0])
         self._pos_cache[g] = (table, key)
+
+    # ---- the text tower at another context length ----------------------------------------------------------------
+    def set_context_length(self, T: Optional[int] = None, keep: int = 20):
+        """Run (and train) the text tower on ``[n, T]`` token matrices, ``T`` in 2 .. 1024.  ``None`` or the native length switches
+        the feature off.  The parameter ``positional_embedding`` keeps its shape ``[native_context_length, d]``; the tower adds the
+        table ``posembed.text_weights(native, T, keep)`` makes of it -- longer: the first ``keep`` rows copied, the rest stretched
+        linearly; shorter: truncated -- and the backward applies the transpose.  ``context_length`` reports the run length from here
+        on, ``native_context_length`` the parameter's.  A run-time switch like ``set_image_size``: not a parameter or a buffer, so not
+        in ``state_dict()`` or a checkpoint; it may change between steps.  Returns the length."""
+        from .posembed import check_context_length
+        T = self.native_context_length if T is None else check_context_length(T)
+        keep = int(keep)
+        if keep < 0:
+            raise ValueError(f"keep must be non-negative (got {keep})")
+        self.context_length, self.context_keep = T, keep
+        return T
+
+    def _refresh_text_pos(self, moved: bool):
+        """``_refresh_pos`` for the text table: one small launch when the run length's table is missing or older than the
+        parameter; at the native length nothing is allocated or launched."""
+        T = self.context_length
+        if T == self.native_context_length:
+            return
+        from . import posembed
+        p = self._pmap["positional_embedding"]
+        key = (self._pos_epoch, p._version)       # (_refresh_pos has advanced the epoch if the masters moved)
+        hit = self._tpos_cache.get((T, self.context_keep))
+        if hit is not None and hit[1] == key:
+            return
+        table = posembed.stretch(p.detach(), T, self.context_keep, out=None if hit is None else hit[0])
+        self._tpos_cache[(T, self.context_keep)] = (table, key)
+
+    def _text_pos_run(self):
+        """The positional table the text tower adds at the current run length: None at the native length (the parameter itself)."""
+        T = self.context_length
+        return None if T == self.native_context_length else self._tpos_cache[(T, self.context_keep)][0]
 
     def _pos_run(self):
         """The positional table the image tower adds at the current run size: None at the native size (the parameter itself)."""

@@ -5,6 +5,10 @@
 as one dense matrix per axis, host arithmetic in fp64.  ``resample`` / ``resample_backward`` apply it (and its transpose) on
 the device with the fp32 roundings of those matrices (``ce_pos_resample_fwd`` / ``ce_pos_resample_bwd``);
 ``resize_visual_state_dict`` applies the fp64 matrices on the host, once, to a state dict.
+
+The text tower's table at another context length is the second half of the module: ``text_weights`` defines the
+operator (leading rows copied, the rest stretched linearly; truncation when shorter), ``stretch`` / ``stretch_backward`` apply it
+on the device (``ce_pos_stretch_fwd`` / ``ce_pos_stretch_bwd``), ``stretch_host`` / ``resize_text_state_dict`` on the host.
 """
 from __future__ import annotations
 
@@ -143,4 +147,143 @@ def resize_visual_state_dict(sd: dict, image_size: int) -> dict:
     out = dict(sd)
     if grid_of(pos.shape[0]) != g:
         out["visual.positional_embedding"] = resample_host(pos, g).to(dtype=pos.dtype)
+    return out
+
+
+# ---- the text tower's positional table at another context length ----------------------------------------------
+
+MIN_CONTEXT, MAX_CONTEXT = 2, 1024
+DEFAULT_KEEP = 20
+
+
+def check_context_length(T) -> int:
+    """A run length of the text tower: an integer in 2 .. 1024 (SOT and EOT need two rows; the stretch kernels take 1024);
+    ValueError otherwise."""
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)):
+        raise ValueError(f"the context length must be an integer (got {T!r})")
+    T = int(T)
+    if not MIN_CONTEXT <= T <= MAX_CONTEXT:
+        raise ValueError(f"the context length must lie in {MIN_CONTEXT}..{MAX_CONTEXT} (got {T})")
+    return T
+
+
+def text_weights(t_in: int, t_out: int, keep: int = DEFAULT_KEEP) -> np.ndarray:
+    """fp64 [t_out, t_in], the operator that takes a ``t_in``-row text positional table to ``t_out`` rows.
+
+    ``t_out <= t_in``: row j is the unit row e_j (truncation; ``keep`` is ignored).  ``t_out > t_in``, with
+    ``k = min(keep, t_in - 1)``: rows ``j < k`` are e_j (the leading positions are copied); row ``j >= k`` has the source
+    coordinate ``u = k + (j - k) (t_in - k) / (t_out - k)``, ``i0 = floor(u)``, ``w = u - i0`` and carries ``1 - w`` on ``i0``
+    and ``w`` on ``min(i0 + 1, t_in - 1)``.  Every row sums to 1 and has at most two non-zeros.  This definition is the
+    contract: a linear stretch of the rows behind the first ``keep`` (77 -> 248 with keep 20 is exactly 4x)."""
+    t_in, t_out, keep = int(t_in), int(t_out), int(keep)
+    if t_in < 1 or t_out < 1 or keep < 0:
+        raise ValueError(f"lengths must be positive and keep non-negative (got {t_in} -> {t_out}, keep {keep})")
+    w = np.zeros((t_out, t_in), dtype=np.float64)
+    if t_out <= t_in:
+        w[np.arange(t_out), np.arange(t_out)] = 1.0
+        return w
+    k = min(keep, t_in - 1)
+    for j in range(t_out):
+        if j < k:
+            w[j, j] = 1.0
+            continue
+        u = k + (j - k) * (t_in - k) / (t_out - k)
+        i0 = int(np.floor(u))
+        f = u - i0
+        w[j, i0] += 1.0 - f
+        w[j, min(i0 + 1, t_in - 1)] += f
+    return w
+
+
+def stretch_host(pos, t_out: int, keep: int = DEFAULT_KEEP) -> np.ndarray:
+    """``text_weights(t_in, t_out, keep) @ pos`` in fp64 (tensor or array in, fp64 array out), each row formed as its one or
+    two products, rounded separately, and their sum: a fixed arithmetic (a BLAS product may fuse the multiply-adds) that
+    ``ce_pos_stretch_fwd`` repeats on the device, so the device table is the fp32 rounding of this one bit for bit."""
+    p = pos.detach().cpu().double().numpy() if isinstance(pos, torch.Tensor) else np.asarray(pos, dtype=np.float64)
+    i0, w, _ = stretch_tables(p.shape[0], t_out, keep)
+    first = w[:, :1] * p[i0]
+    return np.where(w[:, 1:] == 0.0, first, first + w[:, 1:] * p[np.minimum(i0 + 1, p.shape[0] - 1)])
+
+
+def stretch_tables(t_in: int, t_out: int, keep: int = DEFAULT_KEEP):
+    """The kernels' form of ``text_weights`` (host arrays): ``i0`` int32 [t_out] = each row's first non-zero, ``w`` fp64
+    [t_out, 2] = its weight and the next column's (0 when the row has one non-zero), ``span`` int32 [t_in, 2] = the contiguous
+    range [lo, hi) of run rows with a non-zero in each native column (empty: lo = hi)."""
+    W = text_weights(t_in, t_out, keep)
+    i0 = (W != 0).argmax(axis=1).astype(np.int32)
+    nxt = np.minimum(i0 + 1, t_in - 1)
+    rows = np.arange(t_out)
+    w = np.stack([W[rows, i0], np.where(nxt > i0, W[rows, nxt], 0.0)], axis=1)
+    span = np.zeros((t_in, 2), dtype=np.int32)
+    for i in range(t_in):
+        nz = np.flatnonzero(W[:, i])
+        if nz.size:
+            span[i] = (nz[0], nz[-1] + 1)
+    return i0, w, span
+
+
+_STRETCH = {}
+
+
+def stretch_device_tables(t_in: int, t_out: int, keep: int, device):
+    """``stretch_tables`` on ``device``, cached per (lengths, keep, device)."""
+    key = (int(t_in), int(t_out), int(keep), str(device))
+    t = _STRETCH.get(key)
+    if t is None:
+        t = _STRETCH[key] = tuple(torch.from_numpy(a).to(device) for a in stretch_tables(t_in, t_out, keep))
+    return t
+
+
+def _text_table(t: torch.Tensor, what: str, rows: int = None, like: torch.Tensor = None) -> torch.Tensor:
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or not t.is_cuda:
+        raise ValueError(f"{what} must be a contiguous fp32 matrix on the GPU (got {t.dtype} {tuple(t.shape)} on {t.device})")
+    if like is not None and (tuple(t.shape) != (rows, like.shape[1]) or t.device != like.device):
+        raise ValueError(f"{what} must be [{rows}, {like.shape[1]}] on {like.device} (got {tuple(t.shape)} on {t.device})")
+    return t
+
+
+def _length(t) -> int:
+    t = int(t)
+    if not 1 <= t <= MAX_CONTEXT:
+        raise ValueError(f"a table length must lie in 1..{MAX_CONTEXT} (got {t})")
+    return t
+
+
+def stretch(pos: torch.Tensor, t_out: int, keep: int = DEFAULT_KEEP, out: torch.Tensor = None) -> torch.Tensor:
+    """Device op: ``pos`` fp32 [t_in, D] -> [t_out, D] (``out``, or a new tensor): ``text_weights`` applied in fp64 and rounded to
+    fp32 once, i.e. the fp32 rounding of ``stretch_host``."""
+    t_in, D, t_out = _length(_text_table(pos, "stretch: pos").shape[0]), pos.shape[1], _length(t_out)
+    if out is None:
+        out = torch.empty(t_out, D, dtype=torch.float32, device=pos.device)
+    _text_table(out, "stretch: out", t_out, pos)
+    i0, w, _ = stretch_device_tables(t_in, t_out, keep, pos.device)
+    check(lib().ce_pos_stretch_fwd(ptr(pos), t_in, ptr(i0), ptr(w), ptr(out), t_out, D, stream()), "ce_pos_stretch_fwd")
+    return out
+
+
+def stretch_backward(dout: torch.Tensor, t_in: int, keep: int = DEFAULT_KEEP, accumulate: bool = False,
+                     out: torch.Tensor = None) -> torch.Tensor:
+    """Device op, the transpose: ``dout`` fp32 [t_out, D] -> [t_in, D]; stored into a new tensor, or stored / added
+    (``accumulate``) into ``out``."""
+    t_out, D, t_in = _length(_text_table(dout, "stretch_backward: dout").shape[0]), dout.shape[1], _length(t_in)
+    if out is None:
+        if accumulate:
+            raise ValueError("stretch_backward: accumulate needs the tensor to add to (out=)")
+        out = torch.empty(t_in, D, dtype=torch.float32, device=dout.device)
+    _text_table(out, "stretch_backward: out", t_in, dout)
+    i0, w, span = stretch_device_tables(t_in, t_out, keep, dout.device)
+    check(lib().ce_pos_stretch_bwd(ptr(dout), t_out, ptr(i0), ptr(w), ptr(span), ptr(out), t_in, D, int(bool(accumulate)),
+                                   stream()), "ce_pos_stretch_bwd")
+    return out
+
+
+def resize_text_state_dict(sd: dict, T: int, keep: int = DEFAULT_KEEP) -> dict:
+    """A copy of the state dict ``sd`` whose ``positional_embedding`` has ``T`` rows (``stretch_host`` rounded to the table's
+    dtype): the permanent form -- ``build_model`` of the result is a model that is native at ``T``.  Host only; every other
+    entry is the same object as in ``sd``; at the table's own length so is the table."""
+    T = check_context_length(T)
+    pos = sd["positional_embedding"]
+    out = dict(sd)
+    if pos.shape[0] != T:
+        out["positional_embedding"] = torch.from_numpy(stretch_host(pos, T, keep)).to(dtype=pos.dtype)
     return out

@@ -200,6 +200,19 @@ int ce_attention_bwd(const void* qkv, long ld, const void* o, long ldo, const vo
 int ce_attention_bwd_partials(const void* qkv, long ld, const void* o, long ldo, const void* dout, long lddo,
                               const float* lse, void* dqkv, long lddq, float* partials, const int* cu_seqlens, int B,
                               int L, int H, int causal, void* stream);
+/* Variable-length batches of any length: the signatures of ce_attention_fwd / ce_attention_bwd, cu_seqlens required
+ * (NULL is -EINVAL before any launch), L = the longest sample the launch is sized for, 1 .. 4096.  L <= 128 IS ce_attention_fwd /
+ * ce_attention_bwd (same kernels, same bits).  Longer: the tiled kernels with per-sample lengths -- sample b's own length (at most L)
+ * bounds its key and query blocks, loads, clamps and masks, so no load reaches into the next sample's rows; the grid stays
+ * (blocks of L, B H) and a workgroup whose block starts at or past its sample's length returns at once, an empty sample's
+ * workgroups all do.  lse and the backward's delta scratch stay [B, H, L]; rows past a sample's length are not written.  bias_grad
+ * is accumulated with atomics as in the dense long path.  The profiler scope charges B L^2 as the short packed path does, not the
+ * live sum of squares. */
+int ce_attention_fwd_packed(const void* qkv, long ld, void* o, long ldo, float* lse, const int* cu_seqlens, int B, int L,
+                            int H, int causal, void* stream);
+int ce_attention_bwd_packed(const void* qkv, long ld, const void* o, long ldo, const void* dout, long lddo,
+                            const float* lse, void* dqkv, long lddq, float* bias_grad, const int* cu_seqlens, int B, int L,
+                            int H, int causal, void* stream);
 
 /* ---- input side, bookkeeping (embed.hip) ---- */
 /* image f32 [B,3,R,R] -> patch rows bf16 [B*(R/p)^2, k_padded], columns ordered (c, py, px) like the
@@ -264,6 +277,18 @@ int ce_pos_resample_fwd(const float* pos, int g_in, const float* wy, const float
                         void* stream);
 int ce_pos_resample_bwd(const float* dout, int g_out, const float* wy, const float* wx, float* dpos, int g_in, int D,
                         int accumulate, void* stream);
+/* ---- the text tower's positional table at another context length (posembed.hip) ----
+ * pos [t_in, D] -> out [t_out, D]:  out[j,:] = w[2j] pos[i0[j],:] + w[2j+1] pos[min(i0[j] + 1, t_in - 1),:], the second term skipped
+ * when its weight is zero (a unit row is a bit-exact copy).  i0 int32 [t_out] ascending, w fp64 [t_out][2]: the caller's, device
+ * memory (clip_event_amd/posembed.py text_weights: host arithmetic).  Products and sum are formed in fp64 and rounded to fp32 once,
+ * so out is the fp32 rounding of the host's fp64 W pos -- the table a checkpoint resized on the host carries.  The backward is the
+ * transpose in gather form, no atomics, bit-identical run to run: native row i adds the run rows span[2i] .. span[2i+1] - 1 (int32
+ * [t_in][2], the contiguous range whose i0 is i - 1 or i) in ascending order in fp64, each with the weight it gave row i;
+ * accumulate = 0 stores, 1 adds to the old value before the one rounding.  Indices read from the tables are clamped into the
+ * buffers.  1 <= t_in, t_out <= 1024, D a multiple of 4, 16-byte aligned pos / out / dout / dpos; nothing is allocated. */
+int ce_pos_stretch_fwd(const float* pos, int t_in, const int* i0, const double* w, float* out, int t_out, int D, void* stream);
+int ce_pos_stretch_bwd(const float* dout, int t_out, const int* i0, const double* w, const int* span, float* dpos, int t_in,
+                       int D, int accumulate, void* stream);
 /* out[n] += sum_m x[m,n]  (bias gradients; atomics) */
 int ce_colsum_bf16(const void* x, long ld, float* out, int M, int N, void* stream);
 /* fp32 master weight [R,C] -> bf16 copy [R,C] (nullable) and bf16 transposed copy [C,R] (nullable) */

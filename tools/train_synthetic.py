@@ -43,7 +43,12 @@ read back has them.
 ``--image-size R`` runs and trains the image tower at ``R`` x ``R`` instead of the checkpoint's own resolution (``CLIP.set_image_size``:
 the positional table is resampled, the parameter keeps its shape); ``--image-size-schedule STEP:R ...`` changes the size at the given
 steps (progressive resizing: cheap low-resolution steps first).  The synthetic images, the augmentation and the evaluation pass
-follow the size; the setting is not in the checkpoint, so the resumed run sets it again."""
+follow the size; the setting is not in the checkpoint, so the resumed run sets it again.
+
+``--context-length T`` (``--context-keep K``) runs and trains the text tower on ``T``-token rows instead of the checkpoint's 77
+(``CLIP.set_context_length``: the first K rows of the positional table copied, the rest stretched; the parameter keeps its shape).  The
+captions are tokenised at ``T`` and, beyond 77 tokens, padded out with repeated sentences so that some exceed the 128 tokens of the short
+attention kernels.  Like the image size the setting is not in the checkpoint: the resumed run sets it again."""
 import argparse
 import os
 import sys
@@ -62,12 +67,14 @@ from clip_event_amd.preprocess import Augment, preprocess
 CAPTIONS = list(S.ASCII_CAPTIONS)
 
 
-def batch(rng, B, K, dev, aug=None, draw=0, n_px=224, positives=None):
+def batch(rng, B, K, dev, aug=None, draw=0, n_px=224, positives=None, context=77):
     sizes = [(int(rng.integers(240, 640)), int(rng.integers(240, 640))) for _ in range(B)]
     imgs = [torch.from_numpy(rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)).to(dev) for (w, h) in sizes]
     image = preprocess(imgs, n_px=n_px) if aug is None else aug(imgs, draw=draw)   # clip.py:62-69 / the training transform, on the GPU
     texts = [CAPTIONS[int(rng.integers(len(CAPTIONS)))] + f" number {int(rng.integers(1000))}" for _ in range(B * K)]
-    text = clip.tokenize(texts)                                                 # clip.py:168-201: stays on the HOST, as the reference's loader
+    if context > 77:                                                            # long captions: a third of them several sentences long
+        texts = [t if i % 3 else " ".join([t] * int(rng.integers(2, 2 + context // 16))) for i, t in enumerate(texts)]
+    text = clip.tokenize(texts, context_length=context)                                               # clip.py:168-201: stays on the HOST, as the reference's loader
                                                                                 # yields it -- train_step copies it and keeps the caption lengths
     if positives is None:
         yi, yt, ip = D.global_labels(B, 1, K - 1, True, device=dev)             # dataset_voa.py:605-664
@@ -113,6 +120,8 @@ def main():
     ap.add_argument("--lora-layers", type=int, default=None, metavar="N", help="with --lora: the top N blocks of each tower only")
     ap.add_argument("--image-size", type=int, default=None, metavar="R", help="run the image tower at R x R (CLIP.set_image_size)")
     ap.add_argument("--image-size-schedule", nargs="+", default=(), metavar="STEP:R", help="from step STEP on, run at R x R")
+    ap.add_argument("--context-length", type=int, default=None, metavar="T", help="run the text tower on T-token rows (CLIP.set_context_length)")
+    ap.add_argument("--context-keep", type=int, default=20, metavar="K", help="with --context-length: leading positions copied, not stretched")
     args = ap.parse_args()
     try:
         schedule = sorted((int(a), int(b)) for a, b in (item.split(":") for item in args.image_size_schedule))
@@ -217,12 +226,13 @@ def main():
     lock(model)
     model.set_patch_dropout(args.patch_dropout, seed=0)
     size = model.set_image_size(size_at(0))           # a ValueError names the rule a bad size breaks
+    ctx = model.set_context_length(args.context_length, keep=args.context_keep)      # likewise
     optimizer = make_optimizer(model)
     if args.ema is not None:
         optimizer.enable_ema(args.ema, warmup=args.ema_warmup)
     scheduler = build_lr_scheduler(cfg, optimizer, 0)                           # engine.py:154-176
     aug = aug_at(size)
-    data, decoded = batch(rng, B, K, dev, aug, n_px=size, positives=P)                       # one fixed batch: the loss must fall
+    data, decoded = batch(rng, B, K, dev, aug, n_px=size, positives=P, context=ctx)          # one fixed batch: the loss must fall
     losses = []
     for it in range(20):
         if size_at(it) != size:                                                 # progressive resizing: the same images at the new size
@@ -253,6 +263,8 @@ def main():
         model2.set_patch_dropout(args.patch_dropout, seed=0)
         model2.patch_draw = model.patch_draw
         assert model2.visual.input_resolution == native                                         # nor is the run size
+        assert model2.context_length == model2.native_context_length                           # nor is the run length
+        model2.set_context_length(args.context_length, keep=args.context_keep)
         size = model2.set_image_size(size_at(20))
         if size != model.visual.input_resolution:
             model.set_image_size(size)
@@ -280,14 +292,14 @@ def main():
     la, lb = float(sum(v.detach() for v in a.values())), float(sum(v.detach() for v in b.values()))
     print(f"resumed run continues: loss {la:.5f} vs {lb:.5f}")
     assert abs(la - lb) < 1e-3 * max(1.0, abs(la))
-    new, _ = batch(rng, B, K, dev, aug, 21, n_px=size, positives=P)                          # a fresh ragged batch goes through too
+    new, _ = batch(rng, B, K, dev, aug, 21, n_px=size, positives=P, context=ctx)                          # a fresh ragged batch goes through too
     ld = train_step(model2, criterion, optimizer2, *new, micro_batch=mb)
     scheduler2.step()
     assert all(torch.isfinite(v) for v in ld.values())
     # a longer stretch of fresh batches with no host synchronisation in the loop: host-side caption lengths, the run-ahead
     # limit of engine.train_step, the asynchronous poll of the fp16-stream clamp counters (every 16 optimiser steps)
     import time
-    batches = [batch(rng, 32, K, dev, aug, 22 + i, n_px=size, positives=P)[0] for i in range(8)]
+    batches = [batch(rng, 32, K, dev, aug, 22 + i, n_px=size, positives=P, context=ctx)[0] for i in range(8)]
     for it in range(4):                                                         # new batch size: workspaces are allocated here
         train_step(model2, criterion, optimizer2, *batches[it], micro_batch=mb)
     torch.cuda.synchronize()
@@ -298,7 +310,7 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / 96
     assert all(torch.isfinite(v) for v in ld.values()) and model2.stream16_saturation() == (0, 0)
-    print(f"96 steps at B = 32, K = {K}, {size} px: {dt * 1e3:.2f} ms/step, clamp counters {model2.stream16_saturation()}")
+    print(f"96 steps at B = 32, K = {K}, {size} px, {ctx} tokens: {dt * 1e3:.2f} ms/step, clamp counters {model2.stream16_saturation()}")
     if args.ema is not None:
         image, text, _, _, ip = data
 
