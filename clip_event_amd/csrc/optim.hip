@@ -7,6 +7,8 @@
 // max_norm / (norm + 1e-6) (clamped to 1) on the fly.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.hpp"
 #include "../../include/clip_event_hip.h"
 
@@ -594,10 +596,6 @@ int sgd_check(const char* who, const float* buf, float momentum, float dampening
 float adam_bc1(float beta1, int step) { return (float)(1.0 - pow((double)beta1, (double)step)); }
 float adam_bc2_sqrt(float beta2, int step) { return (float)sqrt(1.0 - pow((double)beta2, (double)step)); }
 
-AdamRule::Args adam_args(const float* sumsq, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step) {
-    return {sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, adam_bc1(beta1, step), adam_bc2_sqrt(beta2, step)};
-}
-
 // the by-value group table of a grouped launch; 0 or -EINVAL with a message
 int fill_groups(const char* who, group_table& t, const ce_optim_group* groups, int ngroups, const int* segment_group, bool decoupled_ok) {
     CE_CHECK_ARG(groups && ngroups >= 1 && ngroups <= kMaxGroups, "%s: need 1..%d groups (got %d, table %s)", who, kMaxGroups, ngroups,
@@ -610,47 +608,10 @@ int fill_groups(const char* who, group_table& t, const ce_optim_group* groups, i
     return 0;
 }
 
-// ---- launchers: one per form, for every rule (arguments are checked by the callers) ------------------------------------------------
 unsigned flat_blocks(long n) {
     static const long cap = getenv("CE_ADAM_BLOCKS") ? atol(getenv("CE_ADAM_BLOCKS")) : 4096;
     const long blocks = (n + 2047) / 2048;
     return (unsigned)(blocks > cap ? cap : blocks);
-}
-// `ema` (every launcher): NULL = the step as it is without a weight average (the kernels' EMA = false instantiations, which never name
-// the pointer); otherwise the EMA instantiation of the same kernels
-template <class Rule>
-void launch_flat(float* p, const float* g, float* s0, float* s1, void* p_bf16, long n, const typename Rule::Args& a, void* stream,
-                 float* ema = nullptr, float ema_rate = 0.f) {
-    if (ema)
-        hipLaunchKernelGGL((optim_flat_kernel<Rule, true>), dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, s0, s1,
-                           (bf16_t*)p_bf16, n, a, ema, ema_rate);
-    else
-        hipLaunchKernelGGL((optim_flat_kernel<Rule, false>), dim3(flat_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, s0, s1,
-                           (bf16_t*)p_bf16, n, a, ema, 0.f);
-}
-
-// the matrices of the job table in tiles, then the [lo, hi) table in segments; either table may be empty
-template <class Rule>
-void launch_tiles(float* p, const float* g, float* s0, float* s1, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
-                  int total_tiles, const long* segments_device, int nsegments, const typename Rule::Args& a, void* stream,
-                  float* ema = nullptr, float ema_rate = 0.f) {
-    const hipStream_t s = (hipStream_t)stream;
-    if (jobs_device && njobs > 0 && total_tiles > 0) {
-        if (ema)
-            hipLaunchKernelGGL((optim_tiles_kernel<Rule, true>), dim3((unsigned)total_tiles), dim3(256), 0, s, p, g, s0, s1,
-                               (bf16_t*)p_bf16, jobs_device, njobs, a, ema, ema_rate);
-        else
-            hipLaunchKernelGGL((optim_tiles_kernel<Rule, false>), dim3((unsigned)total_tiles), dim3(256), 0, s, p, g, s0, s1,
-                               (bf16_t*)p_bf16, jobs_device, njobs, a, ema, 0.f);
-    }
-    if (segments_device && nsegments > 0) {
-        if (ema)
-            hipLaunchKernelGGL((optim_segments_kernel<Rule, true>), dim3((unsigned)nsegments), dim3(256), 0, s, p, g, s0, s1,
-                               (bf16_t*)p_bf16, segments_device, a, ema, ema_rate);
-        else
-            hipLaunchKernelGGL((optim_segments_kernel<Rule, false>), dim3((unsigned)nsegments), dim3(256), 0, s, p, g, s0, s1,
-                               (bf16_t*)p_bf16, segments_device, a, ema, 0.f);
-    }
 }
 
 // what every _ema entry point asks of its two extra arguments; 0 or -EINVAL with a message
@@ -685,95 +646,137 @@ extern "C" int ce_sumsq(const float* g, long n, float* out, void* stream) {
     return 0;
 }
 
+extern "C" int ce_sumsq_segments(const float* g, const long* table_device, int nchunks, float* out, void* stream) {
+    CE_CHECK_ARG(g && table_device && out && nchunks > 0, "ce_sumsq_segments: empty");
+    hipLaunchKernelGGL(sumsq_segments_kernel, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, g, table_device, out);
+    CE_LAUNCH_CHECK();
+    return 0;
+}
 
-// ---- the step entry points: each form once, for the plain entry point (ema NULL) and its _ema twin ------------------------------
+// ---- the optimiser step: entry point -> the rule's host part -> run_step -----------------------------------------------------------
+// An entry point (extern "C", at the end) only fills a StepCall from its arguments.  The host part of its rule (run_adam, run_sgd,
+// run_lion and their grouped forms) checks the rule's scalars and builds Rule::Args.  run_step checks what no rule decides and
+// launches.  That is also the order of the checks, which decides the message when several arguments are bad at once:
+//   1. the rule's own -- Adam: step >= 1; SGD: sgd_check (momentum, nesterov, a momentum buffer when momentum > 0); Lion: lion_check
+//      (m, the betas), then lr / weight decay; the grouped forms then the group table (fill_groups; Lion: every group's lr / weight decay)
+//   2. the form: n > 0 (flat), or a table with something in it (tiles / groups)
+//   3. the buffers: p and g, every state stream the rule has (Rule::NS), and in the table forms p_bf16, which the tiles are located
+//      in; the flat form takes p_bf16 == NULL (no mirror is written)
+//   4. the weight average (ema_check), when the _ema twin was called
 namespace {
 
-int adam_step(const char* who, float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* sumsq, float max_norm,
-              float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* ema, float ema_rate, void* stream) {
-    CE_CHECK_ARG(n > 0 && step >= 1, "%s: need n>0 and step>=1", who);
-    launch_flat<AdamRule>(p, g, m, v, p_bf16, n, adam_args(sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step), stream, ema,
-                          ema_rate);
+struct StepCall {
+    const char* who;                  // the entry point that was called: every message starts with it
+    float* p;
+    const float* g;
+    float* state[2];                  // Adam: m, v; SGD: buf; Lion: m.  Only the first Rule::NS reach a kernel
+    void* p_bf16;
+    const float* sumsq;
+    float max_norm;
+    void* stream;
+    bool flat = false;                // [0, n); otherwise the table forms: `jobs` in tiles, then `segments`
+    long n = 0;
+    const ce_transpose_job* jobs = nullptr;
+    int njobs = 0, total_tiles = 0;
+    const long* segments = nullptr;
+    int nsegments = 0;
+    const int* segment_group = nullptr;      // the grouped forms (what fill_groups reads)
+    const ce_optim_group* groups = nullptr;
+    int ngroups = 0;
+    bool with_ema = false;            // the _ema twin was called
+    float* ema = nullptr;
+    float ema_rate = 0.f;
+};
+
+StepCall flat_call(const char* who, float* p, const float* g, float* s0, float* s1, void* p_bf16, long n, const float* sumsq,
+                   float max_norm, void* stream) {
+    StepCall c = {who, p, g, {s0, s1}, p_bf16, sumsq, max_norm, stream};
+    c.flat = true, c.n = n;
+    return c;
+}
+StepCall table_call(const char* who, float* p, const float* g, float* s0, float* s1, void* p_bf16, const ce_transpose_job* jobs,
+                    int njobs, int total_tiles, const long* segments, int nsegments, const float* sumsq, float max_norm, void* stream) {
+    StepCall c = {who, p, g, {s0, s1}, p_bf16, sumsq, max_norm, stream};
+    c.jobs = jobs, c.njobs = njobs, c.total_tiles = total_tiles, c.segments = segments, c.nsegments = nsegments;
+    return c;
+}
+StepCall with_groups(StepCall c, const int* segment_group, const ce_optim_group* groups, int ngroups) {
+    c.segment_group = segment_group, c.groups = groups, c.ngroups = ngroups;
+    return c;
+}
+StepCall with_ema(StepCall c, float* ema, float ema_rate) {
+    c.with_ema = true, c.ema = ema, c.ema_rate = ema_rate;
+    return c;
+}
+
+// f(std::true_type) or f(std::false_type): the one place where the EMA instantiation of a traversal is chosen
+template <class F>
+void pick_ema(bool on, F&& f) {
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+template <class Rule>
+int run_step(const StepCall& c, const typename Rule::Args& a) {
+    const bool tiles = c.jobs && c.njobs > 0 && c.total_tiles > 0, segments = c.segments && c.nsegments > 0;      // either table may be empty
+    if (c.flat) CE_CHECK_ARG(c.n > 0, "%s: need n>0", c.who);
+    else CE_CHECK_ARG(tiles || segments, "%s: nothing to update", c.who);
+    bool buffers = c.p && c.g && (c.flat || c.p_bf16);
+    for (int k = 0; k < Rule::NS; ++k) buffers = buffers && c.state[k];
+    CE_CHECK_ARG(buffers, "%s: null buffer", c.who);
+    if (c.with_ema)
+        if (int rc = ema_check(c.who, c.ema, c.ema_rate)) return rc;
+    float* const s0 = Rule::NS > 0 ? c.state[0] : nullptr;
+    float* const s1 = Rule::NS > 1 ? c.state[1] : nullptr;
+    bf16_t* const p16 = (bf16_t*)c.p_bf16;
+    const hipStream_t s = (hipStream_t)c.stream;
+    pick_ema(c.with_ema, [&](auto on) {
+        // without the average the kernels never name the pointer: NULL and rate 0
+        constexpr bool EMA = decltype(on)::value;
+        float* const ema = EMA ? c.ema : nullptr;
+        const float ema_rate = EMA ? c.ema_rate : 0.f;
+        if constexpr (!Rule::GROUPED) {      // (no entry point is flat and grouped: those kernels are not instantiated)
+            if (c.flat)
+                hipLaunchKernelGGL((optim_flat_kernel<Rule, EMA>), dim3(flat_blocks(c.n)), dim3(256), 0, s, c.p, c.g, s0, s1, p16, c.n, a,
+                                   ema, ema_rate);
+        }
+        if (!c.flat && tiles)
+            hipLaunchKernelGGL((optim_tiles_kernel<Rule, EMA>), dim3((unsigned)c.total_tiles), dim3(256), 0, s, c.p, c.g, s0, s1, p16,
+                               c.jobs, c.njobs, a, ema, ema_rate);
+        if (!c.flat && segments)
+            hipLaunchKernelGGL((optim_segments_kernel<Rule, EMA>), dim3((unsigned)c.nsegments), dim3(256), 0, s, c.p, c.g, s0, s1, p16,
+                               c.segments, a, ema, ema_rate);
+    });
     CE_LAUNCH_CHECK();
     return 0;
 }
 
-int adam_step_tiles(const char* who, float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
-                    int njobs, int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
-                    float beta1, float beta2, float eps, float weight_decay, int step, float* ema, float ema_rate, void* stream) {
-    CE_CHECK_ARG(p && g && m && v && p_bf16 && step >= 1, "%s: null buffer or step < 1", who);
-    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
-    launch_tiles<AdamRule>(p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
-                           adam_args(sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step), stream, ema, ema_rate);
-    CE_LAUNCH_CHECK();
-    return 0;
+int run_adam(const StepCall& c, float lr, float beta1, float beta2, float eps, float weight_decay, int step) {
+    CE_CHECK_ARG(step >= 1, "%s: need step>=1", c.who);
+    return run_step<AdamRule>(c, {c.sumsq, c.max_norm, lr, beta1, beta2, eps, weight_decay, adam_bc1(beta1, step), adam_bc2_sqrt(beta2, step)});
+}
+int run_adam_groups(const StepCall& c, float beta1, float beta2, float eps, int step) {
+    CE_CHECK_ARG(step >= 1, "%s: need step>=1", c.who);
+    AdamGroupRule::Args a = {c.sumsq, c.max_norm, beta1, beta2, eps, adam_bc1(beta1, step), adam_bc2_sqrt(beta2, step), {}};
+    if (int rc = fill_groups(c.who, a.groups, c.groups, c.ngroups, c.segment_group, true)) return rc;
+    return run_step<AdamGroupRule>(c, a);
 }
 
-int sgd_step(const char* who, float* p, const float* g, float* buf, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
-             float momentum, float dampening, float weight_decay, int nesterov, int first_step, float* ema, float ema_rate,
-             void* stream) {
-    CE_CHECK_ARG(n > 0, "%s: need n>0", who);
-    if (int rc = sgd_check(who, buf, momentum, dampening, nesterov)) return rc;
-    CE_CHECK_ARG(p && g, "%s: null buffer", who);
-    const sgd_args a = {sumsq, max_norm, lr, momentum, 1.0f - dampening, weight_decay, first_step != 0, nesterov != 0};
-    if (momentum > 0.f) launch_flat<SgdRule<true>>(p, g, buf, nullptr, p_bf16, n, a, stream, ema, ema_rate);
-    else launch_flat<SgdRule<false>>(p, g, nullptr, nullptr, p_bf16, n, a, stream, ema, ema_rate);
-    CE_LAUNCH_CHECK();
-    return 0;
+// SGD: momentum 0 is the instantiation without a momentum stream (`buf` is then not looked at, NULL or not)
+int run_sgd(const StepCall& c, float lr, float momentum, float dampening, float weight_decay, int nesterov, int first_step) {
+    if (int rc = sgd_check(c.who, c.state[0], momentum, dampening, nesterov)) return rc;
+    const sgd_args a = {c.sumsq, c.max_norm, lr, momentum, 1.0f - dampening, weight_decay, first_step != 0, nesterov != 0};
+    return momentum > 0.f ? run_step<SgdRule<true>>(c, a) : run_step<SgdRule<false>>(c, a);
 }
-
-int sgd_step_tiles(const char* who, float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
-                   int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
-                   float momentum, float dampening, float weight_decay, int nesterov, int first_step, float* ema, float ema_rate,
-                   void* stream) {
-    if (int rc = sgd_check(who, buf, momentum, dampening, nesterov)) return rc;
-    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
-    CE_CHECK_ARG(p && g && p_bf16, "%s: null buffer", who);
-    const sgd_args a = {sumsq, max_norm, lr, momentum, 1.0f - dampening, weight_decay, first_step != 0, nesterov != 0};
-    if (momentum > 0.f)
-        launch_tiles<SgdRule<true>>(p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream,
-                                    ema, ema_rate);
-    else
-        launch_tiles<SgdRule<false>>(p, g, nullptr, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a,
-                                     stream, ema, ema_rate);
-    CE_LAUNCH_CHECK();
-    return 0;
-}
-
-int adam_step_groups(const char* who, float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
-                     int njobs, int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
-                     const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float beta1, float beta2, float eps,
-                     int step, float* ema, float ema_rate, void* stream) {
-    CE_CHECK_ARG(p && g && m && v && p_bf16 && step >= 1, "%s: null buffer or step < 1", who);
-    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
-    AdamGroupRule::Args a = {sumsq, max_norm, beta1, beta2, eps, adam_bc1(beta1, step), adam_bc2_sqrt(beta2, step), {}};
-    if (int rc = fill_groups(who, a.groups, groups, ngroups, segment_group, true)) return rc;
-    launch_tiles<AdamGroupRule>(p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream, ema, ema_rate);
-    CE_LAUNCH_CHECK();
-    return 0;
-}
-
-int sgd_step_groups(const char* who, float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
-                    int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
-                    float max_norm, const ce_optim_group* groups, int ngroups, float momentum, float dampening, int nesterov,
-                    int first_step, float* ema, float ema_rate, void* stream) {
-    if (int rc = sgd_check(who, buf, momentum, dampening, nesterov)) return rc;
-    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
-    CE_CHECK_ARG(p && g && p_bf16, "%s: null buffer", who);
-    sgd_group_args a = {sumsq, max_norm, momentum, 1.0f - dampening, first_step != 0, nesterov != 0, {}};
-    if (int rc = fill_groups(who, a.groups, groups, ngroups, segment_group, false)) return rc;
-    if (momentum > 0.f)
-        launch_tiles<SgdGroupRule<true>>(p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a,
-                                         stream, ema, ema_rate);
-    else
-        launch_tiles<SgdGroupRule<false>>(p, g, nullptr, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
-                                          a, stream, ema, ema_rate);
-    CE_LAUNCH_CHECK();
-    return 0;
+int run_sgd_groups(const StepCall& c, float momentum, float dampening, int nesterov, int first_step) {
+    if (int rc = sgd_check(c.who, c.state[0], momentum, dampening, nesterov)) return rc;
+    sgd_group_args a = {c.sumsq, c.max_norm, momentum, 1.0f - dampening, first_step != 0, nesterov != 0, {}};
+    if (int rc = fill_groups(c.who, a.groups, c.groups, c.ngroups, c.segment_group, false)) return rc;
+    return momentum > 0.f ? run_step<SgdGroupRule<true>>(c, a) : run_step<SgdGroupRule<false>>(c, a);
 }
 
 // what every Lion entry point asks of its momentum and its hyper-parameters (the grouped forms: of every group's lr / weight decay,
-// checked by lion_groups_check); 0 or -EINVAL with a message
+// checked in run_lion_groups); 0 or -EINVAL with a message
 int lion_check(const char* who, const float* m, float beta1, float beta2) {
     CE_CHECK_ARG(m, "%s: the momentum buffer m is NULL", who);
     CE_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f, "%s: invalid beta1 value %g (outside [0, 1))", who, (double)beta1);
@@ -785,191 +788,153 @@ int lion_scalars_check(const char* who, float lr, float weight_decay) {
     CE_CHECK_ARG(weight_decay >= 0.f, "%s: invalid weight_decay value %g", who, (double)weight_decay);
     return 0;
 }
-
-int lion_step(const char* who, float* p, const float* g, float* m, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
-              float beta1, float beta2, float weight_decay, float* ema, float ema_rate, void* stream) {
-    CE_CHECK_ARG(n > 0, "%s: need n>0", who);
-    if (int rc = lion_check(who, m, beta1, beta2)) return rc;
-    if (int rc = lion_scalars_check(who, lr, weight_decay)) return rc;
-    CE_CHECK_ARG(p && g, "%s: null buffer", who);
-    const LionRule::Args a = {sumsq, max_norm, lr, beta1, beta2, weight_decay};
-    launch_flat<LionRule>(p, g, m, nullptr, p_bf16, n, a, stream, ema, ema_rate);
-    CE_LAUNCH_CHECK();
-    return 0;
+int run_lion(const StepCall& c, float lr, float beta1, float beta2, float weight_decay) {
+    if (int rc = lion_check(c.who, c.state[0], beta1, beta2)) return rc;
+    if (int rc = lion_scalars_check(c.who, lr, weight_decay)) return rc;
+    return run_step<LionRule>(c, {c.sumsq, c.max_norm, lr, beta1, beta2, weight_decay});
 }
-
-int lion_step_tiles(const char* who, float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
-                    int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm, float lr,
-                    float beta1, float beta2, float weight_decay, float* ema, float ema_rate, void* stream) {
-    if (int rc = lion_check(who, m, beta1, beta2)) return rc;
-    if (int rc = lion_scalars_check(who, lr, weight_decay)) return rc;
-    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
-    CE_CHECK_ARG(p && g && p_bf16, "%s: null buffer", who);
-    const LionRule::Args a = {sumsq, max_norm, lr, beta1, beta2, weight_decay};
-    launch_tiles<LionRule>(p, g, m, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream, ema,
-                           ema_rate);
-    CE_LAUNCH_CHECK();
-    return 0;
-}
-
-int lion_step_groups(const char* who, float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
-                     int total_tiles, const long* segments_device, int nsegments, const int* segment_group, const float* sumsq,
-                     float max_norm, const ce_optim_group* groups, int ngroups, float beta1, float beta2, float* ema, float ema_rate,
-                     void* stream) {
-    if (int rc = lion_check(who, m, beta1, beta2)) return rc;
-    CE_CHECK_ARG((jobs_device && njobs > 0 && total_tiles > 0) || (segments_device && nsegments > 0), "%s: nothing to update", who);
-    CE_CHECK_ARG(p && g && p_bf16, "%s: null buffer", who);
-    LionGroupRule::Args a = {sumsq, max_norm, beta1, beta2, {}};
-    if (int rc = fill_groups(who, a.groups, groups, ngroups, segment_group, true)) return rc;      // (`decoupled` is not read)
-    for (int i = 0; i < ngroups; ++i)
-        if (int rc = lion_scalars_check(who, groups[i].lr, groups[i].weight_decay)) return rc;
-    launch_tiles<LionGroupRule>(p, g, m, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, a, stream, ema,
-                                ema_rate);
-    CE_LAUNCH_CHECK();
-    return 0;
+int run_lion_groups(const StepCall& c, float beta1, float beta2) {
+    if (int rc = lion_check(c.who, c.state[0], beta1, beta2)) return rc;
+    LionGroupRule::Args a = {c.sumsq, c.max_norm, beta1, beta2, {}};
+    if (int rc = fill_groups(c.who, a.groups, c.groups, c.ngroups, c.segment_group, true)) return rc;      // (`decoupled` is not read)
+    for (int i = 0; i < c.ngroups; ++i)
+        if (int rc = lion_scalars_check(c.who, c.groups[i].lr, c.groups[i].weight_decay)) return rc;
+    return run_step<LionGroupRule>(c, a);
 }
 
 }  // namespace
 
+// ---- the eighteen entry points: flat, tiles and groups for each rule, each with its _ema twin ----------------------------------------
 extern "C" int ce_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* sumsq,
                             float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                             void* stream) {
-    return adam_step("ce_adam_step", p, g, m, v, p_bf16, n, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step, nullptr, 0.f,
-                     stream);
+    const StepCall c = flat_call("ce_adam_step", p, g, m, v, p_bf16, n, sumsq, max_norm, stream);
+    return run_adam(c, lr, beta1, beta2, eps, weight_decay, step);
 }
 extern "C" int ce_adam_step_ema(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* sumsq,
                                 float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                 float* ema, float ema_rate, void* stream) {
-    if (int rc = ema_check("ce_adam_step_ema", ema, ema_rate)) return rc;
-    return adam_step("ce_adam_step_ema", p, g, m, v, p_bf16, n, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step, ema,
-                     ema_rate, stream);
+    const StepCall c = flat_call("ce_adam_step_ema", p, g, m, v, p_bf16, n, sumsq, max_norm, stream);
+    return run_adam(with_ema(c, ema, ema_rate), lr, beta1, beta2, eps, weight_decay, step);
 }
-
 extern "C" int ce_adam_step_tiles(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
                                   int njobs, int total_tiles, const long* segments_device, int nsegments, const float* sumsq,
                                   float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                   void* stream) {
-    return adam_step_tiles("ce_adam_step_tiles", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, sumsq,
-                           max_norm, lr, beta1, beta2, eps, weight_decay, step, nullptr, 0.f, stream);
+    const StepCall c = table_call("ce_adam_step_tiles", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                                  sumsq, max_norm, stream);
+    return run_adam(c, lr, beta1, beta2, eps, weight_decay, step);
 }
 extern "C" int ce_adam_step_tiles_ema(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
                                       int njobs, int total_tiles, const long* segments_device, int nsegments, const float* sumsq,
                                       float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                       float* ema, float ema_rate, void* stream) {
-    if (int rc = ema_check("ce_adam_step_tiles_ema", ema, ema_rate)) return rc;
-    return adam_step_tiles("ce_adam_step_tiles_ema", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
-                           sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step, ema, ema_rate, stream);
+    const StepCall c = table_call("ce_adam_step_tiles_ema", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                                  sumsq, max_norm, stream);
+    return run_adam(with_ema(c, ema, ema_rate), lr, beta1, beta2, eps, weight_decay, step);
 }
-
-extern "C" int ce_sgd_step(float* p, const float* g, float* buf, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
-                           float momentum, float dampening, float weight_decay, int nesterov, int first_step, void* stream) {
-    return sgd_step("ce_sgd_step", p, g, buf, p_bf16, n, sumsq, max_norm, lr, momentum, dampening, weight_decay, nesterov, first_step,
-                    nullptr, 0.f, stream);
-}
-extern "C" int ce_sgd_step_ema(float* p, const float* g, float* buf, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
-                               float momentum, float dampening, float weight_decay, int nesterov, int first_step, float* ema,
-                               float ema_rate, void* stream) {
-    if (int rc = ema_check("ce_sgd_step_ema", ema, ema_rate)) return rc;
-    return sgd_step("ce_sgd_step_ema", p, g, buf, p_bf16, n, sumsq, max_norm, lr, momentum, dampening, weight_decay, nesterov,
-                    first_step, ema, ema_rate, stream);
-}
-
-extern "C" int ce_sgd_step_tiles(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
-                                 int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm,
-                                 float lr, float momentum, float dampening, float weight_decay, int nesterov, int first_step,
-                                 void* stream) {
-    return sgd_step_tiles("ce_sgd_step_tiles", p, g, buf, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, sumsq,
-                          max_norm, lr, momentum, dampening, weight_decay, nesterov, first_step, nullptr, 0.f, stream);
-}
-extern "C" int ce_sgd_step_tiles_ema(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
-                                     int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm,
-                                     float lr, float momentum, float dampening, float weight_decay, int nesterov, int first_step,
-                                     float* ema, float ema_rate, void* stream) {
-    if (int rc = ema_check("ce_sgd_step_tiles_ema", ema, ema_rate)) return rc;
-    return sgd_step_tiles("ce_sgd_step_tiles_ema", p, g, buf, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, sumsq,
-                          max_norm, lr, momentum, dampening, weight_decay, nesterov, first_step, ema, ema_rate, stream);
-}
-
-extern "C" int ce_sumsq_segments(const float* g, const long* table_device, int nchunks, float* out, void* stream) {
-    CE_CHECK_ARG(g && table_device && out && nchunks > 0, "ce_sumsq_segments: empty");
-    hipLaunchKernelGGL(sumsq_segments_kernel, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, g, table_device, out);
-    CE_LAUNCH_CHECK();
-    return 0;
-}
-
 extern "C" int ce_adam_step_groups(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
                                    int njobs, int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
                                    const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float beta1,
                                    float beta2, float eps, int step, void* stream) {
-    return adam_step_groups("ce_adam_step_groups", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
-                            segment_group, sumsq, max_norm, groups, ngroups, beta1, beta2, eps, step, nullptr, 0.f, stream);
+    const StepCall c = table_call("ce_adam_step_groups", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
+                                  sumsq, max_norm, stream);
+    return run_adam_groups(with_groups(c, segment_group, groups, ngroups), beta1, beta2, eps, step);
 }
 extern "C" int ce_adam_step_groups_ema(float* p, const float* g, float* m, float* v, void* p_bf16, const ce_transpose_job* jobs_device,
                                        int njobs, int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
                                        const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float beta1,
                                        float beta2, float eps, int step, float* ema, float ema_rate, void* stream) {
-    if (int rc = ema_check("ce_adam_step_groups_ema", ema, ema_rate)) return rc;
-    return adam_step_groups("ce_adam_step_groups_ema", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
-                            segment_group, sumsq, max_norm, groups, ngroups, beta1, beta2, eps, step, ema, ema_rate, stream);
+    const StepCall c = table_call("ce_adam_step_groups_ema", p, g, m, v, p_bf16, jobs_device, njobs, total_tiles, segments_device,
+                                  nsegments, sumsq, max_norm, stream);
+    return run_adam_groups(with_ema(with_groups(c, segment_group, groups, ngroups), ema, ema_rate), beta1, beta2, eps, step);
 }
 
+extern "C" int ce_sgd_step(float* p, const float* g, float* buf, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+                           float momentum, float dampening, float weight_decay, int nesterov, int first_step, void* stream) {
+    const StepCall c = flat_call("ce_sgd_step", p, g, buf, nullptr, p_bf16, n, sumsq, max_norm, stream);
+    return run_sgd(c, lr, momentum, dampening, weight_decay, nesterov, first_step);
+}
+extern "C" int ce_sgd_step_ema(float* p, const float* g, float* buf, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
+                               float momentum, float dampening, float weight_decay, int nesterov, int first_step, float* ema,
+                               float ema_rate, void* stream) {
+    const StepCall c = flat_call("ce_sgd_step_ema", p, g, buf, nullptr, p_bf16, n, sumsq, max_norm, stream);
+    return run_sgd(with_ema(c, ema, ema_rate), lr, momentum, dampening, weight_decay, nesterov, first_step);
+}
+extern "C" int ce_sgd_step_tiles(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                                 int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm,
+                                 float lr, float momentum, float dampening, float weight_decay, int nesterov, int first_step,
+                                 void* stream) {
+    const StepCall c = table_call("ce_sgd_step_tiles", p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device,
+                                  nsegments, sumsq, max_norm, stream);
+    return run_sgd(c, lr, momentum, dampening, weight_decay, nesterov, first_step);
+}
+extern "C" int ce_sgd_step_tiles_ema(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
+                                     int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm,
+                                     float lr, float momentum, float dampening, float weight_decay, int nesterov, int first_step,
+                                     float* ema, float ema_rate, void* stream) {
+    const StepCall c = table_call("ce_sgd_step_tiles_ema", p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device,
+                                  nsegments, sumsq, max_norm, stream);
+    return run_sgd(with_ema(c, ema, ema_rate), lr, momentum, dampening, weight_decay, nesterov, first_step);
+}
 extern "C" int ce_sgd_step_groups(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
                                   int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
                                   const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float momentum,
                                   float dampening, int nesterov, int first_step, void* stream) {
-    return sgd_step_groups("ce_sgd_step_groups", p, g, buf, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
-                           segment_group, sumsq, max_norm, groups, ngroups, momentum, dampening, nesterov, first_step, nullptr, 0.f,
-                           stream);
+    const StepCall c = table_call("ce_sgd_step_groups", p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device,
+                                  nsegments, sumsq, max_norm, stream);
+    return run_sgd_groups(with_groups(c, segment_group, groups, ngroups), momentum, dampening, nesterov, first_step);
 }
 extern "C" int ce_sgd_step_groups_ema(float* p, const float* g, float* buf, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
                                       int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
                                       const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float momentum,
                                       float dampening, int nesterov, int first_step, float* ema, float ema_rate, void* stream) {
-    if (int rc = ema_check("ce_sgd_step_groups_ema", ema, ema_rate)) return rc;
-    return sgd_step_groups("ce_sgd_step_groups_ema", p, g, buf, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
-                           segment_group, sumsq, max_norm, groups, ngroups, momentum, dampening, nesterov, first_step, ema, ema_rate,
-                           stream);
+    const StepCall c = table_call("ce_sgd_step_groups_ema", p, g, buf, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device,
+                                  nsegments, sumsq, max_norm, stream);
+    return run_sgd_groups(with_ema(with_groups(c, segment_group, groups, ngroups), ema, ema_rate), momentum, dampening, nesterov,
+                          first_step);
 }
 
 extern "C" int ce_lion_step(float* p, const float* g, float* m, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
                             float beta1, float beta2, float weight_decay, void* stream) {
-    return lion_step("ce_lion_step", p, g, m, p_bf16, n, sumsq, max_norm, lr, beta1, beta2, weight_decay, nullptr, 0.f, stream);
+    const StepCall c = flat_call("ce_lion_step", p, g, m, nullptr, p_bf16, n, sumsq, max_norm, stream);
+    return run_lion(c, lr, beta1, beta2, weight_decay);
 }
 extern "C" int ce_lion_step_ema(float* p, const float* g, float* m, void* p_bf16, long n, const float* sumsq, float max_norm, float lr,
                                 float beta1, float beta2, float weight_decay, float* ema, float ema_rate, void* stream) {
-    if (int rc = ema_check("ce_lion_step_ema", ema, ema_rate)) return rc;
-    return lion_step("ce_lion_step_ema", p, g, m, p_bf16, n, sumsq, max_norm, lr, beta1, beta2, weight_decay, ema, ema_rate, stream);
+    const StepCall c = flat_call("ce_lion_step_ema", p, g, m, nullptr, p_bf16, n, sumsq, max_norm, stream);
+    return run_lion(with_ema(c, ema, ema_rate), lr, beta1, beta2, weight_decay);
 }
-
 extern "C" int ce_lion_step_tiles(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
                                   int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm,
                                   float lr, float beta1, float beta2, float weight_decay, void* stream) {
-    return lion_step_tiles("ce_lion_step_tiles", p, g, m, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments, sumsq,
-                           max_norm, lr, beta1, beta2, weight_decay, nullptr, 0.f, stream);
+    const StepCall c = table_call("ce_lion_step_tiles", p, g, m, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device,
+                                  nsegments, sumsq, max_norm, stream);
+    return run_lion(c, lr, beta1, beta2, weight_decay);
 }
 extern "C" int ce_lion_step_tiles_ema(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
                                       int total_tiles, const long* segments_device, int nsegments, const float* sumsq, float max_norm,
                                       float lr, float beta1, float beta2, float weight_decay, float* ema, float ema_rate,
                                       void* stream) {
-    if (int rc = ema_check("ce_lion_step_tiles_ema", ema, ema_rate)) return rc;
-    return lion_step_tiles("ce_lion_step_tiles_ema", p, g, m, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
-                           sumsq, max_norm, lr, beta1, beta2, weight_decay, ema, ema_rate, stream);
+    const StepCall c = table_call("ce_lion_step_tiles_ema", p, g, m, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device,
+                                  nsegments, sumsq, max_norm, stream);
+    return run_lion(with_ema(c, ema, ema_rate), lr, beta1, beta2, weight_decay);
 }
-
 extern "C" int ce_lion_step_groups(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
                                    int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
                                    const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float beta1,
                                    float beta2, void* stream) {
-    return lion_step_groups("ce_lion_step_groups", p, g, m, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
-                            segment_group, sumsq, max_norm, groups, ngroups, beta1, beta2, nullptr, 0.f, stream);
+    const StepCall c = table_call("ce_lion_step_groups", p, g, m, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device,
+                                  nsegments, sumsq, max_norm, stream);
+    return run_lion_groups(with_groups(c, segment_group, groups, ngroups), beta1, beta2);
 }
 extern "C" int ce_lion_step_groups_ema(float* p, const float* g, float* m, void* p_bf16, const ce_transpose_job* jobs_device, int njobs,
                                        int total_tiles, const long* segments_device, int nsegments, const int* segment_group,
                                        const float* sumsq, float max_norm, const ce_optim_group* groups, int ngroups, float beta1,
                                        float beta2, float* ema, float ema_rate, void* stream) {
-    if (int rc = ema_check("ce_lion_step_groups_ema", ema, ema_rate)) return rc;
-    return lion_step_groups("ce_lion_step_groups_ema", p, g, m, p_bf16, jobs_device, njobs, total_tiles, segments_device, nsegments,
-                            segment_group, sumsq, max_norm, groups, ngroups, beta1, beta2, ema, ema_rate, stream);
+    const StepCall c = table_call("ce_lion_step_groups_ema", p, g, m, nullptr, p_bf16, jobs_device, njobs, total_tiles, segments_device,
+                                  nsegments, sumsq, max_norm, stream);
+    return run_lion_groups(with_ema(with_groups(c, segment_group, groups, ngroups), ema, ema_rate), beta1, beta2);
 }
 
 extern "C" int ce_swap_cast_bf16(float* a, float* b, void* a_bf16, long n, void* stream) {

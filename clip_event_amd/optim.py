@@ -47,12 +47,13 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
     TRAINABLE parameters; a parameter frozen or unfrozen between steps leaves or joins its group at the next ``step()`` (an
     unfrozen one starts with zero moments, under the one shared step count).
 
-    A subclass names its entry points (``_flat_op(p, g, *state, p16, n, *args, stream)`` on a range of the flat buffers,
-    ``_tiles_op(p, g, *state, p16, jobs, njobs, tiles, segments, nsegments, *args, stream)``, ``_groups_op``: the same with
-    ``segment_group`` behind ``nsegments`` and ``groups, ngroups`` in place of lr / weight decay) and its torch counterpart
-    (``_stock``), and provides ``_state()`` (allocate the flat state buffers and ``sumsq``), ``_step_args(sumsq)`` /
-    ``_group_args(sumsq)`` (the state buffers the kernels take and the rule's scalar arguments, without lr / weight decay in the
-    grouped form) and ``_after_step(sharded)`` (what to note once the step is launched).
+    A subclass names its rule (``_rule``: the entry points are ``ce_<rule>_step(p, g, *state, p16, n, *args, stream)`` on a range of the
+    flat buffers, ``ce_<rule>_step_tiles(p, g, *state, p16, jobs, njobs, tiles, segments, nsegments, *args, stream)`` and
+    ``ce_<rule>_step_groups``: the same with ``segment_group`` behind ``nsegments`` and ``groups, ngroups`` in place of lr / weight
+    decay), its flat state buffers (``_STATE``: attribute names, in the kernels' order; ``_state()`` allocates them and ``sumsq``) and
+    its torch counterpart (``_stock``), and provides ``_rule_args(sumsq, grouped)`` (the rule's arguments behind the form's, without
+    clip and lr / weight decay in the grouped form), ``_after_step(sharded)`` (what to note once the step is launched) and, where a
+    fresh state buffer means something, ``_new_state()``.
 
     Weight EMA (``enable_ema``; off by default, and then every launch is what it is without it): one more flat fp32 buffer,
     ``ema <- ema + rate (p - ema)`` with ``rate = ema_rate(decay, warmup, ema_updates)``, carried by the SAME kernels as the
@@ -64,6 +65,7 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
     and swaps the training weights back on exit."""
 
     _GROUP_KEYS = ("lr", "weight_decay")       # what a group may set for itself; everything else is shared
+    _STATE = ()                                # the flat fp32 state buffers: attribute names, in the order the kernels take them
 
     def __init__(self, model, max_norm, defaults, groups=None):
         name = type(self).__name__
@@ -181,13 +183,9 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
             sumsq.zero_()
             check(lib().ce_sumsq_segments(ptr(m._flat_grad), ptr(plan.chunks), plan.chunks.shape[0], ptr(sumsq), s),
                   "ce_sumsq_segments")
-        state, args = self._group_args(sumsq)
         tj, tn_, tt = plan.tjobs
-        suffix, ema = self._ema_args()
-        check(getattr(lib(), self._groups_op + suffix)(ptr(m._flat), ptr(m._flat_grad), *(ptr(b) for b in state), ptr(m._flat16),
-                                                       ptr(tj), tn_, tt, ptr(plan.segments), plan.segments.shape[0],
-                                                       ptr(plan.segment_group), ptr(sumsq), self.max_norm or 0.0, garr,
-                                                       len(garr), *args, *ema, s), self._groups_op + suffix)
+        self._launch("groups", (ptr(tj), tn_, tt, ptr(plan.segments), plan.segments.shape[0], ptr(plan.segment_group), ptr(sumsq),
+                                self.max_norm or 0.0, garr, len(garr)), self._rule_args(sumsq, True), s)
         # a frozen range was not touched: its mirror and W^T copy were current before the step and its master did not move
         m.mark_operands_stale(mirror_fresh=True, wt_fresh=tiles)
 
@@ -227,13 +225,6 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
             self.ema = flat.detach().clone()
             self._ema_of = flat
             self.ema_updates = 0
-
-    def _ema_args(self, lo=None, hi=None):
-        """``(suffix of the entry point, the two arguments in front of the stream)`` of this step."""
-        if not self.ema_enabled:
-            return "", ()
-        e = self.ema if lo is None else self.ema[lo:hi]
-        return "_ema", (ptr(e), ema_rate(self.ema_decay, self.ema_warmup, self.ema_updates))
 
     def _swap_average(self):
         m = self.model
@@ -347,51 +338,84 @@ class _FusedFlatOptimizer(torch.optim.Optimizer):
         sumsq = self.sumsq if self.max_norm is not None else None
         if not self._plain():
             self._grouped_step(sumsq, s)
-            self._after_step(False)
-            self.ema_updates += int(self.ema_enabled)
-            if self.sat_poll_every and self.step_count % self.sat_poll_every == 0 and hasattr(m, "poll_stream16_saturation"):
-                m.poll_stream16_saturation()
-            return
-        state, args = self._step_args(sumsq)
-
-        def sum_squares(lo, hi):
-            check(lib().ce_sumsq(ptr(m._flat_grad[lo:hi]), hi - lo, ptr(self.sumsq), s), "ce_sumsq")
-
-        def update(lo, hi):
-            suffix, ema = self._ema_args(lo, hi)
-            check(getattr(lib(), self._flat_op + suffix)(ptr(m._flat[lo:hi]), ptr(m._flat_grad[lo:hi]),
-                                                         *(ptr(b if b is None else b[lo:hi]) for b in state),      # (None: SGD without momentum)
-                                                         ptr(m._flat16[lo:hi]), hi - lo, *args, *ema, s), self._flat_op + suffix)
-
-        if sharded:
-            # sharded step (distributed.ShardPlan; DESIGN 5 lever 2): the gradient pieces arrived reduce-SCATTERED, this rank updates
-            # its shard of every piece (+ the replicated head range), the fp32 masters are completed by an all-gather in place and
-            # the bf16 operand mirror is re-cast from them by the next refresh_operands; the optimiser state stays sharded
-            D.sharded_update(plan, m._flat, sumsq, sum_squares, update)
-            m.mark_operands_stale(mirror_fresh=False)
         else:
-            if sumsq is not None:
-                sumsq.zero_()
-                sum_squares(0, n)
-            if getattr(m, "_adam_tiles_ok", False) and os.environ.get("CE_ADAM_TILES", "1") != "0":
-                # the block weights tile by tile, which also writes their W^T operand copies (no transpose pass at the start of the
-                # next step); everything else by the chunk table of the first-touch zero-fill (= the complement of the block weights)
-                tj, tn_, tt = m._tjobs_bwd
-                seg = m._adam_segment_table()
-                suffix, ema = self._ema_args()
-                check(getattr(lib(), self._tiles_op + suffix)(ptr(m._flat), ptr(m._flat_grad), *(ptr(b) for b in state), ptr(m._flat16),
-                                                              ptr(tj), tn_, tt, ptr(seg), seg.shape[0], *args, *ema, s),
-                      self._tiles_op + suffix)
-                m.mark_operands_stale(mirror_fresh=True, wt_fresh=True)
+            args = self._rule_args(sumsq, False)
+
+            def sum_squares(lo, hi):
+                check(lib().ce_sumsq(ptr(m._flat_grad[lo:hi]), hi - lo, ptr(self.sumsq), s), "ce_sumsq")
+
+            def update(lo, hi):
+                self._launch("", (hi - lo,), args, s, lo, hi)
+
+            if sharded:
+                # sharded step (distributed.ShardPlan; DESIGN 5 lever 2): the gradient pieces arrived reduce-SCATTERED, this rank updates
+                # its shard of every piece (+ the replicated head range), the fp32 masters are completed by an all-gather in place and
+                # the bf16 operand mirror is re-cast from them by the next refresh_operands; the optimiser state stays sharded
+                D.sharded_update(plan, m._flat, sumsq, sum_squares, update)
+                m.mark_operands_stale(mirror_fresh=False)
             else:
-                update(0, n)
-                m.mark_operands_stale(mirror_fresh=True)
+                if sumsq is not None:
+                    sumsq.zero_()
+                    sum_squares(0, n)
+                if getattr(m, "_adam_tiles_ok", False) and os.environ.get("CE_ADAM_TILES", "1") != "0":
+                    # the block weights tile by tile, which also writes their W^T operand copies (no transpose pass at the start of the
+                    # next step); everything else by the chunk table of the first-touch zero-fill (= the complement of the block weights)
+                    tj, tn_, tt = m._tjobs_bwd
+                    seg = m._adam_segment_table()
+                    self._launch("tiles", (ptr(tj), tn_, tt, ptr(seg), seg.shape[0]), args, s)
+                    m.mark_operands_stale(mirror_fresh=True, wt_fresh=True)
+                else:
+                    update(0, n)
+                    m.mark_operands_stale(mirror_fresh=True)
+        # every path ends here, the grouped and the sharded one included
         self._after_step(sharded)
         self.ema_updates += int(self.ema_enabled)
         # fp16 streams: look at the clamp counters every few steps, without a synchronisation (the copy started by one poll is
-        # examined by the next); raises model.Stream16Saturation.  On every exit of step(), the sharded one included.
+        # examined by the next); raises model.Stream16Saturation
         if self.sat_poll_every and self.step_count % self.sat_poll_every == 0 and hasattr(m, "poll_stream16_saturation"):
             m.poll_stream16_saturation()
+
+    def _launch(self, form, operands, args, s, lo=None, hi=None):
+        """One update launch: ``ce_<rule>_step`` (``form`` ""; on ``[lo, hi)`` of the flat buffers), ``..._tiles`` or ``..._groups``
+        (on the whole buffers), its ``_ema`` twin while the average is on -- the one place where an entry point gets its name.
+        ``operands``: the form's between ``p_bf16`` and the rule's ``args``."""
+        m = self.model
+        name = f"ce_{self._rule}_step" + (form and "_" + form) + ("_ema" if self.ema_enabled else "")
+        state = (getattr(self, b) if b in self._state_names() else None for b in self._STATE)      # (None: SGD without momentum)
+
+        def at(b):
+            return ptr(b if b is None or lo is None else b[lo:hi])
+
+        ema = (at(self.ema), ema_rate(self.ema_decay, self.ema_warmup, self.ema_updates)) if self.ema_enabled else ()
+        check(getattr(lib(), name)(at(m._flat), at(m._flat_grad), *map(at, state), at(m._flat16), *operands, *args, *ema, s), name)
+
+    # ---- the flat state buffers ----
+    def _state_names(self):
+        """The buffers of ``_STATE`` this optimiser keeps (SGD: none at momentum 0; the kernels then get NULL)."""
+        return self._STATE
+
+    def _state(self):
+        """Make ``sumsq`` and the flat state buffers exist for the model's present flat buffer (its size, its device); a buffer
+        that had to be created starts at zero, and the subclass is told (``_new_state``)."""
+        m = self.model
+        m._ready()
+        flat = m._flat
+        if self.sumsq is None or self.sumsq.device != flat.device:
+            self.sumsq = torch.zeros(1, dtype=torch.float32, device=flat.device)
+        for name in self._state_names():
+            buf = getattr(self, name)
+            if buf is None or buf.numel() != flat.numel() or buf.device != flat.device:
+                setattr(self, name, torch.zeros_like(flat))
+                self._new_state()
+
+    def _new_state(self):
+        pass
+
+    def state_buffers(self):
+        """The flat optimiser state tensors (what ``distributed.consolidate`` gathers after sharded steps): Adam ``(m, v)``, SGD
+        ``(buf,)`` or ``()`` without momentum, Lion ``(exp_avg,)``."""
+        self._state()
+        return tuple(getattr(self, name) for name in self._state_names())
 
     def _params(self):
         """Every parameter of every group, in group order: torch's state indices run consecutively over them."""
@@ -462,7 +486,7 @@ class FusedAdam(_FusedFlatOptimizer):
     ``exp_avg_sq``): the ``'optimizer'`` entry of a reference checkpoint (engine.py:202-218) loads here and vice
     versa.  The moments themselves live in two flat buffers next to the flat parameters."""
 
-    _flat_op, _tiles_op, _groups_op, _stock = "ce_adam_step", "ce_adam_step_tiles", "ce_adam_step_groups", "torch.optim.Adam"
+    _rule, _STATE, _stock = "adam", ("m", "v"), "torch.optim.Adam"
     _GROUP_KEYS = ("lr", "weight_decay", "decoupled")
 
     def __init__(self, model, lr: float = 1e-6, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
@@ -489,25 +513,10 @@ class FusedAdam(_FusedFlatOptimizer):
     def eps(self):
         return self.param_groups[0]["eps"]
 
-    def _state(self):
-        m = self.model
-        m._ready()
-        if self.m is None or self.m.numel() != m._flat.numel() or self.m.device != m._flat.device:
-            self.m = torch.zeros_like(m._flat)
-            self.v = torch.zeros_like(m._flat)
-            self.sumsq = torch.zeros(1, dtype=torch.float32, device=m._flat.device)
-
-    def state_buffers(self):
-        """The flat optimiser state tensors (what ``distributed.consolidate`` gathers after sharded steps)."""
-        self._state()
-        return (self.m, self.v)
-
-    def _step_args(self, sumsq):
-        return (self.m, self.v), (ptr(sumsq), self.max_norm or 0.0, float(self.lr), self.betas[0],
-                                  self.betas[1], self.eps, self.weight_decay, self.step_count)
-
-    def _group_args(self, sumsq):
-        return (self.m, self.v), (self.betas[0], self.betas[1], self.eps, self.step_count)
+    def _rule_args(self, sumsq, grouped):
+        if grouped:
+            return (self.betas[0], self.betas[1], self.eps, self.step_count)
+        return (ptr(sumsq), self.max_norm or 0.0, float(self.lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count)
 
     def _after_step(self, sharded):
         if sharded:
@@ -551,7 +560,7 @@ class FusedSGD(_FusedFlatOptimizer):
     as in torch, "first step" means "no buffer yet", not a counter (the arithmetic never reads ``step_count``): the first step
     copies the decayed gradient into it whatever the dampening is."""
 
-    _flat_op, _tiles_op, _groups_op, _stock = "ce_sgd_step", "ce_sgd_step_tiles", "ce_sgd_step_groups", "torch.optim.SGD"
+    _rule, _STATE, _stock = "sgd", ("buf",), "torch.optim.SGD"
 
     def __init__(self, model, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
                  nesterov: bool = False, max_norm=1.0, groups=None):
@@ -573,36 +582,19 @@ class FusedSGD(_FusedFlatOptimizer):
     def momentum(self):
         return self.param_groups[0]["momentum"]
 
-    def _state(self):
-        m = self.model
-        m._ready()
-        flat = m._flat
-        if self.sumsq is None or self.sumsq.device != flat.device:
-            self.sumsq = torch.zeros(1, dtype=torch.float32, device=flat.device)
-        if self.momentum != 0 and (self.buf is None or self.buf.numel() != flat.numel() or self.buf.device != flat.device):
-            self.buf = torch.zeros_like(flat)
-            self._has_buf = False
+    def _state_names(self):
+        return self._STATE if self.momentum != 0 else ()       # no buffer at momentum 0
 
-    def state_buffers(self):
-        """``(buf,)``, or ``()`` when there is no momentum."""
-        self._state()
-        return (self.buf,) if self.momentum != 0 else ()
+    def _new_state(self):
+        self._has_buf = False
 
-    def _step_args(self, sumsq):
-        group = self.param_groups[0]
-        if group.get("maximize"):
-            raise NotImplementedError("FusedSGD: maximize is not supported")
-        lr, mu, damp, wd = (float(group[k]) for k in ("lr", "momentum", "dampening", "weight_decay"))
-        return (self.buf if mu != 0 else None,), (ptr(sumsq), self.max_norm or 0.0, lr, mu, damp,
-                                                  wd, int(bool(group["nesterov"])), int(not self._has_buf))
-
-    def _group_args(self, sumsq):
+    def _rule_args(self, sumsq, grouped):
         group = self.param_groups[0]
         if any(g.get("maximize") for g in self.param_groups):
             raise NotImplementedError("FusedSGD: maximize is not supported")
-        mu, damp = float(group["momentum"]), float(group["dampening"])
-        return (self.buf if mu != 0 else None,), (mu, damp, int(bool(group["nesterov"])),
-                                                  int(not self._has_buf))
+        lr, mu, damp, wd = (float(group[k]) for k in ("lr", "momentum", "dampening", "weight_decay"))
+        flags = (int(bool(group["nesterov"])), int(not self._has_buf))
+        return (mu, damp, *flags) if grouped else (ptr(sumsq), self.max_norm or 0.0, lr, mu, damp, wd, *flags)
 
     def _after_step(self, sharded):
         if sharded:
@@ -651,8 +643,7 @@ class FusedLion(_FusedFlatOptimizer):
     layout of the common Lion implementations (timm, lion-pytorch): per-parameter ``{"exp_avg": tensor}``, group keys ``lr`` /
     ``betas`` / ``weight_decay``, an empty state before the first step."""
 
-    _flat_op, _tiles_op, _groups_op = "ce_lion_step", "ce_lion_step_tiles", "ce_lion_step_groups"
-    _stock = "a stock Lion (timm.optim.Lion, lion_pytorch.Lion)"
+    _rule, _STATE, _stock = "lion", ("exp_avg",), "a stock Lion (timm.optim.Lion, lion_pytorch.Lion)"
 
     def __init__(self, model, lr: float = 1e-4, betas=(0.9, 0.99), weight_decay: float = 0.0, max_norm=1.0, groups=None):
         if not 0.0 <= lr:
@@ -677,26 +668,12 @@ class FusedLion(_FusedFlatOptimizer):
     def betas(self):
         return self.param_groups[0]["betas"]
 
-    def _state(self):
-        m = self.model
-        m._ready()
-        flat = m._flat
-        if self.exp_avg is None or self.exp_avg.numel() != flat.numel() or self.exp_avg.device != flat.device:
-            self.exp_avg = torch.zeros_like(flat)
-            self.sumsq = torch.zeros(1, dtype=torch.float32, device=flat.device)
-            self._has_state = False
+    def _new_state(self):
+        self._has_state = False
 
-    def state_buffers(self):
-        """``(exp_avg,)``: the one flat state tensor (what ``distributed.consolidate`` gathers after sharded steps)."""
-        self._state()
-        return (self.exp_avg,)
-
-    def _step_args(self, sumsq):
-        return (self.exp_avg,), (ptr(sumsq), self.max_norm or 0.0, float(self.lr), float(self.betas[0]), float(self.betas[1]),
-                                 float(self.weight_decay))
-
-    def _group_args(self, sumsq):
-        return (self.exp_avg,), (float(self.betas[0]), float(self.betas[1]))
+    def _rule_args(self, sumsq, grouped):
+        b1, b2 = float(self.betas[0]), float(self.betas[1])
+        return (b1, b2) if grouped else (ptr(sumsq), self.max_norm or 0.0, float(self.lr), b1, b2, float(self.weight_decay))
 
     def _after_step(self, sharded):
         if sharded:

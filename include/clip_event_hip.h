@@ -413,7 +413,9 @@ int ce_sumsq(const float* g, long n, float* out, void* stream);
 /* base[table[2b] .. table[2b+1]) = 0 for b < nchunks (element offsets, multiples of 4, in DEVICE memory): the gradient
  * zero-fill of a step restricted to the tensors that are accumulated into (ce_tower_desc.wgrad_overwrite) */
 int ce_zero_segments(float* base, const long* table_device, int nchunks, void* stream);
-/* p_bf16 (nullable): bf16 mirror of the updated parameters, same flat layout (the GEMM operand copies) */
+/* p_bf16 (nullable): bf16 mirror of the updated parameters, same flat layout (the GEMM operand copies).  -EINVAL for step < 1,
+ * n <= 0 and p, g, m or v NULL -- every step entry point below refuses NULL p / g / state buffers (and, in the tile and group forms,
+ * NULL p_bf16) before any launch */
 int ce_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* sumsq, float max_norm,
                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
 /* dst[c][r] = src[r][c] (bf16, dense) for a device table of matrices in one launch; tile_start = running
